@@ -120,6 +120,30 @@ def cpu_baseline(packed_frame: np.ndarray):
                       f"(oracle/isp_oracle.py), host has {ncores} cores"}
 
 
+DUMP_VALUES = 8 << 20       # --dump-outputs: at most this many float32 values per output list (32 MB)
+DUMP_SEED = 20260415        # --dump-outputs: the sampled pixels are the same from run to run and from build to build
+
+
+def dump_outputs(path, name, outputs):
+    """--dump-outputs: `outputs` (the frames one step returned, all of one shape (H, W, C)) as float32 in path/<name>.npy.
+    Whole when they fit DUMP_VALUES; otherwise the same seeded sample of pixels (all channels) of every frame:
+    <name>.npy is (frames, pixels, C) and <name>_pixels.npy the flat pixel indices (y * W + x) sampled, as float64."""
+    os.makedirs(path, exist_ok=True)
+    shape = tuple(outputs[0].shape)
+    assert all(tuple(o.shape) == shape for o in outputs) and len(shape) == 3, "dump_outputs: frames of one (H, W, C) shape"
+    n_px, C = shape[0] * shape[1], shape[2]
+    if len(outputs) * n_px * C <= DUMP_VALUES:
+        arr = torch.stack([o.float() for o in outputs]).cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), arr)
+        return
+    n_sample = max(1, DUMP_VALUES // (len(outputs) * C))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, size=n_sample, replace=False))
+    idx_dev = torch.from_numpy(idx).to(outputs[0].device)
+    arr = torch.stack([o.reshape(n_px, C)[idx_dev].float() for o in outputs]).cpu().numpy()
+    np.save(os.path.join(path, f"{name}.npy"), arr)
+    np.save(os.path.join(path, f"{name}_pixels.npy"), idx.astype(np.float64))
+
+
 def host_frames(first, count, distinct):
     """`distinct` different synthetic frames (seeds 1234 + index), generated on a thread pool (3 s of numpy
     each), cycled over `count` slots.  Returns (list of the distinct host frames, index of every slot)."""
@@ -211,7 +235,13 @@ def isp_workload(args, rank, world, device):
 
     from taichi_image_amd import distributed as tdist
     local = []
+    last = []
+    if args.dump_outputs:
+        step_run = step
+        step = lambda: last.__setitem__(slice(None), step_run())   # keep what the step returned (the u8 frames)
     elapsed = timed(step, args.steps, args.warmup, device, barrier, local)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "outputs", last)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=reduce_device(device))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -450,7 +480,15 @@ def main():
                          "tonemap_reinhard(gamma=0.6), config 3 | isp-shared-stats: the same with the rolling metering "
                          "statistics all-reduced over the ranks (config 5) | camera-group[-shared-stats]: full-resolution "
                          "Camera16.process_packed12 (the reference bench's step as one call), optionally with the shared metering")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step computed (rank 0's output frames) to "
+                         "DIR/outputs.npy as float32: a seeded sample of pixels of every frame when they exceed 32 MB, the "
+                         "sampled pixel indices in DIR/outputs_pixels.npy; same inputs on every run, for comparing builds")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
     isp = args.workload != "config2"
     if args.steps is None:
         args.steps = 200 if isp else 160
@@ -536,6 +574,10 @@ def main():
     _native.check(_native.lib().mi_isp_profile_collect(live_us, ctypes.byref(live_n)))
     _native.check(_native.lib().mi_isp_profile_enable(0, 1))
     faults = len(bp.check(frames)) if whole else 0          # after the timed region: every output valid, or repaired and counted
+    if args.dump_outputs and rank == 0:
+        # the last timed step's f16 frames, before anything behind the timed region writes bp.outputs again
+        torch.cuda.synchronize(device)
+        dump_outputs(args.dump_outputs, "outputs", bp.outputs)
     per_rank = rank_stats(elapsed_local, args.frames, args.steps, world, device)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=reduce_device(device))
