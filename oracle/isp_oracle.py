@@ -36,6 +36,13 @@ Conventions: arrays are [row, col] / [row, col, ch]; dtypes are the strings
 
 Defined behaviour where the reference is undefined (fptoui of NaN / out-of-range):
 NaN -> 0 and saturation to the integer range.
+
+NaN rule (every reduction here, in the C restatement and in the kernels): min / max IGNORE NaN - they are fminf / fmaxf,
+as ti.min / ti.max lower to, and that includes the max(gray, 1e-4) clamp in front of the log (a NaN gray enters the log
+statistics as log(1e-4)) - while sums PROPAGATE it, as the reference's atomic adds do.  So a NaN on the metering
+subsample (the p = NaN camera_isp.py:211 writes back over black pixels with light_adapt == 1) leaves the bounds and the
+log bounds finite and turns the means it reaches into NaN.  A subsample that is all NaN has bounds (inf, -inf).
+pow is powf (np.power): a negative base with an integral exponent is defined ((-0.3)^2 = 0.09), with any other NaN.
 """
 from __future__ import annotations
 
@@ -371,7 +378,8 @@ def metering_partials_bounds(images, stride: int = 8):
     lo, hi = np.inf, -np.inf
     for im in images:
         s = im[::stride, ::stride, :].astype(f32)
-        lo, hi = min(lo, float(s.min())), max(hi, float(s.max()))
+        if not np.isnan(s).all():                       # NaN is ignored by min / max (module docstring)
+            lo, hi = min(lo, float(np.nanmin(s))), max(hi, float(np.nanmax(s)))
     return np.array([lo, hi], dtype=f32)
 
 
@@ -386,7 +394,7 @@ def metering_partials_sums(images, b, stride: int = 8):
         s = im[::stride, ::stride, :].astype(f32)
         sc = (s - bmin) / (bmax - bmin + f32(1e-6))
         g = (sc[..., 0] * GRAY_W[0] + sc[..., 1] * GRAY_W[1]) + sc[..., 2] * GRAY_W[2]
-        lg = np.log(np.maximum(g, f32(1e-4)))
+        lg = np.log(np.fmax(g, f32(1e-4)))                 # ti.max is fmaxf: a NaN gray clamps to 1e-4
         lmin, lmax = min(lmin, float(np.nanmin(lg))), max(lmax, float(np.nanmax(lg)))
         sums += [lg.sum(dtype=np.float64), g.sum(dtype=np.float64),
                  sc[..., 0].sum(dtype=np.float64), sc[..., 1].sum(dtype=np.float64),

@@ -740,15 +740,11 @@ __global__ __launch_bounds__(PASS_THREADS, 4) void rgb_pass_kernel(const PassArg
       }
     }
     if (P2ANY) {                                     // camera_isp.py:217-218 (no clamp there)
-      if (a.gamma_inv != 1.f) {
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int j = 0; j < 24; ++j) o[j] = hw_pow(o[j], a.gamma_inv);
-      }
+      if (a.gamma_inv != 1.f) pow_n(o, a.gamma_inv);   // (even 1/gamma: powf of the bases below the bounds)
 #pragma unroll
       for (int j = 0; j < 24; ++j) o[j] *= 255.f;
     }
-    if (MODE == PM_LINEAR_STORE) linear_n<24>(o, lo, inv, a.gamma_inv, a.out_scale);
+    if (MODE == PM_LINEAR_STORE) linear_n<24, true>(o, lo, inv, a.gamma_inv, a.out_scale);   // (also the ISP's linear_kernel)
     if (MODE == PM_RH_STORE) linear_n<24>(o, lo2, inv2, a.gamma_inv, a.out_scale);
     if (MODE == PM_ISP_RH_P1 && a.no_writeback) {
       // (nothing to store: pass 2 recomputes p from the image)
@@ -1039,11 +1035,7 @@ __global__ __launch_bounds__(ISPF_THREADS, BPC) void isp_reinhard_fused_kernel(c
         }
 #pragma unroll
         for (int i = 0; i < 24; ++i) o[i] *= maxout_inv;
-        if (a.gamma_inv != 1.f) {
-          asm volatile("" ::: "memory");
-#pragma unroll
-          for (int j = 0; j < 24; ++j) o[j] = hw_pow(o[j], a.gamma_inv);
-        }
+        if (a.gamma_inv != 1.f) pow_n(o, a.gamma_inv);   // (even 1/gamma: powf of the bases below the bounds)
         uint8_t ot[24];
 #pragma unroll
         for (int i = 0; i < 24; ++i) ot[i] = cast_out<uint8_t>(o[i] * 255.f);    // no clamp there; the cast saturates, NaN -> 0
@@ -1109,11 +1101,7 @@ __global__ __launch_bounds__(EW_THREADS) void isp_p2_yuv420_kernel(const ew::Ptr
     for (int dr = 0; dr < 2; ++dr) {
 #pragma unroll
       for (int j = 0; j < 24; ++j) a[dr][j] *= maxout_inv;
-      if (gamma_inv != 1.f) {
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int j = 0; j < 24; ++j) a[dr][j] = hw_pow(a[dr][j], gamma_inv);
-      }
+      if (gamma_inv != 1.f) pow_n(a[dr], gamma_inv);   // (even 1/gamma: powf of the bases below the bounds)
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float rgb[3];

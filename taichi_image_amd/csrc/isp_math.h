@@ -10,7 +10,8 @@
 MI_DEV float hw_log2(float x) { return __builtin_amdgcn_logf(x); }
 MI_DEV float hw_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 MI_DEV float hw_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-// pow for the bases that occur here: b == 0 -> 0 (e > 0), b < 0 -> NaN, like powf.
+// exp2(e log2 b): b == 0 -> 0 (e > 0), b < 0 -> NaN - powf only for a non-integral e (the Reinhard adaptation's map_key).
+// An exponent that may be integral and meet negative bases goes through pow_n.
 MI_DEV float hw_pow(float b, float e) { return hw_exp2(e * hw_log2(b)); }
 MI_DEV float hw_log(float x) { return hw_log2(x) * 0.6931471805599453f; }
 
@@ -101,12 +102,41 @@ MI_DEV float linear_px(float x, float lo, float inv, float gamma_inv, float scal
 #ifndef MI_CENSUS_GAMMA            /* reading aid of scripts/isa_census.py: gamma == 1 as a constant */
 #define MI_CENSUS_GAMMA(expr) (expr)
 #endif
+// pow(v, e) of N values for an exponent uniform over the call (1/gamma), for callers that clamp the result at 0 (the u8
+// casts, clamp01).  The ISP's bases go negative for every pixel below the metering bounds, and powf of a negative base is
+// defined for an integral e: |v|^e for an even e - which survives the clamp - and -|v|^e for an odd one, which the clamp
+// maps to 0 as it maps the NaN of exp2(e log2 v).  So only an even e needs more than hw_pow: |v| first, behind a scalar
+// branch decided once per call; the values of any other exponent cost what they did.  (The |v| as a source modifier of
+// v_log_f32 means a second copy of the pow loop: the kernels at the register limit spilled to scratch.)
+MI_DEV bool even_integral(float e) { return __builtin_fabsf(e) >= 16777216.f || (e == __builtin_truncf(e) && !((int)e & 1)); }
 template <int N>
-MI_DEV void linear_n(float (&v)[N], float lo, float inv, float gamma_inv, float scale) {
-  if (MI_CENSUS_GAMMA(gamma_inv != 1.f)) {
+MI_DEV void pow_n(float (&v)[N], float e) {
+  if (even_integral(e)) {
     asm volatile("" ::: "memory");
 #pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = clamp01(hw_pow((v[i] - lo) * inv, gamma_inv)) * scale;
+    for (int i = 0; i < N; ++i) v[i] = __builtin_fabsf(v[i]);
+  }
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = hw_pow(v[i], e);
+}
+
+// SIGNED: the bounds are not those of the image (the ISP's metering state), so bases below them are negative (pow_n).
+// The stateless chains' bases are >= 0 or NaN.
+template <int N, bool SIGNED = false>
+MI_DEV void linear_n(float (&v)[N], float lo, float inv, float gamma_inv, float scale) {
+  if (MI_CENSUS_GAMMA(gamma_inv != 1.f)) {
+    if constexpr (SIGNED) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) v[i] = (v[i] - lo) * inv;
+      pow_n(v, gamma_inv);
+#pragma unroll
+      for (int i = 0; i < N; ++i) v[i] = clamp01(v[i]) * scale;
+    } else {
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int i = 0; i < N; ++i) v[i] = clamp01(hw_pow((v[i] - lo) * inv, gamma_inv)) * scale;
+    }
   } else {
     // gamma == 1: clamp(x, 0, 1) * scale == med3(x * scale, 0, scale) up to one rounding
     const float inv_s = inv * scale;

@@ -328,11 +328,7 @@ __global__ __launch_bounds__(THREADS, 2) void camera_kernel(const CBatch cb) {
     // p / max_out straight from the packed halves (v_fma_mix_f32 with a zero addend: the half is widened exactly, the product
     // rounded once - the bits of converting first and multiplying, one instruction instead of two)
     static_for<0, 24>([&](auto ec) { constexpr int e = decltype(ec)::value; o[e] = mul_mix_h<e>(pk[e / 2], maxout_inv); });
-    if (gamma_inv != 1.f) {
-      asm volatile("" ::: "memory");                    // (a real branch: see linear_n)
-#pragma unroll
-      for (int j = 0; j < 24; ++j) o[j] = hw_pow(o[j], gamma_inv);
-    }
+    if (gamma_inv != 1.f) pow_n(o, gamma_inv);   // (even 1/gamma: powf of the bases below the bounds)
 #pragma unroll
     for (int j = 0; j < 24; ++j) o[j] *= 255.f;
     // staging: the LDS slot of a row that has been consumed (its own, or row 0's for the register rows)

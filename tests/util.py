@@ -128,3 +128,65 @@ def reuse_case(ti, dev, cam, frames, sequence, alpha=0.3):
     stale = c_oracle.IspState(alpha)
     stale.update_metering(refs)
     assert not np.allclose(stale.update_metering(refs), m2, rtol=1e-3), "the sequence does not tell stale from fresh"
+
+
+def scene_cut_state(rng, H, W, bright, work="f16", alpha=0.3):
+    """A scene cut: the metering state of a group of the other brightness (`bright=True`: the state of a bright group,
+    for a dark group to follow; False: a dark state before a bright group).  Seeded as the previous state, it puts
+    pixels of the next group below bmin (scaled < 0) and above bmax (scaled > 1)."""
+    frames = [natural_packed12(rng, H, W, dark=(-0.35 if bright else 0.6) + 0.02 * k) for k in range(2)]
+    return O.IspState(alpha).update_metering([O.isp_load_packed12(f, work) for f in frames])
+
+
+def scene_cut_frames(rng, H, W, bright, n=2):
+    """The group that follows `scene_cut_state(bright)`: the opposite brightness.  The dark group carries colour patches
+    (red and green sites at a ramp of levels, blue sites black): pixels with a channel below bmin and a positive gray,
+    whose p < 0 the Reinhard output maps through the gamma curve - visibly for an even 1/gamma."""
+    if not bright:
+        return [natural_packed12(rng, H, W, dark=-0.4 + 0.03 * k) for k in range(n)]
+    frames = []
+    for k in range(n):
+        v12 = O.decode12(natural_packed12(rng, H, W, dark=0.55 + 0.03 * k), "u16")
+        i = 0
+        for r0 in range(4, H - 12, 24):
+            for c0 in range(4, W - 12, 24):
+                patch = v12[r0:r0 + 12, c0:c0 + 12]
+                patch[...] = 1500 + (i * 97) % 1500
+                patch[1::2, 1::2] = 0
+                i += 1
+        frames.append(O.encode12(v12))
+    return frames
+
+
+def degenerate_cfa(kind, H, W, rng=None):
+    """12-bit CFA frames where the bounds collapse or sit exactly at (0, 1): lens cap, blown out, flat grey card,
+    binary 0/4095, one non-black pixel."""
+    if kind == "zero":
+        return np.zeros((H, W), np.uint16)
+    if kind == "full":
+        return np.full((H, W), 4095, np.uint16)
+    if kind == "flat":
+        return np.full((H, W), 1800, np.uint16)
+    if kind == "binary":
+        rng = rng or np.random.default_rng(5)
+        return (rng.random((H, W)) < 0.5).astype(np.uint16) * 4095
+    if kind == "one":
+        v = np.zeros((H, W), np.uint16)
+        v[H // 2, W // 3] = 3000
+        return v
+    raise ValueError(kind)
+
+
+DEGENERATE = ["zero", "full", "flat", "binary", "one"]
+# 1/gamma in f32 is exactly 2, 4, 3, 1.667, 1 and 0.4545: even and odd integral exponents and non-integral ones
+GAMMAS = [0.5, 0.25, 1.0 / 3.0, 0.6, 1.0, 2.2]
+
+
+def nan_on_grid(img, stride=8, where=((0, 0), (-1, -1)), ch=1):
+    """A copy of an (H, W, 3) float image with NaN at sample points of the stride grid (last grid row / column for -1)."""
+    out = np.array(img, copy=True)
+    H, W = out.shape[:2]
+    last_r, last_c = (H - 1) // stride * stride, (W - 1) // stride * stride
+    for r, c in where:
+        out[last_r if r == -1 else r, last_c if c == -1 else c, ch] = np.nan
+    return out
