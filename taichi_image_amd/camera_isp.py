@@ -119,6 +119,14 @@ def camera_isp(name: str, dtype=types.f32):
             image.data_ptr(), output.data_ptr(), H, W, dtype.code, metering.data_ptr(), float(gamma),
             interpolate.transform_code(transform), ws.data_ptr(), _native.stream_ptr(image.device)))
 
+    def _check_transform(images, transform):
+        """interpolate.transform's rule, checked before a tonemap touches the metering state: the C entries reject a
+        non-square transverse too, but only after update_metering has already moved the state."""
+        if transform == interpolate.ImageTransform.transverse:
+            for im in images:
+                if isinstance(im, torch.Tensor) and im.ndim >= 2:
+                    assert im.shape[0] == im.shape[1], "transverse is only defined for square images"
+
     def _out_shape(image, transform):
         H, W = image.shape[:2]
         if transform in (interpolate.ImageTransform.rotate_90, interpolate.ImageTransform.rotate_270,
@@ -444,6 +452,7 @@ def camera_isp(name: str, dtype=types.f32):
             for n, v in (("gamma", gamma), ("intensity", intensity), ("light_adapt", light_adapt),
                          ("color_adapt", color_adapt)):
                 _typecheck(n, v, float)
+            _check_transform(images, self.transform)
             self.update_metering(images)
             outputs = [torch.empty(_out_shape(image, self.transform), dtype=torch.uint8, device=self.device)
                        for image in images]
@@ -497,9 +506,10 @@ def camera_isp(name: str, dtype=types.f32):
 
             with the same u8 outputs and the same metering state afterwards, bit for bit.  For a full-resolution
             Camera16 group that fits the chip (`mi_isp_camera_group_fits`: 4096 x 3072 on MI355X, metering stride 8, no
-            resize, no orientation transform, single process) the loaded images never exist in memory: the metering reads
-            a subsample demosaiced straight from the packed frames, and ONE persistent launch takes every camera from
-            packed bytes to its u8 image (csrc/isp_mega_cam.h).  Everything else takes the two calls above.
+            resize, no orientation transform, single process, every packed frame 4-byte aligned) the loaded images never
+            exist in memory: the metering reads a subsample demosaiced straight from the packed frames, and ONE persistent
+            launch takes every camera from packed bytes to its u8 image (csrc/isp_mega_cam.h).  Everything else takes the
+            two calls above.
             keep_images=True returns `(outputs, images)`, the images holding what the reference leaves in them (p,
             camera_isp.py:211); by default only the outputs are returned, as the bench's Processor does."""
             _typecheck("frames", frames, list)
@@ -516,6 +526,10 @@ def camera_isp(name: str, dtype=types.f32):
                      and all(isinstance(f, torch.Tensor) and f.ndim == 2 and f.dtype == torch.uint8 and f.shape == f0.shape
                              for f in frames)
                      and f0.shape[1] % 3 == 0)
+            srcs = [f.to(self.device).contiguous() for f in frames] if fused else None
+            # (the camera-group kernel reads the packed rows as 4-byte words: a frame that is a view at another byte offset
+            # takes the two calls, whose loader reads it byte by byte)
+            fused = fused and all(s.data_ptr() % 4 == 0 for s in srcs)
             if fused and torch.cuda.is_current_stream_capturing():
                 fused = False                  # (a captured resident launch can be neither ordered against others nor checked)
             if fused:
@@ -526,7 +540,6 @@ def camera_isp(name: str, dtype=types.f32):
                 images = self.load_packed12_batch(frames, ids_format)
                 outputs = self.tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt)
                 return (outputs, images) if keep_images else outputs
-            srcs = [f.to(self.device).contiguous() for f in frames]
             with torch.cuda.device(self.device):
                 if L.mi_isp_metering_faults(1):
                     raise MeteringTimeout("an earlier update_metering on this device timed out at its grid barrier: its "
@@ -570,6 +583,7 @@ def camera_isp(name: str, dtype=types.f32):
             """camera_isp.py:405-413."""
             _typecheck("images", images, list)
             _typecheck("gamma", gamma, float)
+            _check_transform(images, self.transform)
             self.update_metering(images)
             outputs = [torch.empty(_out_shape(image, self.transform), dtype=torch.uint8, device=self.device)
                        for image in images]

@@ -742,6 +742,10 @@ extern "C" int mi_isp_camera_frame_batch(const uint8_t* const* packed, void* con
   MI_REQUIRE(n >= 1, "camera_frame_batch: need at least one camera");
   MI_REQUIRE(tonemap == 0 || tonemap == 1, "camera_frame_batch: tonemap must be 0 (reinhard) or 1 (linear)");
   MI_REQUIRE(metering_stride >= 1, "camera_frame_batch: bad metering stride");
+  // (what the tonemap entries would reject, rejected before the metering moves state9)
+  MI_REQUIRE(gamma > 0.f, "camera_frame_batch: gamma must be positive");
+  MI_REQUIRE(transform >= MI_T_NONE && transform <= MI_T_TRANSVERSE, "camera_frame_batch: bad transform");
+  MI_REQUIRE(transform != MI_T_TRANSVERSE || Hd == Wd, "camera_frame_batch: transverse needs a square image");
   for (int i = 0; i < n; ++i) MI_REQUIRE(packed[i] && images[i] && outs[i], "camera_frame_batch: camera %d has a null buffer", i);
   if (int rc = mi_isp_load_packed_batch(packed, images, nullptr, n, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd,
                                         scale, 0, stream))

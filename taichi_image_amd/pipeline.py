@@ -168,7 +168,9 @@ def pipeline12_reinhard(packed, pattern=BayerPattern.RGGB, ids_format=False, cor
     if check is None:
         check = "deferred" if whole_frame is None else False
     if whole_frame is None:
-        whole_frame = not capturing and _auto_whole_frame(H, W, work, odt, ids_format)
+        # (the whole-frame kernel reads the packed rows as 4-byte words: a frame that is a view at another byte offset
+        # takes the multi-pass chain, whose loader reads it byte by byte)
+        whole_frame = not capturing and packed.data_ptr() % 4 == 0 and _auto_whole_frame(H, W, work, odt, ids_format)
     if capturing:
         check = False                                 # (no host-side look is possible at capture time)
     ccm = _native.ccm_arg(correct_colors)

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 from oracle import c_oracle, isp_oracle as O
-from tests.util import assert_close, natural_packed12
+from tests.util import assert_close, assert_exact, natural_packed12
 from taichi_image_amd.synthetic import mosaic_rggb, pack12, synthetic_scene
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not c_oracle.available(), reason="oracle/liborc_isp.so not built")]
@@ -563,3 +563,99 @@ def test_isp_reinhard_4k_one_launch_equals_two_passes(ti, dev, scenes, monkeypat
         assert torch.equal(i1[k].view(torch.int16), i2[k].view(torch.int16)), f"image {k}: in-place p differs"
     from taichi_image_amd import _native
     assert _native.lib().mi_isp_reinhard_faults(1) == 0
+
+
+# ---- the reference's own configurations ----------------------------------------------------------------------------------
+def group_packs(scenes, step):
+    """The packed frames load_group(isp, scenes, step) loads."""
+    return [packed_from(cfa, GAINS[(k + step) % 6] * (1.0 - 0.12 * step), OFFSETS[(k + 2 * step) % 6]) for k, cfa in enumerate(scenes)]
+
+
+def test_reference_test_configuration(ti, dev, scenes):
+    """The reference's only ISP test (test/camera_isp.py:35-39): Camera32(RGGB, moving_alpha=1.0, resize_width=1280) on six
+    cameras, two steps of tonemap_reinhard(gamma=0.6).  The f32 load is the fused one through the resize tile (the
+    streaming resize takes f16 only): bit-exact against the oracle's demosaic + resize; metrics, u8 outputs and the in-place
+    p against the C oracle."""
+    isp = ti.Camera32(ti.BayerPattern.RGGB, moving_alpha=1.0, resize_width=1280, device=dev)
+    st = c_oracle.IspState(1.0)
+    for step in range(2):
+        packs = group_packs(scenes, step)
+        imgs = [isp.load_packed12(torch.from_numpy(p).to(dev)) for p in packs]
+        refs = []
+        for k, p in enumerate(packs):
+            rgb = c_oracle.demosaic(c_oracle.decode12_scaled(p, work="f32").reshape(3072, 4096), 0)
+            refs.append(O.resize_bilinear(rgb, (1280, 960), 1280 / 4096))
+            got = imgs[k].cpu().numpy()
+            assert got.shape == (960, 1280, 3) and got.dtype == np.float32
+            assert_exact(got, refs[k], f"step {step} camera {k}: load_packed12")
+        outs = isp.tonemap_reinhard(imgs, gamma=0.6)
+        m = st.update_metering(refs)
+        assert_close(isp.metrics.cpu().numpy(), m, f"step {step}: metrics", rel=2e-5)
+        for k in range(6):
+            ref_u8, ref_p = c_oracle.reinhard_isp(refs[k], m, gamma=0.6)
+            assert_close(outs[k].cpu().numpy(), ref_u8, f"step {step} camera {k}: u8")
+            assert_close(imgs[k].cpu().numpy(), ref_p, f"step {step} camera {k}: in-place p")
+
+
+def test_reference_bench_configuration(ti, dev, scenes):
+    """The reference's bench (bench/camera_isp.py:39-40): Camera16(moving_alpha=0.1, resize_width=1920, transform=rotate_90),
+    six cameras, three steps: u8 outputs (1920, 1440, 3), the in-place p and the metrics against the C oracle; and
+    process_packed12 on a camera of the same configuration (it takes the two calls) with the same results bit for bit."""
+    def make():
+        return ti.Camera16(ti.BayerPattern.RGGB, moving_alpha=0.1, resize_width=1920, transform=ti.ImageTransform.rotate_90,
+                           device=dev)
+    a, b = make(), make()
+    st = c_oracle.IspState(0.1)
+    for step in range(3):
+        frames = [torch.from_numpy(p).to(dev) for p in group_packs(scenes, step)]
+        imgs = [a.load_packed12(f) for f in frames]
+        refs = [im.cpu().numpy() for im in imgs]                 # (bit-exact: test_isp_load_packed12_config3_full_size)
+        outs = a.tonemap_reinhard(imgs, gamma=0.6)
+        outs_b, imgs_b = b.process_packed12(frames, gamma=0.6, keep_images=True)
+        m = st.update_metering(refs)
+        assert torch.equal(a.metrics, b.metrics), f"step {step}: process_packed12 metrics"
+        assert_close(a.metrics.cpu().numpy(), m, f"step {step}: metrics", rel=2e-5)
+        for k in range(6):
+            assert tuple(outs[k].shape) == (1920, 1440, 3)
+            assert torch.equal(outs[k], outs_b[k]), f"step {step} camera {k}: process_packed12 u8"
+            assert torch.equal(imgs[k].view(torch.int16), imgs_b[k].view(torch.int16)), f"step {step} camera {k}: process_packed12 p"
+            ref_u8, ref_p = c_oracle.reinhard_isp(refs[k], m, gamma=0.6)
+            assert_close(outs[k].cpu().numpy(), O.transform(ref_u8, "rotate_90"), f"step {step} camera {k}: u8")
+            assert_close(imgs[k].cpu().numpy(), ref_p, f"step {step} camera {k}: in-place p")
+
+
+def test_scan_cli_default_camera_full_size(ti, dev, scenes):
+    """The scan CLI's camera with its defaults (taichi_image_amd/scripts/tonemap_scan.py: Camera32, transform rotate_90,
+    gamma 0.9, intensity 3.0, light_adapt 0.9, moving_alpha 0.02) at full resolution, two cameras, one step."""
+    isp = ti.Camera32(ti.BayerPattern.RGGB, moving_alpha=0.02, transform=ti.ImageTransform.rotate_90, device=dev)
+    imgs = [isp.load_packed12(torch.from_numpy(p).to(dev)) for p in group_packs(scenes[:2], 0)]
+    refs = [im.cpu().numpy() for im in imgs]
+    outs = isp.tonemap_reinhard(imgs, gamma=0.9, intensity=3.0, color_adapt=0.0, light_adapt=0.9)
+    m = c_oracle.IspState(0.02).update_metering(refs)
+    assert_close(isp.metrics.cpu().numpy(), m, "metrics", rel=2e-5)
+    for k in range(2):
+        assert tuple(outs[k].shape) == (4096, 3072, 3)
+        ref_u8, ref_p = c_oracle.reinhard_isp(refs[k], m, gamma=0.9, intensity=3.0, light_adapt=0.9, color_adapt=0.0)
+        assert_close(outs[k].cpu().numpy(), O.transform(ref_u8, "rotate_90"), f"camera {k}: u8")
+        assert_close(imgs[k].cpu().numpy(), ref_p, f"camera {k}: in-place p")
+
+
+def test_isp_process_packed12_full_size_with_a_frame_at_a_byte_offset(ti, dev, scenes):
+    """A 4096 x 3072 group with one packed frame 2 bytes off its 4-byte boundary: process_packed12 leaves the camera-group
+    kernel (which reads 4-byte words) to the two calls and equals load_packed12_batch + tonemap_reinhard in outputs, images
+    and metrics."""
+    packs = group_packs(scenes[:3], 0)
+    frames = [torch.from_numpy(p).to(dev) for p in packs]
+    buf = torch.zeros(packs[1].size + 64, dtype=torch.uint8, device=dev)
+    frames[1] = buf[2:2 + packs[1].size].view(packs[1].shape)
+    frames[1].copy_(torch.from_numpy(packs[1]))
+    assert frames[1].is_contiguous() and frames[1].data_ptr() % 4 == 2
+    a = ti.Camera16(ti.BayerPattern.RGGB, moving_alpha=0.3, device=dev)
+    b = ti.Camera16(ti.BayerPattern.RGGB, moving_alpha=0.3, device=dev)
+    outs, images = a.process_packed12(frames, gamma=0.6, keep_images=True)
+    want_images = b.load_packed12_batch(frames)
+    want = b.tonemap_reinhard(want_images, gamma=0.6)
+    assert torch.equal(a.metrics.view(torch.int32), b.metrics.view(torch.int32))
+    for k in range(3):
+        assert torch.equal(outs[k], want[k]), f"camera {k}: u8"
+        assert torch.equal(images[k].view(torch.int16), want_images[k].view(torch.int16)), f"camera {k}: p"

@@ -90,3 +90,30 @@ def test_scan_end_to_end(tmp_path):
     imgs = [isp.load_packed12(torch.from_numpy(frames[(cam, 0)]).to(dev)) for cam in ("cam0", "cam1")]
     want = isp.tonemap_reinhard(imgs, gamma=0.9, intensity=3.0, color_adapt=0.0, light_adapt=0.9)
     assert np.array_equal(got, torch.concat(want, dim=1).cpu().numpy())
+
+
+@pytest.mark.gpu
+def test_scan_with_the_default_transform_against_the_oracle(tmp_path):
+    """The CLI with its defaults (Camera32, transform rotate_90, gamma 0.9, intensity 3.0, light_adapt 0.9,
+    moving_alpha 0.02) on two cameras x two frames of 34 x 130 (the last pixel group of a frame is ragged): every grid
+    against the oracle's rolling metering and tonemap, transformed."""
+    from oracle import isp_oracle as O
+    from tests.util import assert_close, natural_packed12
+    H, W = 34, 130
+    frames = {}
+    for c, cam in enumerate(("cam0", "cam1")):
+        (tmp_path / "scan" / cam).mkdir(parents=True)
+        for k in range(2):
+            frames[(cam, k)] = natural_packed12(np.random.default_rng(10 * c + k), H, W, dark=0.2 * c + 0.05 * k)
+            (tmp_path / "scan" / cam / f"frame{k}.raw").write_bytes(frames[(cam, k)].tobytes())
+    out = tmp_path / "out"
+    assert ts.main(["--scan", str(tmp_path / "scan"), "--width", str(W), "--write", str(out), "--rows", "1"]) == 0
+    st = O.IspState(0.02)
+    for k in range(2):
+        refs = [O.isp_load_packed12(frames[(cam, k)], "f32") for cam in ("cam0", "cam1")]
+        m = st.update_metering(refs)
+        want = np.concatenate([O.transform(O.reinhard_isp(r, m, gamma=0.9, intensity=3.0, light_adapt=0.9, color_adapt=0.0)[0],
+                                           "rotate_90") for r in refs], axis=1)
+        got = _read_png(out / f"frame{k}.png")
+        assert got.shape == (W, 2 * H, 3)
+        assert_close(got, want, f"frame {k}")
