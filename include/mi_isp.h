@@ -211,6 +211,31 @@ int mi_isp_load_packed_metered_is_fused(int H, int W, int bits, int ids_format, 
  * 64x16 destination tile for scale >= ~0.39, any upscale); otherwise demosaic at full size and
  * call mi_isp_resize_bilinear. */
 int mi_isp_load_packed_scale_supported(float scale);
+
+/* ---- sensor black and white levels ------------------------------------------------------------------------------------
+ * A raw code v at CFA site s = (row & 1) * 2 + (col & 1) of the raw frame (whatever the pattern) decodes to
+ *   cast_work(f32(max(v - black[s], 0)) * k[s]),  k[s] = f32(S / (white - black[s])) (computed in double, rounded once),
+ * S the work dtype's scale; no upper clamp (as the unscaled decode).  black[s] = 0 with the container's full scale as
+ * white (4095 packed-12, 65535 packed-16 / u16) is bit-identical to the entry points without levels.  Levels must hold
+ * 0 <= black[s] < white <= 2^bits - 1.  A NULL levels pointer means "no levels": exactly the call without _levels.
+ * One black level for every site is folded into the packed-12 kernels' decode table; four distinct ones are applied in
+ * registers. */
+typedef struct { int32_t black[4]; int32_t white; } mi_isp_levels;
+int mi_isp_load_packed_levels(const uint8_t* packed_dev, void* rgb_dev, int H, int W, int bits, int ids_format,
+                              int pattern, const float* ccm9_host, int work_dtype, int Hd, int Wd, float scale,
+                              const mi_isp_levels* levels_host, void* stream);
+int mi_isp_load_packed_metered_levels(const uint8_t* packed_dev, void* rgb_dev, int H, int W, int bits, int ids_format,
+                                      int pattern, const float* ccm9_host, int work_dtype, int Hd, int Wd, float scale,
+                                      void* sub_dev, int sub_stride, const mi_isp_levels* levels_host, void* stream);
+int mi_isp_load_packed_batch_levels(const uint8_t* const* packed_host, void* const* rgb_host, void* const* subs_host,
+                                    int n, int H, int W, int bits, int ids_format, int pattern, const float* ccm9_host,
+                                    int work_dtype, int Hd, int Wd, float scale, int sub_stride,
+                                    const mi_isp_levels* levels_host, void* stream);
+/* mi_isp_load_convert with levels (mode MI_LOAD_16U only, 16-bit codes, row-major H x W frame for the sites): as that
+ * loader divides - cast_work(f32(max(v - black[s], 0)) / f32(white - black[s])) - instead of multiplying by k[s], so
+ * that black 0 / white 65535 keeps its bits. */
+int mi_isp_load_convert_levels(const void* src_dev, void* dst_dev, int H, int W, int mode, int out_dtype,
+                               const mi_isp_levels* levels_host, void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==
@@ -277,6 +302,23 @@ int mi_isp_camera_group_fits(int H, int W, int pattern, int work_dtype, int mete
 size_t mi_isp_camera_group_scratch_bytes(int n, int H, int W);
 int mi_isp_camera_group_faults(int clear);
 int mi_isp_camera_group_set_poll_limit(unsigned polls);
+/* The camera group with sensor levels (mi_isp_levels above; NULL = the calls without _levels): the subsample and the
+ * persistent launch decode with the levels, one black level folded into the decode table, four applied in registers.
+ * mi_isp_camera_group_fits_levels: as mi_isp_camera_group_fits for the kernel these levels take (0 for invalid levels). */
+int mi_isp_camera_group_reinhard_levels(const uint8_t* const* packed_host, void* const* images_host, uint8_t* const* outs_host,
+                                        int n, int H, int W, int pattern, const float* ccm9_host, const float* prev9_dev,
+                                        float* state9_dev, float alpha, float gamma, float intensity, float light_adapt,
+                                        float color_adapt, void* scratch_dev, void* ws_dev, const mi_isp_levels* levels_host,
+                                        void* stream);
+int mi_isp_camera_group_subsample_levels(const uint8_t* const* packed_host, int n, int H, int W, int pattern,
+                                         const float* ccm9_host, void* scratch_dev, const mi_isp_levels* levels_host,
+                                         void* stream);
+int mi_isp_camera_group_tonemap_levels(const uint8_t* const* packed_host, void* const* images_host, uint8_t* const* outs_host,
+                                       int n, int H, int W, int pattern, const float* ccm9_host, const float* state9_dev,
+                                       float gamma, float intensity, float light_adapt, float color_adapt, void* ws_dev,
+                                       const mi_isp_levels* levels_host, void* stream);
+int mi_isp_camera_group_fits_levels(int H, int W, int pattern, int work_dtype, int metering_stride,
+                                    const mi_isp_levels* levels_host);
 
 /* The same chain (test/pipeline.py:26-32) as ONE persistent launch (csrc/isp_mega.h): the frame is demosaiced once,
  * the f16 RGB image stays in registers and LDS, the three global dependencies of tonemap.py:146-154 are grid

@@ -19,6 +19,12 @@ LIB_PATH = os.environ.get("MI_ISP_LIB") or os.path.join(_HERE, "lib", "libmi355_
 
 MI_U8, MI_U16, MI_F16, MI_F32 = 0, 1, 2, 3
 
+
+class Levels(ctypes.Structure):
+    """mi_isp_levels: the sensor's black level per CFA site ((row & 1) * 2 + (col & 1)) and its white level."""
+    _fields_ = [("black", c_int32 * 4), ("white", c_int32)]
+
+
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SIGNATURES = {
@@ -57,6 +63,14 @@ SIGNATURES = {
                                            c_float, _P, c_int, _P]),
     "mi_isp_load_packed_batch": (c_int, [POINTER(_P), POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
                                          POINTER(c_float), c_int, c_int, c_int, c_float, c_int, _P]),
+    "mi_isp_load_packed_levels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int, c_int,
+                                          c_float, POINTER(Levels), _P]),
+    "mi_isp_load_packed_metered_levels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,
+                                                  c_int, c_float, _P, c_int, POINTER(Levels), _P]),
+    "mi_isp_load_packed_batch_levels": (c_int, [POINTER(_P), POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int,
+                                                c_int, POINTER(c_float), c_int, c_int, c_int, c_float, c_int,
+                                                POINTER(Levels), _P]),
+    "mi_isp_load_convert_levels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Levels), _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,
@@ -77,6 +91,15 @@ SIGNATURES = {
     "mi_isp_camera_group_tonemap": (c_int, [POINTER(_P), POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, POINTER(c_float),
                                             _P, c_float, c_float, c_float, c_float, _P, _P]),
     "mi_isp_camera_group_fits": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "mi_isp_camera_group_reinhard_levels": (c_int, [POINTER(_P), POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int,
+                                                    POINTER(c_float), _P, _P, c_float, c_float, c_float, c_float, c_float, _P,
+                                                    _P, POINTER(Levels), _P]),
+    "mi_isp_camera_group_subsample_levels": (c_int, [POINTER(_P), c_int, c_int, c_int, c_int, POINTER(c_float), _P,
+                                                     POINTER(Levels), _P]),
+    "mi_isp_camera_group_tonemap_levels": (c_int, [POINTER(_P), POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int,
+                                                   POINTER(c_float), _P, c_float, c_float, c_float, c_float, _P,
+                                                   POINTER(Levels), _P]),
+    "mi_isp_camera_group_fits_levels": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(Levels)]),
     "mi_isp_camera_group_scratch_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
     "mi_isp_camera_group_faults": (c_int, [c_int]),
     "mi_isp_camera_group_set_poll_limit": (c_int, [ctypes.c_uint]),
@@ -182,6 +205,13 @@ def ccm_arg(correct_colors):
     m = np.asarray(correct_colors, dtype=np.float64).reshape(-1)
     assert m.size == 9, "colour correction must be a 3x3 matrix"
     return (c_float * 9)(*[float(v) for v in m])
+
+
+def levels_arg(black, white):
+    """(black[4], white) -> a Levels for the *_levels entry points; None (no levels) stays None."""
+    if black is None:
+        return None
+    return Levels((c_int32 * 4)(*[int(b) for b in black]), int(white))
 
 
 _ws_cache: dict = {}

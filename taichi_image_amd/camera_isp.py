@@ -37,6 +37,35 @@ def _typecheck(name, value, kinds, optional=False):
         raise TypeError(f"{name} must be {kinds}, got {type(value).__name__}")
 
 
+def _check_levels(black_level, white_level, bits=16):
+    """The sensor levels as the kernels take them: (black per CFA site (4 ints), white), or None without levels.
+    ValueError unless they are integers with 0 <= black_s < white <= 2**bits - 1; white defaults to the full scale."""
+    if black_level is None and white_level is None:
+        return None
+    top = (1 << bits) - 1
+
+    def _int(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what} must be an integer, got {type(v).__name__}")
+        return int(v)
+
+    if black_level is None:
+        black = [0, 0, 0, 0]
+    elif isinstance(black_level, (list, tuple, np.ndarray)):
+        if len(black_level) != 4:
+            raise ValueError(f"black_level must be one int or 4 (one per CFA site), got {len(black_level)}")
+        black = [_int(b, "black_level") for b in black_level]
+    else:
+        black = [_int(black_level, "black_level")] * 4
+    white = top if white_level is None else _int(white_level, "white_level")
+    if not 0 < white <= top:
+        raise ValueError(f"white_level {white} outside (0, {top}] for a {bits}-bit source")
+    for b in black:
+        if not 0 <= b < white:
+            raise ValueError(f"black_level {b} outside [0, white_level = {white})")
+    return black, white
+
+
 class MeteringTimeout(RuntimeError):
     """The grid barrier of an earlier one-launch update_metering on this device timed out (something else held compute
     units of the GPU for about a second).  That call left the metrics as they were - bounds folded from half of the blocks
@@ -146,7 +175,9 @@ def camera_isp(name: str, dtype=types.f32):
                      device: torch.device = torch.device('cuda', 0),
                      metering_stride: int = 8,
                      process_group=None,
-                     reference_quirks: bool = False):
+                     reference_quirks: bool = False,
+                     black_level=None,
+                     white_level: Optional[int] = None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -157,6 +188,7 @@ def camera_isp(name: str, dtype=types.f32):
             _typecheck("device", device, torch.device)
             _typecheck("metering_stride", metering_stride, int)
             assert scale is None or resize_width == 0, "Cannot specify both scale and resize_width"
+            _check_levels(black_level, white_level)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -174,6 +206,11 @@ def camera_isp(name: str, dtype=types.f32):
             self.white_balance = white_balance
             self.color_correction = color_correction
 
+            # sensor levels (an extension): black per CFA site of the raw frame ((row & 1) * 2 + (col & 1), whatever the
+            # pattern), white; both None: no levels, the loaders run exactly as without them.  DESIGN.md 3.
+            self.black_level = black_level
+            self.white_level = white_level
+
             self.metrics = None
             self.device = device
             # one-process-per-GPU sharding: statistics are all-reduced over this group (RCCL)
@@ -188,8 +225,12 @@ def camera_isp(name: str, dtype=types.f32):
                 correct_colors: Optional[bool] = None,
                 white_balance: Optional[np.ndarray] = None,
                 color_correction: Optional[np.ndarray] = None,
-                transform: Optional[interpolate.ImageTransform] = None):
-            """camera_isp.py:270-300."""
+                transform: Optional[interpolate.ImageTransform] = None,
+                black_level=None, white_level: Optional[int] = None):
+            """camera_isp.py:270-300; black_level / white_level (the extension): None leaves the current value."""
+            if black_level is not None or white_level is not None:
+                _check_levels(self.black_level if black_level is None else black_level,
+                              self.white_level if white_level is None else white_level)
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -213,6 +254,16 @@ def camera_isp(name: str, dtype=types.f32):
                 self.white_balance = white_balance
             if color_correction is not None:
                 self.color_correction = color_correction
+            if black_level is not None:
+                self.black_level = black_level
+            if white_level is not None:
+                self.white_level = white_level
+
+        def _levels(self, bits):
+            """The Levels argument of the *_levels entry points for a `bits`-bit source, None without levels (ValueError
+            for levels that do not fit it - raised before anything is launched)."""
+            lv = _check_levels(self.black_level, self.white_level, bits)
+            return None if lv is None else _native.levels_arg(*lv)
 
         def resize_image(self, image):
             """camera_isp.py:302-315."""
@@ -232,10 +283,19 @@ def camera_isp(name: str, dtype=types.f32):
                 raise TypeError("image must be a torch.Tensor")
             assert image.ndim == 2, "image must be a 2-D CFA"
             assert image.dtype == src_dtype, f"image must be {src_dtype}, got {image.dtype}"
+            lv = self._levels(16)
+            if lv is not None and mode != 0:
+                raise ValueError("black_level / white_level apply to raw codes (load_16u, load_packed12/16); "
+                                 "load_16f / load_32f take normalised values")
             src = image.to(self.device).contiguous()
             cfa = torch.empty(image.shape, dtype=torch_dtype, device=self.device)
-            _native.check(_native.lib().mi_isp_load_convert(src.data_ptr(), cfa.data_ptr(), cfa.numel(), mode,
-                                                            dtype.code, _native.stream_ptr(self.device)))
+            if lv is None:
+                _native.check(_native.lib().mi_isp_load_convert(src.data_ptr(), cfa.data_ptr(), cfa.numel(), mode,
+                                                                dtype.code, _native.stream_ptr(self.device)))
+            else:
+                _native.check(_native.lib().mi_isp_load_convert_levels(src.data_ptr(), cfa.data_ptr(), image.shape[0],
+                                                                       image.shape[1], mode, dtype.code, lv,
+                                                                       _native.stream_ptr(self.device)))
             return self._process_image(cfa)
 
         def load_16u(self, image):
@@ -260,8 +320,13 @@ def camera_isp(name: str, dtype=types.f32):
             else:
                 w, h = (image_data.shape[1] // 2, image_data.shape[0])             # camera_isp.py:343
             assert w % 2 == 0 and h % 2 == 0, "image must be even size"
+            lv = self._levels(bits)
             src = image_data.to(self.device).contiguous()
             L = _native.lib()
+            # with levels: the same calls through their *_levels twins (the same kernels' level-taking instantiations)
+            load = L.mi_isp_load_packed if lv is None else (lambda *a: L.mi_isp_load_packed_levels(*a[:-1], lv, a[-1]))
+            load_metered = (L.mi_isp_load_packed_metered if lv is None
+                            else (lambda *a: L.mi_isp_load_packed_metered_levels(*a[:-1], lv, a[-1])))
             # camera_isp.py:302-312: output size and scale of resize_image
             if self.resize_width > 0:
                 scale = self.resize_width / w
@@ -275,13 +340,13 @@ def camera_isp(name: str, dtype=types.f32):
             wd, hd = out_size if fused else (w, h)
             rgb = torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device)
             if not fused and scale > 0:                  # a scale the fused kernel does not take: resize separately
-                _native.check(L.mi_isp_load_packed(
+                _native.check(load(
                     src.data_ptr(), rgb.data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
                     _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, 0.0, _native.stream_ptr(self.device)))
                 return self.resize_image(rgb)
             st = self.metering_stride
             if fused or not L.mi_isp_load_packed_metered_is_fused(h, w, bits, int(bool(ids_format)), dtype.code, st):
-                _native.check(L.mi_isp_load_packed(
+                _native.check(load(
                     src.data_ptr(), rgb.data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
                     _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, float(scale) if fused else 0.0,
                     _native.stream_ptr(self.device)))
@@ -289,7 +354,7 @@ def camera_isp(name: str, dtype=types.f32):
             # the image and, on the way, the stride-subsampled copy update_metering will ask for (camera_isp.py:168-170):
             # the load kernel holds those pixels anyway, the strided gather over six 4K images costs 25 us per call
             sub = torch.empty(((hd + st - 1) // st, (wd + st - 1) // st, 3), dtype=torch_dtype, device=self.device)
-            _native.check(L.mi_isp_load_packed_metered(
+            _native.check(load_metered(
                 src.data_ptr(), rgb.data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
                 _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, 0.0,
                 sub.data_ptr(), st, _native.stream_ptr(self.device)))
@@ -324,6 +389,7 @@ def camera_isp(name: str, dtype=types.f32):
             if bits == 12:
                 assert images_data[0].shape[1] % 3 == 0, "packed-12 rows must hold whole pixel pairs (bytes % 3 == 0)"
             assert w % 2 == 0 and h % 2 == 0, "image must be even size"
+            lv = self._levels(bits)
             L = _native.lib()
             if self.resize_width > 0:
                 scale = self.resize_width / w
@@ -343,10 +409,13 @@ def camera_isp(name: str, dtype=types.f32):
             metered = not fused and bool(L.mi_isp_load_packed_metered_is_fused(h, w, bits, int(bool(ids_format)), dtype.code, st))
             subs = [torch.empty(((hd + st - 1) // st, (wd + st - 1) // st, 3), dtype=torch_dtype, device=self.device)
                     for _ in srcs] if metered else None
-            _native.check(L.mi_isp_load_packed_batch(
-                _native.ptr_array(srcs), _native.ptr_array(rgbs), None if subs is None else _native.ptr_array(subs), len(srcs),
-                h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value, _native.ccm_arg(self.color_correct_matrix),
-                dtype.code, hd, wd, float(scale) if fused else 0.0, st, _native.stream_ptr(self.device)))
+            args = (_native.ptr_array(srcs), _native.ptr_array(rgbs), None if subs is None else _native.ptr_array(subs),
+                    len(srcs), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
+                    _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, float(scale) if fused else 0.0, st)
+            if lv is None:
+                _native.check(L.mi_isp_load_packed_batch(*args, _native.stream_ptr(self.device)))
+            else:
+                _native.check(L.mi_isp_load_packed_batch_levels(*args, lv, _native.stream_ptr(self.device)))
             if subs is not None:
                 for rgb, sub in zip(rgbs, subs):
                     _tag_subsample(rgb, sub, st)
@@ -520,6 +589,7 @@ def camera_isp(name: str, dtype=types.f32):
             assert len(frames) > 0, "need at least one frame"
             L = _native.lib()
             f0 = frames[0]
+            lv = self._levels(12)                            # (sensor levels: checked before anything runs)
             fused = (dtype is types.f16 and not ids_format and self.resize_width == 0 and self.scale is None
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8
                      and 1 <= len(frames) <= 64
@@ -535,7 +605,8 @@ def camera_isp(name: str, dtype=types.f32):
             if fused:
                 h, w = f0.shape[0], f0.shape[1] * 2 // 3
                 with torch.cuda.device(self.device):
-                    fused = bool(L.mi_isp_camera_group_fits(h, w, self._demosaic_pattern.value, dtype.code, 8))
+                    fused = bool(L.mi_isp_camera_group_fits(h, w, self._demosaic_pattern.value, dtype.code, 8) if lv is None
+                                 else L.mi_isp_camera_group_fits_levels(h, w, self._demosaic_pattern.value, dtype.code, 8, lv))
             if not fused:
                 images = self.load_packed12_batch(frames, ids_format)
                 outputs = self.tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt)
@@ -561,22 +632,32 @@ def camera_isp(name: str, dtype=types.f32):
             p_srcs, p_imgs, p_outs = _native.ptr_array(srcs), _native.ptr_array(images) if keep_images else None, _native.ptr_array(outputs)
             ccm = _native.ccm_arg(self.color_correct_matrix)
             if self.process_group is None:
-                _native.check(L.mi_isp_camera_group_reinhard(
-                    p_srcs, p_imgs, p_outs, n, h, w, self._demosaic_pattern.value, ccm, prev.data_ptr(), metrics.data_ptr(), float(t),
-                    float(gamma), float(intensity), float(light_adapt), float(color_adapt), scratch.data_ptr(), ws.data_ptr(),
-                    stream))
+                args = (p_srcs, p_imgs, p_outs, n, h, w, self._demosaic_pattern.value, ccm, prev.data_ptr(), metrics.data_ptr(),
+                        float(t), float(gamma), float(intensity), float(light_adapt), float(color_adapt), scratch.data_ptr(),
+                        ws.data_ptr())
+                if lv is None:
+                    _native.check(L.mi_isp_camera_group_reinhard(*args, stream))
+                else:
+                    _native.check(L.mi_isp_camera_group_reinhard_levels(*args, lv, stream))
                 self.metrics = metrics
                 return (outputs, images) if keep_images else outputs
             # a sharded group (one process per GPU): the same three steps with the metering's two all-gathers in between
-            _native.check(L.mi_isp_camera_group_subsample(p_srcs, n, h, w, self._demosaic_pattern.value, ccm,
-                                                          scratch.data_ptr(), stream))
+            if lv is None:
+                _native.check(L.mi_isp_camera_group_subsample(p_srcs, n, h, w, self._demosaic_pattern.value, ccm,
+                                                              scratch.data_ptr(), stream))
+            else:
+                _native.check(L.mi_isp_camera_group_subsample_levels(p_srcs, n, h, w, self._demosaic_pattern.value, ccm,
+                                                                     scratch.data_ptr(), lv, stream))
             per = int(L.mi_isp_camera_group_scratch_bytes(1, h, w))
             hs, ws_ = (h + 7) // 8, (w + 7) // 8
             subs = [scratch[i * per:i * per + hs * ws_ * 6].view(torch_dtype).view(hs, ws_, 3) for i in range(n)]
             self.metrics = self._metering_images(subs, t, prev, stride=1)
-            _native.check(L.mi_isp_camera_group_tonemap(
-                p_srcs, p_imgs, p_outs, n, h, w, self._demosaic_pattern.value, ccm, self.metrics.data_ptr(), float(gamma),
-                float(intensity), float(light_adapt), float(color_adapt), ws.data_ptr(), stream))
+            args = (p_srcs, p_imgs, p_outs, n, h, w, self._demosaic_pattern.value, ccm, self.metrics.data_ptr(), float(gamma),
+                    float(intensity), float(light_adapt), float(color_adapt), ws.data_ptr())
+            if lv is None:
+                _native.check(L.mi_isp_camera_group_tonemap(*args, stream))
+            else:
+                _native.check(L.mi_isp_camera_group_tonemap_levels(*args, lv, stream))
             return (outputs, images) if keep_images else outputs
 
         def tonemap_linear(self, images: List[torch.Tensor], gamma: float = 1.0):

@@ -22,7 +22,7 @@ void mi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int mi_isp_version(void) { return 1000; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
+extern "C" int mi_isp_version(void) { return 1100; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
 extern "C" const char* mi_isp_last_error(void) { return g_err; }
 
 extern "C" int mi_isp_bayer_weights(int32_t out[4 * 13 * 3]) {
@@ -99,6 +99,23 @@ static int packed_params(tile::Params& p, const uint8_t* packed, int H, int W, i
   return 0;
 }
 
+// sensor levels (mi_isp_levels) of a packed source: NULL leaves Params::levels 0 (the kernels without levels)
+static int apply_levels(tile::Params& p, const mi_isp_levels* lv, int bits, const char* who) {
+  if (!lv) { p.levels = 0; return 0; }
+  const int top = bits == 16 ? 65535 : 4095;
+  MI_REQUIRE(lv->white > 0 && lv->white <= top, "%s: white level %d outside (0, %d]", who, (int)lv->white, top);
+  bool uniform = true;
+  for (int s = 0; s < 4; ++s) {
+    MI_REQUIRE(lv->black[s] >= 0 && lv->black[s] < lv->white, "%s: black level %d of site %d outside [0, white = %d)", who,
+               (int)lv->black[s], s, (int)lv->white);
+    p.lv_black[s] = lv->black[s];
+    p.lv_k[s] = (float)(1.0 / (double)(lv->white - lv->black[s]));       // S = 1 for the f16 / f32 work dtypes
+    uniform = uniform && lv->black[s] == lv->black[0];
+  }
+  p.levels = uniform ? 1 : 2;
+  return 0;
+}
+
 #ifdef MI_STREAM_STAMPS
 // measurement build only: a home for the in-kernel stamps of the kernels that take no workspace (16 words per wave)
 static float* stamp_buffer() {
@@ -129,11 +146,12 @@ static bool use_stream(const tile::Params& p, int work_dtype, const void* out, i
 
 static int load_packed_impl(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
                             int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
-                            void* sub, int sub_stride, void* stream) {
+                            void* sub, int sub_stride, const mi_isp_levels* lv, void* stream) {
   MI_REQUIRE(rgb, "load_packed: null output");
   tile::Params p = {};
   if (int rc = fill_common(p, H, W, pattern, ccm9, "load_packed")) return rc;
   if (int rc = packed_params(p, packed, H, W, bits, ids_format, work_dtype, "load_packed")) return rc;
+  if (int rc = apply_levels(p, lv, bits, "load_packed")) return rc;
   p.dst = rgb; p.out_dtype = work_dtype; p.out_scale = 1.f;
   if (scale > 0.f) {
     // unpack -> demosaic -> bilinear fused (isp_resize_tile.h); the caller checks the scale first
@@ -176,15 +194,23 @@ static int load_packed_impl(const uint8_t* packed, void* rgb, int H, int W, int 
 extern "C" int mi_isp_load_packed(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
                                   int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
                                   void* stream) {
-  return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, nullptr, 0, stream);
+  return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, nullptr, 0,
+                          nullptr, stream);
+}
+
+extern "C" int mi_isp_load_packed_levels(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
+                                         int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
+                                         const mi_isp_levels* levels, void* stream) {
+  return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, nullptr, 0,
+                          levels, stream);
 }
 
 // The cameras of a group in ONE launch per 8 (grid.y = camera): dispatch, decode table, first loads and drain are paid per
 // launch instead of per camera (the load kernels take 23 - 30 us each, ~4 us of that is launch overhead: config 3, six
 // cameras, 43.0 -> ~39.5 us per frame).  Same arithmetic, same bits as n calls of mi_isp_load_packed[_metered].
-extern "C" int mi_isp_load_packed_batch(const uint8_t* const* packed, void* const* rgb, void* const* subs, int n, int H, int W,
-                                        int bits, int ids_format, int pattern, const float* ccm9, int work_dtype, int Hd,
-                                        int Wd, float scale, int sub_stride, void* stream) {
+static int load_packed_batch_impl(const uint8_t* const* packed, void* const* rgb, void* const* subs, int n, int H, int W,
+                                  int bits, int ids_format, int pattern, const float* ccm9, int work_dtype, int Hd,
+                                  int Wd, float scale, int sub_stride, const mi_isp_levels* lv, void* stream) {
   MI_REQUIRE(packed && rgb, "load_packed_batch: null pointer");
   MI_REQUIRE(n >= 0, "load_packed_batch: negative frame count");
   for (int i = 0; i < n; ++i) MI_REQUIRE(packed[i] && rgb[i] && (!subs || subs[i]), "load_packed_batch: frame %d has a null buffer", i);
@@ -197,6 +223,7 @@ extern "C" int mi_isp_load_packed_batch(const uint8_t* const* packed, void* cons
     tile::Params p = {};
     if (int rc = fill_common(p, H, W, pattern, ccm9, "load_packed_batch")) return rc;
     if (int rc = packed_params(p, packed[i], H, W, bits, ids_format, work_dtype, "load_packed_batch")) return rc;
+    if (int rc = apply_levels(p, lv, bits, "load_packed_batch")) return rc;
     p.dst = rgb[i]; p.out_dtype = work_dtype; p.out_scale = 1.f;
     if (resize) {
       same = Hd > 0 && Wd > 0 && H >= 2 && W >= 2 && use_stream(p, work_dtype, nullptr, work_dtype) &&
@@ -210,7 +237,7 @@ extern "C" int mi_isp_load_packed_batch(const uint8_t* const* packed, void* cons
   if (!same) {                                               // some frame needs another kernel: one by one
     for (int i = 0; i < n; ++i)
       if (int rc = load_packed_impl(packed[i], rgb[i], H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale,
-                                    subs ? subs[i] : nullptr, sub_stride, stream))
+                                    subs ? subs[i] : nullptr, sub_stride, lv, stream))
         return rc;
     return 0;
   }
@@ -241,6 +268,21 @@ extern "C" int mi_isp_load_packed_batch(const uint8_t* const* packed, void* cons
   return 0;
 }
 
+extern "C" int mi_isp_load_packed_batch(const uint8_t* const* packed, void* const* rgb, void* const* subs, int n, int H, int W,
+                                        int bits, int ids_format, int pattern, const float* ccm9, int work_dtype, int Hd,
+                                        int Wd, float scale, int sub_stride, void* stream) {
+  return load_packed_batch_impl(packed, rgb, subs, n, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale,
+                                sub_stride, nullptr, stream);
+}
+
+extern "C" int mi_isp_load_packed_batch_levels(const uint8_t* const* packed, void* const* rgb, void* const* subs, int n, int H,
+                                               int W, int bits, int ids_format, int pattern, const float* ccm9,
+                                               int work_dtype, int Hd, int Wd, float scale, int sub_stride,
+                                               const mi_isp_levels* levels, void* stream) {
+  return load_packed_batch_impl(packed, rgb, subs, n, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale,
+                                sub_stride, levels, stream);
+}
+
 extern "C" int mi_isp_load_packed_metered_is_fused(int H, int W, int bits, int ids_format, int work_dtype, int sub_stride) {
   if (bits != 12 || ids_format || sub_stride != 8 || H <= 0 || W <= 0) return 0;
   tile::Params p = {};
@@ -252,7 +294,16 @@ extern "C" int mi_isp_load_packed_metered(const uint8_t* packed, void* rgb, int 
                                           int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
                                           void* sub, int sub_stride, void* stream) {
   MI_REQUIRE(sub && sub_stride >= 1, "load_packed_metered: need a subsample buffer and a positive stride");
-  return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, sub, sub_stride, stream);
+  return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, sub, sub_stride,
+                          nullptr, stream);
+}
+
+extern "C" int mi_isp_load_packed_metered_levels(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
+                                                 int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
+                                                 void* sub, int sub_stride, const mi_isp_levels* levels, void* stream) {
+  MI_REQUIRE(sub && sub_stride >= 1, "load_packed_metered: need a subsample buffer and a positive stride");
+  return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, sub, sub_stride,
+                          levels, stream);
 }
 
 extern "C" int mi_isp_load_packed_scale_supported(float scale) { return rtile::scales_fit(scale, scale) ? 1 : 0; }
@@ -767,10 +818,11 @@ extern "C" int mi_isp_camera_frame_batch(const uint8_t* const* packed, void* con
 // mega::camera_kernel walks through the cameras - demosaic, Reinhard, max_out at a grid barrier, u8 out - with the image
 // resident on the chip.  images == NULL: p is not stored (the bench drops it); else images[i] receives what the reference
 // leaves in the loaded image (camera_isp.py:211).
-static int g_cam_per_cu[4] = {-1, -1, -1, -1};
+static int g_cam_per_cu[3][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}};   // [levels][pattern]
 static unsigned g_cam_poll_limit = 0;
 
-static bool camera_group_fits(int H, int W, int pattern, strm::SArgs& a) {
+// lv: the levels instantiation (tile::Params::levels) whose occupancy counts
+static bool camera_group_fits(int H, int W, int pattern, strm::SArgs& a, int lv = 0) {
   if (pattern < 0 || pattern > 3 || H <= 0 || W <= 0) return false;
   tile::Params p = {};
   p.H = H; p.W = W; p.src_kind = tile::SRC_PACKED12; p.src_fast = ((int64_t)W * 3 / 2) % 4 == 0; p.in_scale = 1.f; p.vec_store = 1;
@@ -778,18 +830,32 @@ static bool camera_group_fits(int H, int W, int pattern, strm::SArgs& a) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
   std::lock_guard<std::mutex> lock(mega_mu());
-  if (g_cam_per_cu[pattern] < 0) g_cam_per_cu[pattern] = mega::cam_blocks_per_cu(pattern);
+  if (lv < 0 || lv > 2) return false;
+  if (g_cam_per_cu[lv][pattern] < 0) g_cam_per_cu[lv][pattern] = mega::cam_blocks_per_cu(pattern, lv);
   if (g_mega.n_cus[dev] == 0) {
     int n = 0;
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
     g_mega.n_cus[dev] = n;
   }
-  return g_cam_per_cu[pattern] >= 2 && mega::geometry(H, W, g_mega.n_cus[dev], a);
+  return g_cam_per_cu[lv][pattern] >= 2 && mega::geometry(H, W, g_mega.n_cus[dev], a);
+}
+
+// the instantiation a call with these levels takes (0 without), or -1 for levels apply_levels refuses
+static int levels_mode(const mi_isp_levels* lv) {
+  tile::Params p = {};
+  return apply_levels(p, lv, 12, "camera_group") ? -1 : p.levels;
 }
 
 extern "C" int mi_isp_camera_group_fits(int H, int W, int pattern, int work_dtype, int metering_stride) {
   strm::SArgs a = {};
   return work_dtype == MI_F16 && metering_stride == 8 && camera_group_fits(H, W, pattern, a) ? 1 : 0;
+}
+
+extern "C" int mi_isp_camera_group_fits_levels(int H, int W, int pattern, int work_dtype, int metering_stride,
+                                               const mi_isp_levels* levels) {
+  strm::SArgs a = {};
+  const int lv = levels_mode(levels);
+  return lv >= 0 && work_dtype == MI_F16 && metering_stride == 8 && camera_group_fits(H, W, pattern, a, lv) ? 1 : 0;
 }
 
 extern "C" size_t mi_isp_camera_group_scratch_bytes(int n, int H, int W) {
@@ -818,7 +884,7 @@ extern "C" int mi_isp_camera_group_faults(int clear) {
 
 // the frames' common parameters, checked per camera
 static int camera_group_params(tile::Params& p, const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n,
-                               int H, int W, int pattern, const float* ccm9, const char* who) {
+                               int H, int W, int pattern, const float* ccm9, const mi_isp_levels* lv, const char* who) {
   MI_REQUIRE(packed, "%s: null pointer", who);
   MI_REQUIRE(n >= 1 && n <= mega::MAX_BATCH, "%s: 1 .. %d cameras per call", who, mega::MAX_BATCH);
   for (int i = 0; i < n; ++i) {
@@ -828,6 +894,7 @@ static int camera_group_params(tile::Params& p, const uint8_t* const* packed, vo
     tile::Params pi = {};
     if (int rc = fill_common(pi, H, W, pattern, ccm9, who)) return rc;
     if (int rc = packed_params(pi, packed[i], H, W, 12, 0, MI_F16, who)) return rc;
+    if (int rc = apply_levels(pi, lv, 12, who)) return rc;
     MI_REQUIRE(strm::supported(pi, MI_F16), "%s: camera %d: the packed frame does not take the streaming kernels "
                "(standard 12-bit layout, W %% 8 == 0, even H, 4-byte aligned rows)", who, i);
     if (i == 0) p = pi;
@@ -837,12 +904,12 @@ static int camera_group_params(tile::Params& p, const uint8_t* const* packed, vo
 }
 
 // step 1: image[::8, ::8] of every camera's (never materialised) image, (ceil(H / 8), ceil(W / 8), 3) f16 each, in scratch
-extern "C" int mi_isp_camera_group_subsample(const uint8_t* const* packed, int n, int H, int W, int pattern, const float* ccm9,
-                                             void* scratch, void* stream) {
+static int camera_group_subsample_impl(const uint8_t* const* packed, int n, int H, int W, int pattern, const float* ccm9,
+                                       void* scratch, const mi_isp_levels* lv, void* stream) {
   const char* who = "camera_group_subsample";
   MI_REQUIRE(scratch, "%s: null pointer", who);
   tile::Params p = {};
-  if (int rc = camera_group_params(p, packed, nullptr, nullptr, n, H, W, pattern, ccm9, who)) return rc;
+  if (int rc = camera_group_params(p, packed, nullptr, nullptr, n, H, W, pattern, ccm9, lv, who)) return rc;
   const size_t sub_bytes = mi_isp_camera_group_scratch_bytes(1, H, W);
   for (int i0 = 0; i0 < n; i0 += strm::LOAD_BATCH) {
     strm::SubArgs sa = {};
@@ -855,18 +922,30 @@ extern "C" int mi_isp_camera_group_subsample(const uint8_t* const* packed, int n
   return 0;
 }
 
+extern "C" int mi_isp_camera_group_subsample(const uint8_t* const* packed, int n, int H, int W, int pattern, const float* ccm9,
+                                             void* scratch, void* stream) {
+  return camera_group_subsample_impl(packed, n, H, W, pattern, ccm9, scratch, nullptr, stream);
+}
+
+extern "C" int mi_isp_camera_group_subsample_levels(const uint8_t* const* packed, int n, int H, int W, int pattern,
+                                                    const float* ccm9, void* scratch, const mi_isp_levels* levels,
+                                                    void* stream) {
+  return camera_group_subsample_impl(packed, n, H, W, pattern, ccm9, scratch, levels, stream);
+}
+
 // step 3: the cameras through one resident launch, with the Reinhard scalars of state9 (read on the device)
-extern "C" int mi_isp_camera_group_tonemap(const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n, int H,
-                                           int W, int pattern, const float* ccm9, const float* state9, float gamma,
-                                           float intensity, float light_adapt, float color_adapt, void* ws, void* stream) {
+static int camera_group_tonemap_impl(const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n, int H,
+                                     int W, int pattern, const float* ccm9, const float* state9, float gamma,
+                                     float intensity, float light_adapt, float color_adapt, void* ws,
+                                     const mi_isp_levels* lv, void* stream) {
   const char* who = "camera_group_tonemap";
   MI_REQUIRE(outs && state9 && ws, "%s: null pointer", who);
   MI_REQUIRE(gamma > 0.f, "%s: gamma must be positive", who);
   hipStream_t s = (hipStream_t)stream;
   tile::Params p = {};
-  if (int rc = camera_group_params(p, packed, images, outs, n, H, W, pattern, ccm9, who)) return rc;
+  if (int rc = camera_group_params(p, packed, images, outs, n, H, W, pattern, ccm9, lv, who)) return rc;
   strm::SArgs ma = {};
-  MI_REQUIRE(camera_group_fits(H, W, pattern, ma),
+  MI_REQUIRE(camera_group_fits(H, W, pattern, ma, p.levels),
              "%s: the frame does not fit the resident grid (mi_isp_camera_group_fits); use mi_isp_camera_frame_batch", who);
   p.out_dtype = MI_U8; p.out_scale = 255.f; p.gamma_inv = 1.0f / gamma; p.la = light_adapt; p.ca = color_adapt;
   p.part_stride = mi_partial_cap(H, W);
@@ -905,20 +984,37 @@ extern "C" int mi_isp_camera_group_tonemap(const uint8_t* const* packed, void* c
   return 0;
 }
 
-extern "C" int mi_isp_camera_group_reinhard(const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n,
-                                            int H, int W, int pattern, const float* ccm9, const float* prev9, float* state9,
-                                            float alpha, float gamma, float intensity, float light_adapt, float color_adapt,
-                                            void* scratch, void* ws, void* stream) {
+extern "C" int mi_isp_camera_group_tonemap(const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n, int H,
+                                           int W, int pattern, const float* ccm9, const float* state9, float gamma,
+                                           float intensity, float light_adapt, float color_adapt, void* ws, void* stream) {
+  return camera_group_tonemap_impl(packed, images, outs, n, H, W, pattern, ccm9, state9, gamma, intensity, light_adapt,
+                                   color_adapt, ws, nullptr, stream);
+}
+
+extern "C" int mi_isp_camera_group_tonemap_levels(const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n,
+                                                  int H, int W, int pattern, const float* ccm9, const float* state9,
+                                                  float gamma, float intensity, float light_adapt, float color_adapt,
+                                                  void* ws, const mi_isp_levels* levels, void* stream) {
+  return camera_group_tonemap_impl(packed, images, outs, n, H, W, pattern, ccm9, state9, gamma, intensity, light_adapt,
+                                   color_adapt, ws, levels, stream);
+}
+
+static int camera_group_reinhard_impl(const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n,
+                                      int H, int W, int pattern, const float* ccm9, const float* prev9, float* state9,
+                                      float alpha, float gamma, float intensity, float light_adapt, float color_adapt,
+                                      void* scratch, void* ws, const mi_isp_levels* lv, void* stream) {
   const char* who = "camera_group_reinhard";
   MI_REQUIRE(packed && outs && prev9 && state9 && scratch && ws, "%s: null pointer", who);
   MI_REQUIRE(n >= 1 && n <= mega::MAX_BATCH, "%s: 1 .. %d cameras per call", who, mega::MAX_BATCH);
   {                                                          // refuse before anything is launched
+    const int mode = levels_mode(lv);
+    if (mode < 0) return 1;                                  // (apply_levels set the message)
     strm::SArgs ma = {};
-    MI_REQUIRE(camera_group_fits(H, W, pattern, ma),
+    MI_REQUIRE(camera_group_fits(H, W, pattern, ma, mode),
                "%s: the frame does not fit the resident grid (mi_isp_camera_group_fits); use mi_isp_camera_frame_batch", who);
   }
   // 1. the subsample of every camera, straight from its packed frame
-  if (int rc = mi_isp_camera_group_subsample(packed, n, H, W, pattern, ccm9, scratch, stream)) return rc;
+  if (int rc = camera_group_subsample_impl(packed, n, H, W, pattern, ccm9, scratch, lv, stream)) return rc;
   // 2. the rolling metering over the group (its own workspace: the last of the n + 1)
   const int Hs = (H + 7) / 8, Ws = (W + 7) / 8;
   const size_t sub_bytes = mi_isp_camera_group_scratch_bytes(1, H, W);
@@ -928,8 +1024,25 @@ extern "C" int mi_isp_camera_group_reinhard(const uint8_t* const* packed, void* 
   float* ws_meter = static_cast<float*>(ws) + (size_t)n * ws_floats;
   if (int rc = mi_isp_metering_to(subs, n, Hs, Ws, 1, MI_F16, prev9, state9, alpha, ws_meter, stream)) return rc;
   // 3. the cameras through one resident launch
-  return mi_isp_camera_group_tonemap(packed, images, outs, n, H, W, pattern, ccm9, state9, gamma, intensity, light_adapt,
-                                     color_adapt, ws, stream);
+  return camera_group_tonemap_impl(packed, images, outs, n, H, W, pattern, ccm9, state9, gamma, intensity, light_adapt,
+                                   color_adapt, ws, lv, stream);
+}
+
+extern "C" int mi_isp_camera_group_reinhard(const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n,
+                                            int H, int W, int pattern, const float* ccm9, const float* prev9, float* state9,
+                                            float alpha, float gamma, float intensity, float light_adapt, float color_adapt,
+                                            void* scratch, void* ws, void* stream) {
+  return camera_group_reinhard_impl(packed, images, outs, n, H, W, pattern, ccm9, prev9, state9, alpha, gamma, intensity,
+                                    light_adapt, color_adapt, scratch, ws, nullptr, stream);
+}
+
+extern "C" int mi_isp_camera_group_reinhard_levels(const uint8_t* const* packed, void* const* images, uint8_t* const* outs,
+                                                   int n, int H, int W, int pattern, const float* ccm9, const float* prev9,
+                                                   float* state9, float alpha, float gamma, float intensity,
+                                                   float light_adapt, float color_adapt, void* scratch, void* ws,
+                                                   const mi_isp_levels* levels, void* stream) {
+  return camera_group_reinhard_impl(packed, images, outs, n, H, W, pattern, ccm9, prev9, state9, alpha, gamma, intensity,
+                                    light_adapt, color_adapt, scratch, ws, levels, stream);
 }
 
 // ---- a batch as a HIP graph: capture once, replay per step ---------------------------------------------------------

@@ -173,6 +173,24 @@ __global__ __launch_bounds__(EW_THREADS) void load_convert_kernel(const void* __
   }
 }
 
+// load_16u with sensor levels (mi_isp_load_convert_levels): cast(f32(max(v - black[s], 0)) / f32(white - black[s])), the
+// loader's own division; site s = (r & 1) * 2 + (c & 1) of the H x W frame.  black / den: the four sites' levels.
+struct ConvLevels { int black[4]; float den[4]; };
+template <class T>
+__global__ __launch_bounds__(EW_THREADS) void load_u16_levels_kernel(const uint16_t* __restrict__ src, T* __restrict__ dst,
+                                                                     int H, int W, const ConvLevels lv) {
+  const int64_t n = (int64_t)H * W;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int r = (int)(i / W), c = (int)(i - (int64_t)r * W);
+    const bool ro = (r & 1) != 0, co = (c & 1) != 0;  // (selects: a run-time index would put lv in scratch)
+    const int b = ro ? (co ? lv.black[3] : lv.black[2]) : (co ? lv.black[1] : lv.black[0]);
+    const float den = ro ? (co ? lv.den[3] : lv.den[2]) : (co ? lv.den[1] : lv.den[0]);
+    const int d = (int)src[i] - b;
+    dst[i] = cast_out<T>((float)(d > 0 ? d : 0) / den);
+  }
+}
+
 // K5 rgb_to_bayer (bayer.py:101-112): channel index per site from pixel_orders (bayer.py:85-90)
 template <class T>
 __global__ __launch_bounds__(EW_THREADS) void mosaic_kernel(const T* __restrict__ rgb,
@@ -1724,6 +1742,35 @@ extern "C" int mi_isp_load_convert(const void* src, void* dst, int64_t n, int mo
     using T = decltype(tag);
     hipLaunchKernelGGL((load_convert_kernel<T>), dim3(grid_for(n)), dim3(EW_THREADS), 0, s, src,
                        static_cast<T*>(dst), n, mode);
+    MI_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+extern "C" int mi_isp_load_convert_levels(const void* src, void* dst, int H, int W, int mode, int out_dtype,
+                                          const mi_isp_levels* levels, void* stream) {
+  MI_REQUIRE(H >= 0 && W >= 0, "load_convert_levels: bad shape %dx%d", H, W);
+  if (!levels) return mi_isp_load_convert(src, dst, (int64_t)H * W, mode, out_dtype, stream);
+  MI_REQUIRE(src && dst, "load_convert_levels: null pointer");
+  MI_REQUIRE(mode == MI_LOAD_16U, "load_convert_levels: levels apply to u16 codes only (mode %d)", mode);
+  MI_REQUIRE(out_dtype == MI_F16 || out_dtype == MI_F32, "load_convert_levels: output must be f16/f32");
+  MI_REQUIRE(levels->white > 0 && levels->white <= 65535, "load_convert_levels: white level %d outside (0, 65535]",
+             (int)levels->white);
+  ConvLevels lv;
+  for (int s = 0; s < 4; ++s) {
+    MI_REQUIRE(levels->black[s] >= 0 && levels->black[s] < levels->white,
+               "load_convert_levels: black level %d of site %d outside [0, white = %d)", (int)levels->black[s], s,
+               (int)levels->white);
+    lv.black[s] = levels->black[s];
+    lv.den[s] = (float)(levels->white - levels->black[s]);                 // exact: < 2^24
+  }
+  const int64_t n = (int64_t)H * W;
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  return dispatch_dtype(out_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((load_u16_levels_kernel<T>), dim3(grid_for(n)), dim3(EW_THREADS), 0, s,
+                       static_cast<const uint16_t*>(src), static_cast<T*>(dst), H, W, lv);
     MI_LAUNCH_CHECK();
     return 0;
   });

@@ -73,7 +73,8 @@ MI_DEV void pack12_u8_rtz(const float* v, uint32_t (&d)[3]) {
         "v"(v[11]));
 }
 
-template <int PR, int PC>
+// LV: sensor levels (tile::Params::levels; strm::decode_row): 1 folded into the decode table, 2 per site in registers
+template <int PR, int PC, int LV = 0>
 __global__ __launch_bounds__(THREADS, 2) void camera_kernel(const CBatch cb) {
   typedef half_t E;
   const MArgs& m = cb.m;
@@ -141,7 +142,11 @@ __global__ __launch_bounds__(THREADS, 2) void camera_kernel(const CBatch cb) {
   };
   first_loads(geo(threadIdx.x, blockIdx.x), cb.io[0].src);
 
-  for (int e = threadIdx.x; e < 4096; e += THREADS) lut[e] = tile::decode_scaled<E>((uint32_t)e, p.k_decode);
+  if constexpr (LV == 0) {
+    for (int e = threadIdx.x; e < 4096; e += THREADS) lut[e] = tile::decode_scaled<E>((uint32_t)e, p.k_decode);
+  } else {
+    fill_lut<E, LV>(lut, p);
+  }
   __syncthreads();                                    // table, scalars, tickets, flags, `arrived`: the only workgroup barrier
 
   const int wave_s = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -174,14 +179,25 @@ __global__ __launch_bounds__(THREADS, 2) void camera_kernel(const CBatch cb) {
   for (int i = 0; i < 8; ++i) wq[i] = vgpr(wq_value(i));
   WinRow win[6];
   uint32_t xr[NR][12];                                // resident rows NL..ROWS-1 (packed f16 pairs)
+  // LV == 2: the levels of even / odd rows (r_begin is a multiple of ROWS, which is even: window slot q has q's parity)
+  const tile::RowLevels lv_even = LV == 2 ? tile::row_levels(p, 0) : tile::RowLevels{},
+                        lv_odd = LV == 2 ? tile::row_levels(p, 1) : tile::RowLevels{};
 #pragma unroll
-  for (int q = 0; q < 4; ++q) decode_row(pro[q], lut, lane, win[q]);
+  for (int q = 0; q < 4; ++q) {
+    if constexpr (LV == 0) decode_row(pro[q], lut, lane, win[q]);
+    else decode_row<E, LV>(pro[q], lut, lane, win[q], (q & 1) ? lv_odd : lv_even);
+  }
 
   static_for<0, ROWS / 2>([&](auto ibc) {
     constexpr int IB = decltype(ibc)::value, PH = IB % 3;
     const int r = r_begin + 2 * IB;
-    decode_row(raw[IB % 2][0], lut, lane, win[(2 * PH + 4) % 6]);
-    decode_row(raw[IB % 2][1], lut, lane, win[(2 * PH + 5) % 6]);
+    if constexpr (LV == 0) {
+      decode_row(raw[IB % 2][0], lut, lane, win[(2 * PH + 4) % 6]);
+      decode_row(raw[IB % 2][1], lut, lane, win[(2 * PH + 5) % 6]);
+    } else {
+      decode_row<E, LV>(raw[IB % 2][0], lut, lane, win[(2 * PH + 4) % 6], lv_even);
+      decode_row<E, LV>(raw[IB % 2][1], lut, lane, win[(2 * PH + 5) % 6], lv_odd);
+    }
     if constexpr (IB + 2 < ROWS / 2) {
       load_row(G, rsrc, r + 6, raw[IB % 2][0]);
       load_row(G, rsrc, r + 7, raw[IB % 2][1]);
@@ -368,16 +384,17 @@ static inline int launch_cam(const CBatch& cb, int pattern, hipStream_t stream) 
     default: return launch_cam_bggr(cb, stream);
   }
 }
-int cam_blocks_per_cu_rggb();
-int cam_blocks_per_cu_grbg();
-int cam_blocks_per_cu_gbrg();
-int cam_blocks_per_cu_bggr();
-static inline int cam_blocks_per_cu(int pattern) {
+// (lv: the instantiation of Params::levels)
+int cam_blocks_per_cu_rggb(int lv);
+int cam_blocks_per_cu_grbg(int lv);
+int cam_blocks_per_cu_gbrg(int lv);
+int cam_blocks_per_cu_bggr(int lv);
+static inline int cam_blocks_per_cu(int pattern, int lv) {
   switch (pattern) {
-    case MI_RGGB: return cam_blocks_per_cu_rggb();
-    case MI_GRBG: return cam_blocks_per_cu_grbg();
-    case MI_GBRG: return cam_blocks_per_cu_gbrg();
-    default: return cam_blocks_per_cu_bggr();
+    case MI_RGGB: return cam_blocks_per_cu_rggb(lv);
+    case MI_GRBG: return cam_blocks_per_cu_grbg(lv);
+    case MI_GBRG: return cam_blocks_per_cu_gbrg(lv);
+    default: return cam_blocks_per_cu_bggr(lv);
   }
 }
 

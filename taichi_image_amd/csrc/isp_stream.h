@@ -116,22 +116,46 @@ struct WinRow { float v[12]; };
 // rounded to the work dtype, widened back - has 4096 possible results: they are tabulated once per block in LDS
 // (16 KB, filled with exactly that arithmetic) and a pixel costs one ds_read_b32 instead of four half-rate
 // conversions; the table index is the unpacked 12-bit value itself.
-MI_DEV void decode_row(const uint32_t (&d)[4], const float (&lut)[4096], int lane, WinRow& row) {
+//
+// Sensor levels (tile::Params::levels, template parameter LV): 1 - one black level for every CFA site, folded into the
+// table (fill_lut), so a pixel costs what it costs without levels; 2 - one per site: the table is not used, every code
+// is decoded in registers (tile::decode_level: sub, max, cvt, mul, cvt) with the levels of its row parity `lv`
+// (every unit starts at an even column, so the parity of a column is that of its index).
+template <class E = float, int LV = 0>
+MI_DEV void decode_row(const uint32_t (&d)[4], const float (&lut)[4096], int lane, WinRow& row,
+                       const tile::RowLevels& lv = {}) {
   uint32_t v[8];
   tile::unpack12x8(d[0], d[1], d[2], false, v);
   // lane 0: the last pixel pair of the unit to the left = the upper 3 bytes of the dword before this unit;
   // lane 63: the first pair of the unit to the right = the lower 3 bytes of the dword after it
   const uint32_t w = lane == 0 ? d[3] >> 8 : d[3] & 0xFFFFFFu;
   float own[8];
+  float x0, x1;
+  if constexpr (LV == 2) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) own[i] = lut[v[i]];
-  const float x0 = lut[w & 0xFFFu], x1 = lut[w >> 12];
+    for (int i = 0; i < 8; ++i) own[i] = tile::decode_level<E>(v[i], (i & 1) ? lv.b1 : lv.b0, (i & 1) ? lv.k1 : lv.k0);
+    x0 = tile::decode_level<E>(w & 0xFFFu, lv.b0, lv.k0);
+    x1 = tile::decode_level<E>(w >> 12, lv.b1, lv.k1);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) own[i] = lut[v[i]];
+    x0 = lut[w & 0xFFFu]; x1 = lut[w >> 12];
+  }
   row.v[0] = from_left(own[6], x0);
   row.v[1] = from_left(own[7], x1);
 #pragma unroll
   for (int j = 0; j < 8; ++j) row.v[2 + j] = own[j];
   row.v[10] = from_right(own[0], x0);
   row.v[11] = from_right(own[1], x1);
+}
+
+// the decode table of a block (decode_row); LV == 1 folds the uniform black level in, LV == 2 needs none
+template <class E, int LV = 0> MI_DEV void fill_lut(float (&lut)[4096], const Params& p) {
+  if constexpr (LV == 1) {
+    for (int e = threadIdx.x; e < 4096; e += THREADS) lut[e] = tile::decode_level<E>((uint32_t)e, p.lv_black[0], p.lv_k[0]);
+  } else if constexpr (LV == 0) {
+    for (int e = threadIdx.x; e < 4096; e += THREADS) lut[e] = tile::decode_scaled<E>((uint32_t)e, p.k_decode);
+  }
 }
 
 // filter_at (bayer.py:138-155) for the 8 pixels of strip row I of a 6-row window: per pixel and channel a sequential
@@ -529,8 +553,9 @@ MI_DEV void border_fix_rows(float (&v)[24], int rmask, bool is_left, bool is_rig
 #define MI_STAMP_NOW() 0u
 #endif
 
-template <class E, int PR, int PC, int EPI>
+template <class E, int PR, int PC, int EPI, int LV = 0>
 __global__ __launch_bounds__(THREADS, 2) void stream_kernel(const SArgs a) {
+  static_assert(LV == 0 || EPI == S_STORE, "sensor levels: the load's store pass only");
   constexpr bool EXACT = sizeof(E) == 2;
   constexpr bool STORES = EPI == S_STORE || EPI == S_RH_STORE || EPI == S_STORE_BOUNDS;
   constexpr bool BOUNDS = EPI == S_BOUNDS || EPI == S_STORE_BOUNDS;
@@ -605,6 +630,9 @@ __global__ __launch_bounds__(THREADS, 2) void stream_kernel(const SArgs a) {
   float wq[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) wq[i] = vgpr(wq_value(i));
+  // LV == 2: the levels of even / odd rows (unused otherwise)
+  const tile::RowLevels lv_even = LV == 2 ? tile::row_levels(p, 0) : tile::RowLevels{},
+                        lv_odd = LV == 2 ? tile::row_levels(p, 1) : tile::RowLevels{};
   WinRow win[6];                                     // ring: image row (r_begin - 2 + q) lives in slot q % 6
   uint32_t raw[3][2][4];                             // ring: row pair j (rows r_begin + 2 + 2j, + 3 + 2j) in slot j % 3
   {
@@ -616,14 +644,14 @@ __global__ __launch_bounds__(THREADS, 2) void stream_kernel(const SArgs a) {
       load_row(r_begin + 2 + 2 * j, raw[j][0]);
       load_row(r_begin + 3 + 2 * j, raw[j][1]);
     }
-    for (int e = threadIdx.x; e < 4096; e += THREADS) lut[e] = tile::decode_scaled<E>((uint32_t)e, p.k_decode);
+    fill_lut<E, LV>(lut, p);
     MI_SSTAMP(1);
     __syncthreads();                                  // the table is complete, `arrived` is zero for everyone; the kernel's only barrier besides pull()
     // the pass's scalars while the loads fly
     if constexpr (EPI == S_RH_MINMAX) pull<ew::FIN_STATS>(a, p.partials + (size_t)ROW_STATS * p.part_stride, sh_fp, sh_tot);
     if constexpr (EPI == S_RH_STORE) pull<ew::FIN_BOUNDS2>(a, p.partials + (size_t)ROW_BOUNDS2 * p.part_stride, sh_fp, sh_tot);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) decode_row(pro[q], lut, lane, win[q]);
+    for (int q = 0; q < 4; ++q) decode_row<E, LV>(pro[q], lut, lane, win[q], (q & 1) ? lv_odd : lv_even);   // r_begin is even
   }
   MI_SSTAMP(2);
 
@@ -664,8 +692,8 @@ __global__ __launch_bounds__(THREADS, 2) void stream_kernel(const SArgs a) {
     constexpr int PH = decltype(ph_c)::value;
     const int r = r_begin + 2 * i;
     // the pair's two new window rows (image rows r + 2, r + 3), loaded three pairs ago
-    decode_row(raw[PH][0], lut, lane, win[(2 * PH + 4) % 6]);
-    decode_row(raw[PH][1], lut, lane, win[(2 * PH + 5) % 6]);
+    decode_row<E, LV>(raw[PH][0], lut, lane, win[(2 * PH + 4) % 6], lv_even);
+    decode_row<E, LV>(raw[PH][1], lut, lane, win[(2 * PH + 5) % 6], lv_odd);
     load_row(r + 8, raw[PH][0]);
     load_row(r + 9, raw[PH][1]);
     if (r >= r_end) return;                           // wave-uniform: a dead pair of the last rotation
@@ -865,7 +893,7 @@ struct SubArgs {
   void* subs[LOAD_BATCH];
 };
 
-template <class E, int PR, int PC>
+template <class E, int PR, int PC, int LV = 0>
 __global__ __launch_bounds__(THREADS) void sub_kernel(const SubArgs a) {
   constexpr bool EXACT = sizeof(E) == 2;
   const Params& p = a.t;
@@ -894,14 +922,24 @@ __global__ __launch_bounds__(THREADS) void sub_kernel(const SubArgs a) {
     raw[q][0] = d.x; raw[q][1] = d.y; raw[q][2] = d.z;
     raw[q][3] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, ext_off + row_off, 0, 0);
   }
-  for (int e = threadIdx.x; e < 4096; e += THREADS) lut[e] = tile::decode_scaled<E>((uint32_t)e, p.k_decode);
+  if constexpr (LV == 0) {
+    for (int e = threadIdx.x; e < 4096; e += THREADS) lut[e] = tile::decode_scaled<E>((uint32_t)e, p.k_decode);
+  } else {
+    fill_lut<E, LV>(lut, p);
+  }
   __syncthreads();
   float wq[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) wq[i] = vgpr(wq_value(i));
   WinRow w6[6];
+  if constexpr (LV == 0) {
 #pragma unroll
-  for (int q = 0; q < 5; ++q) decode_row(raw[q], lut, lane, w6[q]);
+    for (int q = 0; q < 5; ++q) decode_row(raw[q], lut, lane, w6[q]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 5; ++q)                        // (row is even: row - 2 + q has the parity of q)
+      decode_row<E, LV>(raw[q], lut, lane, w6[q], LV == 2 ? tile::row_levels(p, q) : tile::RowLevels{});
+  }
 #pragma unroll
   for (int j = 0; j < 12; ++j) w6[5].v[j] = 0.f;         // (strip row 0 does not look at the window's sixth row)
   const bool is_left = col_ok && c0 == 0, is_right = col_ok && c0 + 8 == p.W;

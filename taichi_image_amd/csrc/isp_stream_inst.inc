@@ -8,6 +8,13 @@ namespace strm {
 template <class E>
 static int launch_e(const SArgs& a, int epi, hipStream_t s) {
   const dim3 grid(a.n_blocks, epi == S_STORE && a.n_batch > 0 ? a.n_batch : 1), block(THREADS);
+  if (a.t.levels) {                                // sensor levels (mi_isp_load_packed_levels): the load's store pass only
+    if (epi != S_STORE) { mi_set_error("stream: sensor levels take the store pass only"); return 1; }
+    if (a.t.levels == 1) hipLaunchKernelGGL((stream_kernel<E, PAT_PR, PAT_PC, S_STORE, 1>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((stream_kernel<E, PAT_PR, PAT_PC, S_STORE, 2>), grid, block, 0, s, a);
+    MI_LAUNCH_CHECK();
+    return 0;
+  }
   switch (epi) {
     case S_STORE: hipLaunchKernelGGL((stream_kernel<E, PAT_PR, PAT_PC, S_STORE>), grid, block, 0, s, a); break;
     case S_BOUNDS: hipLaunchKernelGGL((stream_kernel<E, PAT_PR, PAT_PC, S_BOUNDS>), grid, block, 0, s, a); break;
@@ -27,8 +34,17 @@ int PAT_FN(const SArgs& a, int work_dtype, int epi, hipStream_t s) {
 
 int PAT_SUB_FN(const SubArgs& a, int work_dtype, hipStream_t s) {
   const dim3 grid(a.n_blocks, a.n_batch), block(THREADS);
-  if (work_dtype == MI_F16) hipLaunchKernelGGL((sub_kernel<half_t, PAT_PR, PAT_PC>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((sub_kernel<float, PAT_PR, PAT_PC>), grid, block, 0, s, a);
+  if (a.t.levels == 1) {
+    if (work_dtype == MI_F16) hipLaunchKernelGGL((sub_kernel<half_t, PAT_PR, PAT_PC, 1>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((sub_kernel<float, PAT_PR, PAT_PC, 1>), grid, block, 0, s, a);
+  } else if (a.t.levels == 2) {
+    if (work_dtype == MI_F16) hipLaunchKernelGGL((sub_kernel<half_t, PAT_PR, PAT_PC, 2>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((sub_kernel<float, PAT_PR, PAT_PC, 2>), grid, block, 0, s, a);
+  } else if (work_dtype == MI_F16) {
+    hipLaunchKernelGGL((sub_kernel<half_t, PAT_PR, PAT_PC>), grid, block, 0, s, a);
+  } else {
+    hipLaunchKernelGGL((sub_kernel<float, PAT_PR, PAT_PC>), grid, block, 0, s, a);
+  }
   MI_LAUNCH_CHECK();
   return 0;
 }
@@ -37,7 +53,12 @@ int PAT_SUB_FN(const SubArgs& a, int work_dtype, hipStream_t s) {
 
 namespace rstrm {
 int PAT_FN(const RSArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((resize_kernel<PAT_PR, PAT_PC>), dim3(a.n_blocks, a.n_batch > 0 ? a.n_batch : 1), dim3(THREADS), 0, s, a);
+  const dim3 grid(a.n_blocks, a.n_batch > 0 ? a.n_batch : 1);
+  switch (a.t.levels) {                              // sensor levels: 1 in the decode table, 2 per site in registers
+    case 0: hipLaunchKernelGGL((resize_kernel<PAT_PR, PAT_PC>), grid, dim3(THREADS), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((resize_kernel<PAT_PR, PAT_PC, 1>), grid, dim3(THREADS), 0, s, a); break;
+    default: hipLaunchKernelGGL((resize_kernel<PAT_PR, PAT_PC, 2>), grid, dim3(THREADS), 0, s, a); break;
+  }
   MI_LAUNCH_CHECK();
   return 0;
 }

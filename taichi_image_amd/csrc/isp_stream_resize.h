@@ -61,7 +61,8 @@ MI_DEV int first_with_origin(int x, float s, int n_src, int n_dst) {
   return c < n_dst ? c : n_dst;
 }
 
-template <int PR, int PC>
+// LV: sensor levels (tile::Params::levels; strm::decode_row)
+template <int PR, int PC, int LV = 0>
 __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
   typedef half_t E;
   const Params& p = a.t;
@@ -100,14 +101,23 @@ __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
   };
   // the lane right of the band's last lane is inactive and decodes zeros - but the band's last lane needs the REAL two
   // pixels to its right: it takes them from its edge dword like lane 63 does (decode_row_edge below)
-  auto decode = [&](const uint32_t (&d)[4], WinRow& row) {
+  // (LV == 2: `lv` the levels of the row's parity; r_begin is even, so window slot q has the parity of q)
+  auto decode = [&](const uint32_t (&d)[4], WinRow& row, const tile::RowLevels& lv) {
     uint32_t v[8];
     tile::unpack12x8(d[0], d[1], d[2], false, v);
     const uint32_t w = lane == 0 ? d[3] >> 8 : d[3] & 0xFFFFFFu;
     float own[8];
+    float x0, x1;
+    if constexpr (LV == 2) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) own[i] = lut[v[i]];
-    const float x0 = lut[w & 0xFFFu], x1 = lut[w >> 12];
+      for (int i = 0; i < 8; ++i) own[i] = tile::decode_level<E>(v[i], (i & 1) ? lv.b1 : lv.b0, (i & 1) ? lv.k1 : lv.k0);
+      x0 = tile::decode_level<E>(w & 0xFFFu, lv.b0, lv.k0);
+      x1 = tile::decode_level<E>(w >> 12, lv.b1, lv.k1);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) own[i] = lut[v[i]];
+      x0 = lut[w & 0xFFFu]; x1 = lut[w >> 12];
+    }
     const float l0 = from_left(own[6], x0), l1 = from_left(own[7], x1);
     const float r0 = from_right(own[0], x0), r1 = from_right(own[1], x1);
     row.v[0] = l0; row.v[1] = l1;
@@ -166,6 +176,8 @@ __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
   float wq[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) wq[i] = vgpr(wq_value(i));
+  const tile::RowLevels lv_even = LV == 2 ? tile::row_levels(p, 0) : tile::RowLevels{},
+                        lv_odd = LV == 2 ? tile::row_levels(p, 1) : tile::RowLevels{};
   WinRow win[6];
   uint32_t raw[3][2][4];
   {
@@ -177,10 +189,10 @@ __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
       load_row(r_begin + 2 + 2 * j, raw[j][0]);
       load_row(r_begin + 3 + 2 * j, raw[j][1]);
     }
-    for (int e = threadIdx.x; e < 4096; e += THREADS) lut[e] = tile::decode_scaled<E>((uint32_t)e, p.k_decode);
+    strm::fill_lut<E, LV>(lut, p);
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < 4; ++q) decode(pro[q], win[q]);
+    for (int q = 0; q < 4; ++q) decode(pro[q], win[q], (q & 1) ? lv_odd : lv_even);
   }
   MI_SSTAMP(1);
   const bool is_left = col_ok && c0 == 0, is_right = col_ok && c0 + 8 == p.W;
@@ -272,8 +284,8 @@ __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
   auto body = [&](auto ph_c, int i) {
     constexpr int PH = decltype(ph_c)::value;
     const int r = r_begin + 2 * i;
-    decode(raw[PH][0], win[(2 * PH + 4) % 6]);
-    decode(raw[PH][1], win[(2 * PH + 5) % 6]);
+    decode(raw[PH][0], win[(2 * PH + 4) % 6], lv_even);
+    decode(raw[PH][1], win[(2 * PH + 5) % 6], lv_odd);
     load_row(r + 8, raw[PH][0]);
     load_row(r + 9, raw[PH][1]);
     if (r > r_last) return;                            // wave-uniform

@@ -93,6 +93,12 @@ struct Params {
   // instruction with an SGPR operand issues at half the rate of one with VGPR / literal operands
   // (v_fmac_f32 v, s, v: 0.57 wave-instr/ns/SIMD; v_fmac_f32 v, literal, v: 0.95).
   float wq[8];
+  // sensor levels (mi_isp_levels) of packed / u16 sources: 0 none (the kernels compiled without them run); 1 one black
+  // level for every CFA site; 2 one per site.  Site s = (row & 1) * 2 + (col & 1) of the raw frame; a code v decodes to
+  // cast(f32(max(v - lv_black[s], 0)) * lv_k[s], E), lv_k[s] = f32(scale(E) / (white - lv_black[s])).
+  int levels;
+  int lv_black[4];
+  float lv_k[4];
 };
 
 // the distinct weight values of KW and their slot in Params::wq
@@ -192,6 +198,28 @@ MI_DEV void unpack12x8(uint32_t d0, uint32_t d1, uint32_t d2, bool ids, uint32_t
 // scaled write of packed.py:98-100, cast(f32(v) * f32(scale/4095), E), widened back to fp32
 template <class E> MI_DEV float decode_scaled(uint32_t v, float k) { return (float)cast_out<E>((float)v * k); }
 
+// the same with a sensor black level b: cast(f32(max(v - b, 0)) * k, E); b = 0 gives decode_scaled's bits
+template <class E> MI_DEV float decode_level(uint32_t v, int b, float k) {
+  const int d = (int)v - b;
+  return (float)cast_out<E>((float)(d > 0 ? d : 0) * k);
+}
+
+// 8 codes of one raw row r, columns c .. c + 7 with c even, through the levels of p (Params::levels != 0)
+// (selects, no run-time index into the parameter arrays: that would send them through scratch)
+struct RowLevels { int b0, b1; float k0, k1; };      // even / odd columns of one raw row
+MI_DEV RowLevels row_levels(const Params& p, int r) {
+  const bool odd = (r & 1) != 0;
+  return {odd ? p.lv_black[2] : p.lv_black[0], odd ? p.lv_black[3] : p.lv_black[1],
+          odd ? p.lv_k[2] : p.lv_k[0], odd ? p.lv_k[3] : p.lv_k[1]};
+}
+template <class E> MI_DEV void decode_levels8(const uint32_t (&v)[8], const Params& p, int r, float (&out)[8]) {
+  const RowLevels l = row_levels(p, r);
+  const int b0 = l.b0, b1 = l.b1;
+  const float k0 = l.k0, k1 = l.k1;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out[i] = decode_level<E>(v[i], (i & 1) ? b1 : b0, (i & 1) ? k1 : k0);
+}
+
 // 8 values at once; for the f16 work type the products are rounded in pairs (v_cvt_pk_f16_f32: the same
 // RNE conversion of the same fp32 products, half the conversion instructions) and widened back
 template <class E> MI_DEV void decode_scaled8(const uint32_t (&v)[8], float k, float (&out)[8]) {
@@ -222,7 +250,7 @@ MI_DEV void lds_store8(float* row, int lu, const float (&v)[8]) {
 // Out-of-image elements are zero (they contribute 0*w, an exact no-op, to the accumulators).
 // ---------------------------------------------------------------------------------------------
 // General packed path: any width / alignment, byte loads.
-template <class E>
+template <class E, bool LV = false>
 MI_DEV void fill_packed(const Params& p, float* lds, int rb, int cb) {
   const uint8_t* base = static_cast<const uint8_t*>(p.src);
   const bool is16 = p.src_kind == SRC_PACKED16;
@@ -243,15 +271,26 @@ MI_DEV void fill_packed(const Params& p, float* lds, int rb, int cb) {
           const uint32_t w = q[3 * j] | (q[3 * j + 1] << 8) | (q[3 * j + 2] << 16);
           unpack_pair(w, ids, a, b);
         }
-        dst[lds_pos(lu * 8 + 2 * j)] = decode_scaled<E>(a, p.k_decode);
-        dst[lds_pos(lu * 8 + 2 * j + 1)] = decode_scaled<E>(b, p.k_decode);
+        if constexpr (LV) {
+          const RowLevels l = row_levels(p, r);
+          dst[lds_pos(lu * 8 + 2 * j)] = decode_level<E>(a, l.b0, l.k0);
+          dst[lds_pos(lu * 8 + 2 * j + 1)] = decode_level<E>(b, l.b1, l.k1);
+        } else {
+          dst[lds_pos(lu * 8 + 2 * j)] = decode_scaled<E>(a, p.k_decode);
+          dst[lds_pos(lu * 8 + 2 * j + 1)] = decode_scaled<E>(b, p.k_decode);
+        }
       }
     } else {
       const uint8_t* q = rowp + (size_t)(inside ? c : 0) * 2;
       for (int j = 0; j < 8; ++j) {
         uint32_t a = 0;
         if (j < n) a = q[2 * j] | (q[2 * j + 1] << 8);
-        dst[lds_pos(lu * 8 + j)] = decode_scaled<E>(a, p.k_decode);
+        if constexpr (LV) {
+          const RowLevels l = row_levels(p, r);
+          dst[lds_pos(lu * 8 + j)] = (j & 1) ? decode_level<E>(a, l.b1, l.k1) : decode_level<E>(a, l.b0, l.k0);
+        } else {
+          dst[lds_pos(lu * 8 + j)] = decode_scaled<E>(a, p.k_decode);
+        }
       }
     }
   }
@@ -261,7 +300,7 @@ MI_DEV void fill_packed(const Params& p, float* lds, int rb, int cb) {
 // outside.  All global loads of a lane (up to 3 units = 36/48 bytes) are issued before the first
 // use, so one memory latency is paid per tile instead of one per unit; an all-zero unit decodes to
 // zeros, so out-of-image units need no branch after the load.
-template <class E>
+template <class E, bool LV = false>
 MI_DEV void fill_packed_fast(const Params& p, float* lds, int rb, int cb) {
   constexpr int NUNITS = LDS_ROWS * UNITS;
   constexpr int NIT = (NUNITS + THREADS - 1) / THREADS;
@@ -272,6 +311,7 @@ MI_DEV void fill_packed_fast(const Params& p, float* lds, int rb, int cb) {
   const size_t pitch = is16 ? (size_t)p.W * 2 : (size_t)p.W * 3 / 2;
   uint4 raw[NIT];
   int off[NIT];
+  int row[NIT];                                      // (LV only) the image row of the unit
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int u = threadIdx.x + it * THREADS;
@@ -279,6 +319,7 @@ MI_DEV void fill_packed_fast(const Params& p, float* lds, int rb, int cb) {
     const int lu = u - lr * UNITS;
     const int r = rb + lr, c = cb + lu * 8;
     off[it] = u < NUNITS ? lr * PITCH + lu * 4 : -1;
+    row[it] = r;
     raw[it] = make_uint4(0, 0, 0, 0);
     if (u < NUNITS && r >= 0 && r < p.H && c >= 0 && c < p.W) {
       const uint8_t* rowp = base + (size_t)r * pitch;
@@ -302,7 +343,8 @@ MI_DEV void fill_packed_fast(const Params& p, float* lds, int rb, int cb) {
       v[4] = d.z & 0xFFFFu; v[5] = d.z >> 16; v[6] = d.w & 0xFFFFu; v[7] = d.w >> 16;
     }
     float out[8];
-    decode_scaled8<E>(v, p.k_decode, out);
+    if constexpr (LV) decode_levels8<E>(v, p, row[it], out);
+    else decode_scaled8<E>(v, p.k_decode, out);
     lds_store8(lds + off[it], 0, out);
   }
 }
@@ -363,7 +405,7 @@ MI_DEV void fill_plain(const Params& p, float* lds, int rb, int cb) {
   }
 }
 
-template <class E>
+template <class E, bool LV = false>
 MI_DEV void fill_tile(const Params& p, float* lds, int rb, int cb) {
   switch (p.src_kind) {
     case SRC_CFA_U8: fill_plain<uint8_t>(p, lds, rb, cb); break;
@@ -371,8 +413,8 @@ MI_DEV void fill_tile(const Params& p, float* lds, int rb, int cb) {
     case SRC_CFA_F16: fill_plain<half_t>(p, lds, rb, cb); break;
     case SRC_CFA_F32: fill_plain<float>(p, lds, rb, cb); break;
     default:
-      if (p.src_fast) fill_packed_fast<E>(p, lds, rb, cb);
-      else fill_packed<E>(p, lds, rb, cb);
+      if (p.src_fast) fill_packed_fast<E, LV>(p, lds, rb, cb);
+      else fill_packed<E, LV>(p, lds, rb, cb);
       break;
   }
 }
@@ -575,7 +617,8 @@ MI_DEV void store_row_dyn(const Params& p, int r, int c, const float (&v)[24], i
 #define MI_STAMP(i) do {} while (0)
 #endif
 template <class E> constexpr int dtype_code() { return sizeof(E) == 2 ? (int)MI_F16 : (int)MI_F32; }
-template <class E, int PR, int PC, int EPI, int HOT = 0>
+// LV: the packed source carries sensor levels (Params::levels != 0; HOT == 0 only)
+template <class E, int PR, int PC, int EPI, int HOT = 0, bool LV = false>
 __global__ __launch_bounds__(THREADS) void tile_kernel(const Params p_in) {
   constexpr bool EXACT = sizeof(E) == 2;
   Params p = p_in;
@@ -614,7 +657,7 @@ __global__ __launch_bounds__(THREADS) void tile_kernel(const Params p_in) {
   MI_STAMP(0);
   if constexpr (HOT == 1) fill_packed_fast<E>(p, lds, r0 - 2, c0 - 8);
   else if constexpr (HOT >= 2) fill_cfa_fast<CfaT>(p, lds, r0 - 2, c0 - 8);
-  else if (!(MI_DEBUG_SKIP(p) & 1)) fill_tile<E>(p, lds, r0 - 2, c0 - 8);
+  else if (!(MI_DEBUG_SKIP(p) & 1)) fill_tile<E, LV>(p, lds, r0 - 2, c0 - 8);
   MI_STAMP(1);
   __syncthreads();
   MI_STAMP(2);

@@ -122,6 +122,10 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--resize_width", type=int, default=0)
     tone.add_argument("--transform", type=transform, default=ImageTransform.rotate_90)
     tone.add_argument("--correct_colors", action="store_true")
+    # sensor levels (an extension): one black level, or four - one per CFA site (row & 1) * 2 + (col & 1) - and the white
+    # level (default: 4095, the packed-12 full scale)
+    tone.add_argument("--black-level", dest="black_level", type=int, nargs="+", default=None)
+    tone.add_argument("--white-level", dest="white_level", type=int, default=None)
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -135,11 +139,17 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     if args.scan is None and args.images is None:
         raise ValueError("No --scan or --images specified")
+    black = args.black_level
+    if black is not None and len(black) not in (1, 4):
+        raise ValueError(f"--black-level takes one value or four (one per CFA site), got {len(black)}")
+    black = black[0] if black is not None and len(black) == 1 else black
+    camera_isp._check_levels(black, args.white_level, 12)          # before any frame is read
     index = ScanIndex.of_scan(args.scan) if args.scan is not None else ScanIndex.of_directory(args.images)
     print(f"{len(index.cameras)} camera(s) {[c.name for c in index.cameras]}, {len(index.frames)} frame(s) each")
     device = torch.device(args.device)
     isp = camera_isp.Camera32(bayer.BayerPattern.RGGB, transform=args.transform, moving_alpha=args.moving_alpha,
-                              resize_width=args.resize_width, correct_colors=args.correct_colors, device=device)
+                              resize_width=args.resize_width, correct_colors=args.correct_colors, device=device,
+                              black_level=black, white_level=args.white_level)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
