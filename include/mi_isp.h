@@ -236,6 +236,36 @@ int mi_isp_load_packed_batch_levels(const uint8_t* const* packed_host, void* con
  * that black 0 / white 65535 keeps its bits. */
 int mi_isp_load_convert_levels(const void* src_dev, void* dst_dev, int H, int W, int mode, int out_dtype,
                                const mi_isp_levels* levels_host, void* stream);
+
+/* ---- lens shading (flat-field / vignetting correction) ----------------------------------------------------------------
+ * A gain grid of f32 on the device: sites = 1 (one grid for every site) or 4 (one per CFA site s = (row & 1) * 2 +
+ * (col & 1) of the raw frame, whatever the pattern), each grid_h x grid_w row-major, 2 <= grid_h, grid_w <= 64; the
+ * gains must be finite and within [0, 16] (the Python layer checks them; the library reads them on the device only).
+ * Node (i, j) sits at raw pixel (i * (H-1)/(grid_h-1), j * (W-1)/(grid_w-1)).  For raw pixel (r, c), every step one f32
+ * operation rounded to nearest, none contracted:
+ *   sy = f32((grid_h - 1) / (H - 1)), sx = f32((grid_w - 1) / (W - 1))   (in double on the host; 0 for H or W == 1)
+ *   v = f32(r) * sy; i = min(floor(v), grid_h - 2); ty = v - f32(i)    (u, j, tx the same along the columns)
+ *   a = G[i][j] + ty * (G[i+1][j] - G[i][j]);  b = G[i][j+1] + ty * (G[i+1][j+1] - G[i][j+1]);  g = a + tx * (b - a)
+ *   cfa = cast_work(x * g), x the f32 value the loader rounds to the work dtype without shading (with levels included).
+ * A grid of ones gives the bits of the call without shading.  The _shading twins take both a levels and a shading
+ * pointer; either may be NULL, and NULL / NULL is exactly the plain call.  They accept every case the plain entry point
+ * accepts and take the same path (mi_isp_load_packed_metered_is_fused, mi_isp_load_packed_scale_supported). */
+typedef struct { const float* gains_dev; int32_t sites; int32_t grid_h, grid_w; } mi_isp_shading;
+int mi_isp_load_packed_shading(const uint8_t* packed_dev, void* rgb_dev, int H, int W, int bits, int ids_format,
+                               int pattern, const float* ccm9_host, int work_dtype, int Hd, int Wd, float scale,
+                               const mi_isp_levels* levels_host, const mi_isp_shading* shading_host, void* stream);
+int mi_isp_load_packed_metered_shading(const uint8_t* packed_dev, void* rgb_dev, int H, int W, int bits, int ids_format,
+                                       int pattern, const float* ccm9_host, int work_dtype, int Hd, int Wd, float scale,
+                                       void* sub_dev, int sub_stride, const mi_isp_levels* levels_host,
+                                       const mi_isp_shading* shading_host, void* stream);
+int mi_isp_load_packed_batch_shading(const uint8_t* const* packed_host, void* const* rgb_host, void* const* subs_host,
+                                     int n, int H, int W, int bits, int ids_format, int pattern, const float* ccm9_host,
+                                     int work_dtype, int Hd, int Wd, float scale, int sub_stride,
+                                     const mi_isp_levels* levels_host, const mi_isp_shading* shading_host, void* stream);
+/* mi_isp_load_convert with levels and / or shading on a row-major H x W frame: levels need MI_LOAD_16U (as
+ * mi_isp_load_convert_levels); shading takes every mode, x being the f32 value the mode converts. */
+int mi_isp_load_convert_shading(const void* src_dev, void* dst_dev, int H, int W, int mode, int out_dtype,
+                                const mi_isp_levels* levels_host, const mi_isp_shading* shading_host, void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==

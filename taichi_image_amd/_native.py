@@ -25,6 +25,11 @@ class Levels(ctypes.Structure):
     _fields_ = [("black", c_int32 * 4), ("white", c_int32)]
 
 
+class Shading(ctypes.Structure):
+    """mi_isp_shading: a lens shading gain grid on the device, `sites` (1 or 4) x grid_h x grid_w f32."""
+    _fields_ = [("gains_dev", c_void_p), ("sites", c_int32), ("grid_h", c_int32), ("grid_w", c_int32)]
+
+
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SIGNATURES = {
@@ -71,6 +76,15 @@ SIGNATURES = {
                                                 c_int, POINTER(c_float), c_int, c_int, c_int, c_float, c_int,
                                                 POINTER(Levels), _P]),
     "mi_isp_load_convert_levels": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Levels), _P]),
+    "mi_isp_load_packed_shading": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,
+                                           c_int, c_float, POINTER(Levels), POINTER(Shading), _P]),
+    "mi_isp_load_packed_metered_shading": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int,
+                                                   c_int, c_int, c_float, _P, c_int, POINTER(Levels), POINTER(Shading),
+                                                   _P]),
+    "mi_isp_load_packed_batch_shading": (c_int, [POINTER(_P), POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int,
+                                                 c_int, c_int, POINTER(c_float), c_int, c_int, c_int, c_float, c_int,
+                                                 POINTER(Levels), POINTER(Shading), _P]),
+    "mi_isp_load_convert_shading": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading), _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,
@@ -212,6 +226,13 @@ def levels_arg(black, white):
     if black is None:
         return None
     return Levels((c_int32 * 4)(*[int(b) for b in black]), int(white))
+
+
+def shading_arg(grid):
+    """A (sites, grid_h, grid_w) f32 device tensor -> a Shading for the *_shading entry points; None stays None."""
+    if grid is None:
+        return None
+    return Shading(grid.data_ptr(), grid.shape[0], grid.shape[1], grid.shape[2])
 
 
 _ws_cache: dict = {}

@@ -66,6 +66,87 @@ def _check_levels(black_level, white_level, bits=16):
     return black, white
 
 
+def _check_shading(lens_shading):
+    """A lens shading grid as the kernels take it: a contiguous (sites, Gh, Gw) f32 numpy array, sites 1 or 4, from a
+    (Gh, Gw) or (4, Gh, Gw) numpy array or torch tensor.  ValueError unless 2 <= Gh, Gw <= 64 and every gain is finite
+    and within [0, 16].  DESIGN.md 3, "Lens shading"."""
+    if isinstance(lens_shading, torch.Tensor):
+        g = lens_shading.detach().to("cpu", torch.float64).numpy()
+    elif isinstance(lens_shading, np.ndarray):
+        g = np.asarray(lens_shading, dtype=np.float64)
+    else:
+        raise ValueError(f"lens_shading must be a numpy array or a torch tensor, got {type(lens_shading).__name__}")
+    if g.ndim == 2:
+        g = g[None]
+    if g.ndim != 3 or g.shape[0] not in (1, 4) or (lens_shading.ndim == 3 and g.shape[0] != 4):
+        raise ValueError(f"lens_shading must be (Gh, Gw) or (4, Gh, Gw), got shape {tuple(lens_shading.shape)}")
+    if not (2 <= g.shape[1] <= 64 and 2 <= g.shape[2] <= 64):
+        raise ValueError(f"lens_shading grid {g.shape[1]} x {g.shape[2]} outside 2 .. 64 nodes per axis")
+    if not np.all(np.isfinite(g)):
+        raise ValueError("lens_shading gains must be finite")
+    if g.min() < 0 or g.max() > 16:
+        raise ValueError(f"lens_shading gains must be within [0, 16], got [{g.min()}, {g.max()}]")
+    return np.ascontiguousarray(g, dtype=np.float32)
+
+
+def lens_shading_from_flat(codes, grid=(17, 13), black_level=0, per_site=True):
+    """A lens shading grid from a flat-field capture (calibration, off the hot path; torch on the codes' device, or numpy).
+
+    codes: (H, W) raw codes (`packed.decode12(..., scaled=False)` gives them).  grid: (Gh, Gw) nodes, node (i, j) at raw
+    pixel (i * (H-1)/(Gh-1), j * (W-1)/(Gw-1)).  For each CFA site s = (row & 1) * 2 + (col & 1) and node: the mean of
+    max(code - black_s, 0) over the site's pixels within half a cell of the node (clipped to the frame), and
+    gain = max(the site's means) / mean.  per_site=False pools the four sites into one (Gh, Gw) grid.  Returns a
+    (4, Gh, Gw) grid (or (Gh, Gw)), f32, a torch tensor for torch codes and a numpy array otherwise; ValueError for a node
+    whose mean is zero."""
+    as_numpy = not isinstance(codes, torch.Tensor)
+    c = torch.from_numpy(np.asarray(codes)) if as_numpy else codes
+    if c.ndim != 2:
+        raise ValueError(f"codes must be (H, W), got shape {tuple(c.shape)}")
+    gh, gw = (int(grid[0]), int(grid[1]))
+    if not (2 <= gh <= 64 and 2 <= gw <= 64):
+        raise ValueError(f"grid {gh} x {gw} outside 2 .. 64 nodes per axis")
+    black = list(black_level) if isinstance(black_level, (list, tuple, np.ndarray)) else [black_level] * 4
+    if len(black) != 4:
+        raise ValueError(f"black_level must be one value or 4 (one per CFA site), got {len(black)}")
+    H, W = c.shape
+    c = c.to(torch.float64)
+    sums = torch.zeros((4, gh, gw), dtype=torch.float64, device=c.device)
+    counts = torch.zeros((4, gh, gw), dtype=torch.float64, device=c.device)
+
+    def ranges(n_px, n_nodes, off):
+        # per node: the index range [lo, hi) into the site's pixels (off, off + 2, ...) within half a cell of the node
+        cell = (n_px - 1) / (n_nodes - 1)
+        pos = np.arange(n_nodes) * cell
+        lo = np.clip(np.ceil(pos - cell / 2), 0, n_px - 1)
+        hi = np.clip(np.floor(pos + cell / 2), 0, n_px - 1)
+        klo = np.ceil((lo - off) / 2).astype(np.int64)
+        khi = np.floor((hi - off) / 2).astype(np.int64) + 1
+        return np.maximum(klo, 0), np.maximum(khi, np.maximum(klo, 0))
+
+    for s in range(4):
+        r0, c0 = s >> 1, s & 1
+        x = (c[r0::2, c0::2] - float(black[s])).clamp_min(0.0)
+        integ = torch.zeros((x.shape[0] + 1, x.shape[1] + 1), dtype=torch.float64, device=c.device)
+        integ[1:, 1:] = x.cumsum(0).cumsum(1)
+        rlo, rhi = (torch.from_numpy(v).to(c.device) for v in ranges(H, gh, r0))
+        clo, chi = (torch.from_numpy(v).to(c.device) for v in ranges(W, gw, c0))
+        rhi = rhi.clamp_max(x.shape[0]); chi = chi.clamp_max(x.shape[1])
+        R0, C0, R1, C1 = rlo[:, None], clo[None, :], rhi[:, None], chi[None, :]
+        sums[s] = integ[R1, C1] - integ[R0, C1] - integ[R1, C0] + integ[R0, C0]
+        counts[s] = ((R1 - R0).clamp_min(0) * (C1 - C0).clamp_min(0)).to(torch.float64)
+    if not per_site:
+        sums, counts = sums.sum(0, keepdim=True), counts.sum(0, keepdim=True)
+    if bool((counts == 0).any()):
+        raise ValueError("lens_shading_from_flat: a node has no pixel of its site within half a cell (grid too fine)")
+    means = sums / counts
+    if bool((means == 0).any()):
+        raise ValueError("lens_shading_from_flat: a node's flat-field mean is zero")
+    gains = (means.amax(dim=(1, 2), keepdim=True) / means).to(torch.float32)
+    if not per_site:
+        gains = gains[0]
+    return gains.cpu().numpy() if as_numpy else gains
+
+
 class MeteringTimeout(RuntimeError):
     """The grid barrier of an earlier one-launch update_metering on this device timed out (something else held compute
     units of the GPU for about a second).  That call left the metrics as they were - bounds folded from half of the blocks
@@ -177,7 +258,8 @@ def camera_isp(name: str, dtype=types.f32):
                      process_group=None,
                      reference_quirks: bool = False,
                      black_level=None,
-                     white_level: Optional[int] = None):
+                     white_level: Optional[int] = None,
+                     lens_shading=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -189,6 +271,7 @@ def camera_isp(name: str, dtype=types.f32):
             _typecheck("metering_stride", metering_stride, int)
             assert scale is None or resize_width == 0, "Cannot specify both scale and resize_width"
             _check_levels(black_level, white_level)
+            shading = None if lens_shading is None else _check_shading(lens_shading)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -213,6 +296,12 @@ def camera_isp(name: str, dtype=types.f32):
 
             self.metrics = None
             self.device = device
+            # lens shading (an extension): a private (sites, Gh, Gw) f32 grid on the device, uploaded once; None: no
+            # shading, the loaders run exactly as without it.  Grids a later set() replaced by another shape, or removed,
+            # stay referenced in _shading_retired for the ISP's lifetime, so no queued or captured launch reads a freed
+            # grid (a grid is at most 64 KB).  DESIGN.md 3, INTEGRATION.md.
+            self._shading = None if shading is None else torch.from_numpy(shading).to(device)
+            self._shading_retired = []
             # one-process-per-GPU sharding: statistics are all-reduced over this group (RCCL)
             self.process_group = process_group
 
@@ -226,11 +315,16 @@ def camera_isp(name: str, dtype=types.f32):
                 white_balance: Optional[np.ndarray] = None,
                 color_correction: Optional[np.ndarray] = None,
                 transform: Optional[interpolate.ImageTransform] = None,
-                black_level=None, white_level: Optional[int] = None):
-            """camera_isp.py:270-300; black_level / white_level (the extension): None leaves the current value."""
+                black_level=None, white_level: Optional[int] = None, lens_shading=None):
+            """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
+            value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
+            current stream (launches queued before on that stream read the old gains, later ones the new; a captured
+            graph reads the new ones at its next replay); a grid of another shape gets a new device tensor and the old
+            one stays allocated while the ISP lives."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
+            shading = None if lens_shading is None or lens_shading is False else _check_shading(lens_shading)
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -258,6 +352,25 @@ def camera_isp(name: str, dtype=types.f32):
                 self.black_level = black_level
             if white_level is not None:
                 self.white_level = white_level
+            if lens_shading is False:
+                if self._shading is not None:
+                    self._shading_retired.append(self._shading)
+                self._shading = None
+            elif shading is not None:
+                new = torch.from_numpy(shading)
+                if self._shading is not None and tuple(self._shading.shape) == tuple(new.shape):
+                    with torch.cuda.device(self.device):
+                        self._shading.copy_(new)
+                else:
+                    if self._shading is not None:
+                        self._shading_retired.append(self._shading)
+                    self._shading = new.to(self.device)
+
+        @property
+        def lens_shading(self) -> Optional[torch.Tensor]:
+            """The lens shading grid the loaders apply, (sites, Gh, Gw) f32 on the device (do not write it; use set), or
+            None."""
+            return self._shading
 
         def _levels(self, bits):
             """The Levels argument of the *_levels entry points for a `bits`-bit source, None without levels (ValueError
@@ -289,7 +402,12 @@ def camera_isp(name: str, dtype=types.f32):
                                  "load_16f / load_32f take normalised values")
             src = image.to(self.device).contiguous()
             cfa = torch.empty(image.shape, dtype=torch_dtype, device=self.device)
-            if lv is None:
+            sh = _native.shading_arg(self._shading)
+            if sh is not None:
+                _native.check(_native.lib().mi_isp_load_convert_shading(src.data_ptr(), cfa.data_ptr(), image.shape[0],
+                                                                        image.shape[1], mode, dtype.code, lv, sh,
+                                                                        _native.stream_ptr(self.device)))
+            elif lv is None:
                 _native.check(_native.lib().mi_isp_load_convert(src.data_ptr(), cfa.data_ptr(), cfa.numel(), mode,
                                                                 dtype.code, _native.stream_ptr(self.device)))
             else:
@@ -327,6 +445,10 @@ def camera_isp(name: str, dtype=types.f32):
             load = L.mi_isp_load_packed if lv is None else (lambda *a: L.mi_isp_load_packed_levels(*a[:-1], lv, a[-1]))
             load_metered = (L.mi_isp_load_packed_metered if lv is None
                             else (lambda *a: L.mi_isp_load_packed_metered_levels(*a[:-1], lv, a[-1])))
+            sh = _native.shading_arg(self._shading)
+            if sh is not None:                           # lens shading: the *_shading twins (levels or NULL)
+                load = lambda *a: L.mi_isp_load_packed_shading(*a[:-1], lv, sh, a[-1])   # noqa: E731
+                load_metered = lambda *a: L.mi_isp_load_packed_metered_shading(*a[:-1], lv, sh, a[-1])   # noqa: E731
             # camera_isp.py:302-312: output size and scale of resize_image
             if self.resize_width > 0:
                 scale = self.resize_width / w
@@ -412,7 +534,10 @@ def camera_isp(name: str, dtype=types.f32):
             args = (_native.ptr_array(srcs), _native.ptr_array(rgbs), None if subs is None else _native.ptr_array(subs),
                     len(srcs), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
                     _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, float(scale) if fused else 0.0, st)
-            if lv is None:
+            sh = _native.shading_arg(self._shading)
+            if sh is not None:
+                _native.check(L.mi_isp_load_packed_batch_shading(*args, lv, sh, _native.stream_ptr(self.device)))
+            elif lv is None:
                 _native.check(L.mi_isp_load_packed_batch(*args, _native.stream_ptr(self.device)))
             else:
                 _native.check(L.mi_isp_load_packed_batch_levels(*args, lv, _native.stream_ptr(self.device)))
@@ -575,8 +700,8 @@ def camera_isp(name: str, dtype=types.f32):
 
             with the same u8 outputs and the same metering state afterwards, bit for bit.  For a full-resolution
             Camera16 group that fits the chip (`mi_isp_camera_group_fits`: 4096 x 3072 on MI355X, metering stride 8, no
-            resize, no orientation transform, single process, every packed frame 4-byte aligned) the loaded images never
-            exist in memory: the metering reads a subsample demosaiced straight from the packed frames, and ONE persistent
+            resize, no orientation transform, no lens shading grid, single process, every packed frame 4-byte aligned) the
+            loaded images never exist in memory: the metering reads a subsample demosaiced straight from the packed frames, and ONE persistent
             launch takes every camera from packed bytes to its u8 image (csrc/isp_mega_cam.h).  Everything else takes the
             two calls above.
             keep_images=True returns `(outputs, images)`, the images holding what the reference leaves in them (p,
@@ -591,6 +716,7 @@ def camera_isp(name: str, dtype=types.f32):
             f0 = frames[0]
             lv = self._levels(12)                            # (sensor levels: checked before anything runs)
             fused = (dtype is types.f16 and not ids_format and self.resize_width == 0 and self.scale is None
+                     and self._shading is None                # (lens shading: the two calls below)
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8
                      and 1 <= len(frames) <= 64
                      and all(isinstance(f, torch.Tensor) and f.ndim == 2 and f.dtype == torch.uint8 and f.shape == f0.shape

@@ -22,7 +22,7 @@ void mi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int mi_isp_version(void) { return 1100; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
+extern "C" int mi_isp_version(void) { return 1200; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
 extern "C" const char* mi_isp_last_error(void) { return g_err; }
 
 extern "C" int mi_isp_bayer_weights(int32_t out[4 * 13 * 3]) {
@@ -116,6 +116,26 @@ static int apply_levels(tile::Params& p, const mi_isp_levels* lv, int bits, cons
   return 0;
 }
 
+// sensor levels and lens shading of a packed source.  A shading grid always takes the per-site register decode
+// (levels 2): without levels it decodes with black 0 and k_decode, which is the plain decode.
+static int apply_levels_shading(tile::Params& p, const mi_isp_levels* lv, const mi_isp_shading* sh, int bits,
+                                const char* who) {
+  if (int rc = apply_levels(p, lv, bits, who)) return rc;
+  if (int rc = apply_shading(p, sh, p.H, p.W, who)) return rc;
+  if (p.shading) {
+    if (p.levels == 0)
+      for (int s = 0; s < 4; ++s) { p.lv_black[s] = 0; p.lv_k[s] = p.k_decode; }
+    p.levels = 2;
+  }
+  return 0;
+}
+
+// the _shading twins check their grid first, before any other argument (apply_shading again fills it per frame)
+static int check_shading(const mi_isp_shading* sh, const char* who) {
+  tile::Params p = {};
+  return apply_shading(p, sh, 2, 2, who);
+}
+
 #ifdef MI_STREAM_STAMPS
 // measurement build only: a home for the in-kernel stamps of the kernels that take no workspace (16 words per wave)
 static float* stamp_buffer() {
@@ -146,12 +166,13 @@ static bool use_stream(const tile::Params& p, int work_dtype, const void* out, i
 
 static int load_packed_impl(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
                             int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
-                            void* sub, int sub_stride, const mi_isp_levels* lv, void* stream) {
+                            void* sub, int sub_stride, const mi_isp_levels* lv, const mi_isp_shading* sh,
+                            void* stream) {
   MI_REQUIRE(rgb, "load_packed: null output");
   tile::Params p = {};
   if (int rc = fill_common(p, H, W, pattern, ccm9, "load_packed")) return rc;
   if (int rc = packed_params(p, packed, H, W, bits, ids_format, work_dtype, "load_packed")) return rc;
-  if (int rc = apply_levels(p, lv, bits, "load_packed")) return rc;
+  if (int rc = apply_levels_shading(p, lv, sh, bits, "load_packed")) return rc;
   p.dst = rgb; p.out_dtype = work_dtype; p.out_scale = 1.f;
   if (scale > 0.f) {
     // unpack -> demosaic -> bilinear fused (isp_resize_tile.h); the caller checks the scale first
@@ -195,14 +216,22 @@ extern "C" int mi_isp_load_packed(const uint8_t* packed, void* rgb, int H, int W
                                   int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
                                   void* stream) {
   return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, nullptr, 0,
-                          nullptr, stream);
+                          nullptr, nullptr, stream);
 }
 
 extern "C" int mi_isp_load_packed_levels(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
                                          int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
                                          const mi_isp_levels* levels, void* stream) {
   return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, nullptr, 0,
-                          levels, stream);
+                          levels, nullptr, stream);
+}
+
+extern "C" int mi_isp_load_packed_shading(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
+                                          int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
+                                          const mi_isp_levels* levels, const mi_isp_shading* shading, void* stream) {
+  if (int rc = check_shading(shading, "load_packed")) return rc;
+  return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, nullptr, 0,
+                          levels, shading, stream);
 }
 
 // The cameras of a group in ONE launch per 8 (grid.y = camera): dispatch, decode table, first loads and drain are paid per
@@ -210,7 +239,8 @@ extern "C" int mi_isp_load_packed_levels(const uint8_t* packed, void* rgb, int H
 // cameras, 43.0 -> ~39.5 us per frame).  Same arithmetic, same bits as n calls of mi_isp_load_packed[_metered].
 static int load_packed_batch_impl(const uint8_t* const* packed, void* const* rgb, void* const* subs, int n, int H, int W,
                                   int bits, int ids_format, int pattern, const float* ccm9, int work_dtype, int Hd,
-                                  int Wd, float scale, int sub_stride, const mi_isp_levels* lv, void* stream) {
+                                  int Wd, float scale, int sub_stride, const mi_isp_levels* lv, const mi_isp_shading* sh,
+                                  void* stream) {
   MI_REQUIRE(packed && rgb, "load_packed_batch: null pointer");
   MI_REQUIRE(n >= 0, "load_packed_batch: negative frame count");
   for (int i = 0; i < n; ++i) MI_REQUIRE(packed[i] && rgb[i] && (!subs || subs[i]), "load_packed_batch: frame %d has a null buffer", i);
@@ -223,7 +253,7 @@ static int load_packed_batch_impl(const uint8_t* const* packed, void* const* rgb
     tile::Params p = {};
     if (int rc = fill_common(p, H, W, pattern, ccm9, "load_packed_batch")) return rc;
     if (int rc = packed_params(p, packed[i], H, W, bits, ids_format, work_dtype, "load_packed_batch")) return rc;
-    if (int rc = apply_levels(p, lv, bits, "load_packed_batch")) return rc;
+    if (int rc = apply_levels_shading(p, lv, sh, bits, "load_packed_batch")) return rc;
     p.dst = rgb[i]; p.out_dtype = work_dtype; p.out_scale = 1.f;
     if (resize) {
       same = Hd > 0 && Wd > 0 && H >= 2 && W >= 2 && use_stream(p, work_dtype, nullptr, work_dtype) &&
@@ -237,7 +267,7 @@ static int load_packed_batch_impl(const uint8_t* const* packed, void* const* rgb
   if (!same) {                                               // some frame needs another kernel: one by one
     for (int i = 0; i < n; ++i)
       if (int rc = load_packed_impl(packed[i], rgb[i], H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale,
-                                    subs ? subs[i] : nullptr, sub_stride, lv, stream))
+                                    subs ? subs[i] : nullptr, sub_stride, lv, sh, stream))
         return rc;
     return 0;
   }
@@ -272,7 +302,7 @@ extern "C" int mi_isp_load_packed_batch(const uint8_t* const* packed, void* cons
                                         int bits, int ids_format, int pattern, const float* ccm9, int work_dtype, int Hd,
                                         int Wd, float scale, int sub_stride, void* stream) {
   return load_packed_batch_impl(packed, rgb, subs, n, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale,
-                                sub_stride, nullptr, stream);
+                                sub_stride, nullptr, nullptr, stream);
 }
 
 extern "C" int mi_isp_load_packed_batch_levels(const uint8_t* const* packed, void* const* rgb, void* const* subs, int n, int H,
@@ -280,7 +310,16 @@ extern "C" int mi_isp_load_packed_batch_levels(const uint8_t* const* packed, voi
                                                int work_dtype, int Hd, int Wd, float scale, int sub_stride,
                                                const mi_isp_levels* levels, void* stream) {
   return load_packed_batch_impl(packed, rgb, subs, n, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale,
-                                sub_stride, levels, stream);
+                                sub_stride, levels, nullptr, stream);
+}
+
+extern "C" int mi_isp_load_packed_batch_shading(const uint8_t* const* packed, void* const* rgb, void* const* subs, int n,
+                                                int H, int W, int bits, int ids_format, int pattern, const float* ccm9,
+                                                int work_dtype, int Hd, int Wd, float scale, int sub_stride,
+                                                const mi_isp_levels* levels, const mi_isp_shading* shading, void* stream) {
+  if (int rc = check_shading(shading, "load_packed_batch")) return rc;
+  return load_packed_batch_impl(packed, rgb, subs, n, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale,
+                                sub_stride, levels, shading, stream);
 }
 
 extern "C" int mi_isp_load_packed_metered_is_fused(int H, int W, int bits, int ids_format, int work_dtype, int sub_stride) {
@@ -295,7 +334,7 @@ extern "C" int mi_isp_load_packed_metered(const uint8_t* packed, void* rgb, int 
                                           void* sub, int sub_stride, void* stream) {
   MI_REQUIRE(sub && sub_stride >= 1, "load_packed_metered: need a subsample buffer and a positive stride");
   return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, sub, sub_stride,
-                          nullptr, stream);
+                          nullptr, nullptr, stream);
 }
 
 extern "C" int mi_isp_load_packed_metered_levels(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
@@ -303,7 +342,17 @@ extern "C" int mi_isp_load_packed_metered_levels(const uint8_t* packed, void* rg
                                                  void* sub, int sub_stride, const mi_isp_levels* levels, void* stream) {
   MI_REQUIRE(sub && sub_stride >= 1, "load_packed_metered: need a subsample buffer and a positive stride");
   return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, sub, sub_stride,
-                          levels, stream);
+                          levels, nullptr, stream);
+}
+
+extern "C" int mi_isp_load_packed_metered_shading(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
+                                                  int pattern, const float* ccm9, int work_dtype, int Hd, int Wd,
+                                                  float scale, void* sub, int sub_stride, const mi_isp_levels* levels,
+                                                  const mi_isp_shading* shading, void* stream) {
+  if (int rc = check_shading(shading, "load_packed_metered")) return rc;
+  MI_REQUIRE(sub && sub_stride >= 1, "load_packed_metered: need a subsample buffer and a positive stride");
+  return load_packed_impl(packed, rgb, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale, sub, sub_stride,
+                          levels, shading, stream);
 }
 
 extern "C" int mi_isp_load_packed_scale_supported(float scale) { return rtile::scales_fit(scale, scale) ? 1 : 0; }

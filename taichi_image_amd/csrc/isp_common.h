@@ -240,3 +240,40 @@ static inline int mi_partial_cap(int H, int W) {
   long cap = tiles < 4096 ? 4096 : tiles;
   return (int)cap;
 }
+
+// Lens shading (mi_isp_shading): the gain of raw pixel (r, c), clamped into the frame (out-of-image pixels
+// hold code 0 and take an edge gain): the node row i and column j of its cell, then G[i][j..j+1] lerped vertically first,
+// then horizontally; every operation one f32 rounding (the library builds with -ffp-contract=off), as the contract says
+struct ShadeAxis { int n; float t; };                // node index and weight along one axis
+MI_DEV ShadeAxis shade_axis(int x, int n_px, float s, int n_nodes) {
+  x = x < 0 ? 0 : (x < n_px ? x : n_px - 1);
+  const float v = (float)x * s;                      // >= 0: the conversion truncates = floor
+  const int i = (int)v < n_nodes - 2 ? (int)v : n_nodes - 2;
+  return {i, v - (float)i};
+}
+// P: any struct with H, W and the sh_* members of tile::Params
+template <class P> MI_DEV float shade_gain(const P& p, int r, int c) {
+  const ShadeAxis y = shade_axis(r, p.H, p.sh_sy, p.sh_gh), x = shade_axis(c, p.W, p.sh_sx, p.sh_gw);
+  const int site = p.sh_sites == 4 ? (r & 1) * 2 + (c & 1) : 0;
+  const float* g0 = p.sh_gain + ((size_t)site * p.sh_gh + y.n) * p.sh_gw + x.n;
+  const float* g1 = g0 + p.sh_gw;
+  const float a = g0[0] + y.t * (g1[0] - g0[0]);
+  const float b = g0[1] + y.t * (g1[1] - g0[1]);
+  return a + x.t * (b - a);
+}
+
+// the lens shading of an H x W raw frame (mi_isp_shading), checked on the host before anything is launched: fills the
+// shading / sh_* members of p (tile::Params, or any struct with the same members); NULL leaves p.shading 0
+template <class P> static int apply_shading(P& p, const mi_isp_shading* sh, int H, int W, const char* who) {
+  if (!sh) { p.shading = 0; return 0; }
+  MI_REQUIRE(sh->sites == 1 || sh->sites == 4, "%s: shading grid with %d sites (1 or 4)", who, (int)sh->sites);
+  MI_REQUIRE(sh->grid_h >= 2 && sh->grid_h <= 64 && sh->grid_w >= 2 && sh->grid_w <= 64,
+             "%s: shading grid %d x %d outside 2 .. 64", who, (int)sh->grid_h, (int)sh->grid_w);
+  MI_REQUIRE(sh->gains_dev, "%s: shading grid without gains", who);
+  p.shading = 1;
+  p.sh_gain = sh->gains_dev;
+  p.sh_sites = sh->sites; p.sh_gh = sh->grid_h; p.sh_gw = sh->grid_w;
+  p.sh_sy = H > 1 ? (float)((double)(sh->grid_h - 1) / (double)(H - 1)) : 0.f;
+  p.sh_sx = W > 1 ? (float)((double)(sh->grid_w - 1) / (double)(W - 1)) : 0.f;
+  return 0;
+}

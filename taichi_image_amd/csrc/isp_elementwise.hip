@@ -191,6 +191,38 @@ __global__ __launch_bounds__(EW_THREADS) void load_u16_levels_kernel(const uint1
   }
 }
 
+// load_16u / 16f / 32f with lens shading (mi_isp_load_convert_shading): the f32 value the loader converts - with levels
+// (16u only) load_u16_levels_kernel's quotient - times the gain of raw pixel (r, c) of the H x W frame, then the cast
+struct ConvShading { int H, W, shading; const float* sh_gain; int sh_sites, sh_gh, sh_gw; float sh_sy, sh_sx; };
+template <class T>
+__global__ __launch_bounds__(EW_THREADS) void load_shading_kernel(const void* __restrict__ src, T* __restrict__ dst,
+                                                                  int mode, int has_levels, const ConvLevels lv,
+                                                                  const ConvShading sh) {
+  const int64_t n = (int64_t)sh.H * sh.W;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int r = (int)(i / sh.W), c = (int)(i - (int64_t)r * sh.W);
+    float x;
+    if (mode == MI_LOAD_16U) {
+      const uint16_t v = static_cast<const uint16_t*>(src)[i];
+      if (has_levels) {
+        const bool ro = (r & 1) != 0, co = (c & 1) != 0;
+        const int b = ro ? (co ? lv.black[3] : lv.black[2]) : (co ? lv.black[1] : lv.black[0]);
+        const float den = ro ? (co ? lv.den[3] : lv.den[2]) : (co ? lv.den[1] : lv.den[0]);
+        const int d = (int)v - b;
+        x = (float)(d > 0 ? d : 0) / den;
+      } else {
+        x = (float)v / 65535.0f;
+      }
+    } else if (mode == MI_LOAD_32F) {
+      x = static_cast<const float*>(src)[i];
+    } else {
+      x = (float)static_cast<const uint16_t*>(src)[i];
+    }
+    dst[i] = cast_out<T>(x * shade_gain(sh, r, c));
+  }
+}
+
 // K5 rgb_to_bayer (bayer.py:101-112): channel index per site from pixel_orders (bayer.py:85-90)
 template <class T>
 __global__ __launch_bounds__(EW_THREADS) void mosaic_kernel(const T* __restrict__ rgb,
@@ -1771,6 +1803,41 @@ extern "C" int mi_isp_load_convert_levels(const void* src, void* dst, int H, int
     using T = decltype(tag);
     hipLaunchKernelGGL((load_u16_levels_kernel<T>), dim3(grid_for(n)), dim3(EW_THREADS), 0, s,
                        static_cast<const uint16_t*>(src), static_cast<T*>(dst), H, W, lv);
+    MI_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+extern "C" int mi_isp_load_convert_shading(const void* src, void* dst, int H, int W, int mode, int out_dtype,
+                                           const mi_isp_levels* levels, const mi_isp_shading* shading, void* stream) {
+  MI_REQUIRE(H >= 0 && W >= 0, "load_convert_shading: bad shape %dx%d", H, W);
+  ConvShading sh = {};
+  sh.H = H; sh.W = W;
+  if (int rc = apply_shading(sh, shading, H, W, "load_convert_shading")) return rc;
+  if (!shading) return mi_isp_load_convert_levels(src, dst, H, W, mode, out_dtype, levels, stream);
+  MI_REQUIRE(src && dst, "load_convert_shading: null pointer");
+  MI_REQUIRE(mode >= MI_LOAD_16U && mode <= MI_LOAD_16F, "load_convert_shading: bad mode %d", mode);
+  MI_REQUIRE(out_dtype == MI_F16 || out_dtype == MI_F32, "load_convert_shading: output must be f16/f32");
+  ConvLevels lv = {};
+  if (levels) {
+    MI_REQUIRE(mode == MI_LOAD_16U, "load_convert_shading: levels apply to u16 codes only (mode %d)", mode);
+    MI_REQUIRE(levels->white > 0 && levels->white <= 65535, "load_convert_shading: white level %d outside (0, 65535]",
+               (int)levels->white);
+    for (int s = 0; s < 4; ++s) {
+      MI_REQUIRE(levels->black[s] >= 0 && levels->black[s] < levels->white,
+                 "load_convert_shading: black level %d of site %d outside [0, white = %d)", (int)levels->black[s], s,
+                 (int)levels->white);
+      lv.black[s] = levels->black[s];
+      lv.den[s] = (float)(levels->white - levels->black[s]);
+    }
+  }
+  const int64_t n = (int64_t)H * W;
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  return dispatch_dtype(out_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((load_shading_kernel<T>), dim3(grid_for(n)), dim3(EW_THREADS), 0, s, src, static_cast<T*>(dst),
+                       mode, levels ? 1 : 0, lv, sh);
     MI_LAUNCH_CHECK();
     return 0;
   });

@@ -100,10 +100,12 @@ constexpr int FILL_NIT = (R_CAP * (C_CAP / 8) + THREADS - 1) / THREADS;
 
 // HOT: 12-bit standard packing with aligned rows, no colour matrix (the configuration of
 // Camera16/32.load_packed12), fixed at compile time; see tile::tile_kernel.
-// LV: the packed source carries sensor levels (Params::levels != 0; not with HOT)
-template <class E, int PR, int PC, bool HOT = false, bool LV = false>
+// LV: the packed source carries sensor levels (Params::levels != 0; not with HOT); SH: and a lens shading grid
+// (Params::shading; with LV)
+template <class E, int PR, int PC, bool HOT = false, bool LV = false, bool SH = false>
 __global__ __launch_bounds__(THREADS) void resize_tile_kernel(const RParams rp_in) {
   static_assert(!(HOT && LV), "the levels take the general fill");
+  static_assert(LV || !SH, "shading decodes through the levels");
   constexpr bool EXACT = sizeof(E) == 2;
   RParams rp = rp_in;
   Params& p = rp.t;
@@ -196,8 +198,16 @@ __global__ __launch_bounds__(THREADS) void resize_tile_kernel(const RParams rp_i
         }
       }
       float out[8];
-      if constexpr (LV) tile::decode_levels8<E>(v, p, r, out);
-      else tile::decode_scaled8<E>(v, p.k_decode, out);
+      if constexpr (SH) {
+        const tile::RowLevels l = tile::row_levels(p, r);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          out[i] = tile::decode_shaded<E>(v[i], (i & 1) ? l.b1 : l.b0, (i & 1) ? l.k1 : l.k0, p, r, c + i);
+      } else if constexpr (LV) {
+        tile::decode_levels8<E>(v, p, r, out);
+      } else {
+        tile::decode_scaled8<E>(v, p.k_decode, out);
+      }
       float* d = lds + lr * PITCH + lu * 8;
       *reinterpret_cast<float4*>(d) = make_float4(out[0], out[1], out[2], out[3]);
       *reinterpret_cast<float4*>(d + 4) = make_float4(out[4], out[5], out[6], out[7]);

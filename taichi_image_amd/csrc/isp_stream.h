@@ -121,9 +121,59 @@ struct WinRow { float v[12]; };
 // table (fill_lut), so a pixel costs what it costs without levels; 2 - one per site: the table is not used, every code
 // is decoded in registers (tile::decode_level: sub, max, cvt, mul, cvt) with the levels of its row parity `lv`
 // (every unit starts at an even column, so the parity of a column is that of its index).
+// Lens shading (Params::shading; LV == 3): the per-site register decode of LV 2 without its rounding, times the gain of
+// the pixel, then the cast.  A lane's columns stay the same for the whole band walk, so their node index
+// and weight are set up once (shade_init); per window row the wave lerps the two grid rows of that row's cell vertically
+// into its own LDS row, one node per lane for both column parities (shade_row; the grid rows themselves stay in VGPRs
+// until the cell row changes), and a pixel pays a ds_read2 (its two nodes), one lerp and one multiply.
+struct Shade {
+  const Params* p;
+  float* tab;                                        // this wave's LDS row: [column parity][node], 2 x 64 f32
+  int gi;                                            // the grid row n0 / n1 hold (-1: none yet; wave-uniform)
+  float n0[4], n1[4];                                // lane j: G_s[gi][j] and G_s[gi + 1][j] of site s
+  int j[10];                                         // node of own[0..7], x0, x1 (the columns of decode_row)
+  float tx[10];
+};
+MI_DEV void shade_init(Shade& sh, const Params& p, float* tab, int c0, int lane) {
+  sh.p = &p; sh.tab = tab; sh.gi = -1;
+  const int cx = lane == 0 ? c0 - 2 : c0 + 8;        // the columns of x0, x1 (lane 0: left of its unit; else right)
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const ShadeAxis a = shade_axis(k < 8 ? c0 + k : cx + k - 8, p.W, p.sh_sx, p.sh_gw);
+    sh.j[k] = a.n; sh.tx[k] = a.t;
+  }
+}
+MI_DEV void shade_row(Shade& sh, int r, int lane) {
+  const Params& p = *sh.p;
+  const ShadeAxis y = shade_axis(r, p.H, p.sh_sy, p.sh_gh);
+  const int i = __builtin_amdgcn_readfirstlane(y.n);
+  if (i != sh.gi) {                                  // a new cell row: the node rows of every site
+    sh.gi = i;
+    const int jj = lane < p.sh_gw ? lane : p.sh_gw - 1;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const float* g = p.sh_gain + ((size_t)(p.sh_sites == 4 ? s : 0) * p.sh_gh + i) * p.sh_gw + jj;
+      sh.n0[s] = g[0]; sh.n1[s] = g[p.sh_gw];
+    }
+  }
+  const bool odd = (r & 1) != 0;                     // (selects: a run-time index would put n0 / n1 in scratch)
+  const float e0 = odd ? sh.n0[2] : sh.n0[0], e1 = odd ? sh.n1[2] : sh.n1[0];
+  const float o0 = odd ? sh.n0[3] : sh.n0[1], o1 = odd ? sh.n1[3] : sh.n1[1];
+  __builtin_amdgcn_wave_barrier();                   // (the previous row's reads of the table come first)
+  sh.tab[lane] = e0 + y.t * (e1 - e0);
+  sh.tab[64 + lane] = o0 + y.t * (o1 - o0);
+  __builtin_amdgcn_wave_barrier();
+}
+// column k (parity PAR) of the row shade_row prepared: cast(x * g, E), widened back
+template <class E, int PAR> MI_DEV float shade_px(const Shade& sh, int k, float x) {
+  const float* t = sh.tab + PAR * 64 + sh.j[k];
+  const float a = t[0], b = t[1];
+  return (float)cast_out<E>(x * (a + sh.tx[k] * (b - a)));
+}
+
 template <class E = float, int LV = 0>
 MI_DEV void decode_row(const uint32_t (&d)[4], const float (&lut)[4096], int lane, WinRow& row,
-                       const tile::RowLevels& lv = {}) {
+                       const tile::RowLevels& lv = {}, Shade* sh = nullptr, int r = 0) {
   uint32_t v[8];
   tile::unpack12x8(d[0], d[1], d[2], false, v);
   // lane 0: the last pixel pair of the unit to the left = the upper 3 bytes of the dword before this unit;
@@ -131,7 +181,15 @@ MI_DEV void decode_row(const uint32_t (&d)[4], const float (&lut)[4096], int lan
   const uint32_t w = lane == 0 ? d[3] >> 8 : d[3] & 0xFFFFFFu;
   float own[8];
   float x0, x1;
-  if constexpr (LV == 2) {
+  if constexpr (LV == 3) {                            // (r: the image row, for the gain)
+    shade_row(*sh, r, lane);
+    static_for<0, 8>([&](auto ic) {
+      constexpr int I = decltype(ic)::value;
+      own[I] = shade_px<E, I & 1>(*sh, I, tile::level_x(v[I], (I & 1) ? lv.b1 : lv.b0, (I & 1) ? lv.k1 : lv.k0));
+    });
+    x0 = shade_px<E, 0>(*sh, 8, tile::level_x(w & 0xFFFu, lv.b0, lv.k0));
+    x1 = shade_px<E, 1>(*sh, 9, tile::level_x(w >> 12, lv.b1, lv.k1));
+  } else if constexpr (LV == 2) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) own[i] = tile::decode_level<E>(v[i], (i & 1) ? lv.b1 : lv.b0, (i & 1) ? lv.k1 : lv.k0);
     x0 = tile::decode_level<E>(w & 0xFFFu, lv.b0, lv.k0);
@@ -553,6 +611,7 @@ MI_DEV void border_fix_rows(float (&v)[24], int rmask, bool is_left, bool is_rig
 #define MI_STAMP_NOW() 0u
 #endif
 
+// LV: sensor levels (decode_row: 1 in the decode table, 2 per site in registers, 3 per site with lens shading)
 template <class E, int PR, int PC, int EPI, int LV = 0>
 __global__ __launch_bounds__(THREADS, 2) void stream_kernel(const SArgs a) {
   static_assert(LV == 0 || EPI == S_STORE, "sensor levels: the load's store pass only");
@@ -566,6 +625,7 @@ __global__ __launch_bounds__(THREADS, 2) void stream_kernel(const SArgs a) {
   __shared__ double sh_tot[7][WAVES];
   __shared__ unsigned arrived;
   __shared__ float lut[4096];                         // the decoded value of every 12-bit code (decode_row)
+  __shared__ float sh_tab[LV == 3 ? WAVES : 1][128];  // lens shading: each wave's interpolated node row (Shade)
   if (threadIdx.x == 0) arrived = 0;
 
   const int lane = threadIdx.x & 63;
@@ -630,9 +690,11 @@ __global__ __launch_bounds__(THREADS, 2) void stream_kernel(const SArgs a) {
   float wq[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) wq[i] = vgpr(wq_value(i));
-  // LV == 2: the levels of even / odd rows (unused otherwise)
-  const tile::RowLevels lv_even = LV == 2 ? tile::row_levels(p, 0) : tile::RowLevels{},
-                        lv_odd = LV == 2 ? tile::row_levels(p, 1) : tile::RowLevels{};
+  // LV >= 2: the levels of even / odd rows (unused otherwise)
+  const tile::RowLevels lv_even = LV >= 2 ? tile::row_levels(p, 0) : tile::RowLevels{},
+                        lv_odd = LV >= 2 ? tile::row_levels(p, 1) : tile::RowLevels{};
+  Shade sh;                                          // LV == 3 only
+  if constexpr (LV == 3) shade_init(sh, p, sh_tab[wave], c0, lane);
   WinRow win[6];                                     // ring: image row (r_begin - 2 + q) lives in slot q % 6
   uint32_t raw[3][2][4];                             // ring: row pair j (rows r_begin + 2 + 2j, + 3 + 2j) in slot j % 3
   {
@@ -651,7 +713,8 @@ __global__ __launch_bounds__(THREADS, 2) void stream_kernel(const SArgs a) {
     if constexpr (EPI == S_RH_MINMAX) pull<ew::FIN_STATS>(a, p.partials + (size_t)ROW_STATS * p.part_stride, sh_fp, sh_tot);
     if constexpr (EPI == S_RH_STORE) pull<ew::FIN_BOUNDS2>(a, p.partials + (size_t)ROW_BOUNDS2 * p.part_stride, sh_fp, sh_tot);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) decode_row<E, LV>(pro[q], lut, lane, win[q], (q & 1) ? lv_odd : lv_even);   // r_begin is even
+    for (int q = 0; q < 4; ++q)                       // r_begin is even
+      decode_row<E, LV>(pro[q], lut, lane, win[q], (q & 1) ? lv_odd : lv_even, &sh, r_begin - 2 + q);
   }
   MI_SSTAMP(2);
 
@@ -692,8 +755,8 @@ __global__ __launch_bounds__(THREADS, 2) void stream_kernel(const SArgs a) {
     constexpr int PH = decltype(ph_c)::value;
     const int r = r_begin + 2 * i;
     // the pair's two new window rows (image rows r + 2, r + 3), loaded three pairs ago
-    decode_row<E, LV>(raw[PH][0], lut, lane, win[(2 * PH + 4) % 6], lv_even);
-    decode_row<E, LV>(raw[PH][1], lut, lane, win[(2 * PH + 5) % 6], lv_odd);
+    decode_row<E, LV>(raw[PH][0], lut, lane, win[(2 * PH + 4) % 6], lv_even, &sh, r + 2);
+    decode_row<E, LV>(raw[PH][1], lut, lane, win[(2 * PH + 5) % 6], lv_odd, &sh, r + 3);
     load_row(r + 8, raw[PH][0]);
     load_row(r + 9, raw[PH][1]);
     if (r >= r_end) return;                           // wave-uniform: a dead pair of the last rotation

@@ -10,7 +10,8 @@ static int launch_e(const SArgs& a, int epi, hipStream_t s) {
   const dim3 grid(a.n_blocks, epi == S_STORE && a.n_batch > 0 ? a.n_batch : 1), block(THREADS);
   if (a.t.levels) {                                // sensor levels (mi_isp_load_packed_levels): the load's store pass only
     if (epi != S_STORE) { mi_set_error("stream: sensor levels take the store pass only"); return 1; }
-    if (a.t.levels == 1) hipLaunchKernelGGL((stream_kernel<E, PAT_PR, PAT_PC, S_STORE, 1>), grid, block, 0, s, a);
+    if (a.t.shading) hipLaunchKernelGGL((stream_kernel<E, PAT_PR, PAT_PC, S_STORE, 3>), grid, block, 0, s, a);
+    else if (a.t.levels == 1) hipLaunchKernelGGL((stream_kernel<E, PAT_PR, PAT_PC, S_STORE, 1>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((stream_kernel<E, PAT_PR, PAT_PC, S_STORE, 2>), grid, block, 0, s, a);
     MI_LAUNCH_CHECK();
     return 0;
@@ -54,8 +55,10 @@ int PAT_SUB_FN(const SubArgs& a, int work_dtype, hipStream_t s) {
 namespace rstrm {
 int PAT_FN(const RSArgs& a, hipStream_t s) {
   const dim3 grid(a.n_blocks, a.n_batch > 0 ? a.n_batch : 1);
-  switch (a.t.levels) {                              // sensor levels: 1 in the decode table, 2 per site in registers
+  // sensor levels: 1 in the decode table, 2 per site in registers; lens shading: 3 (per site, then the gain)
+  switch (a.t.shading ? 3 : a.t.levels) {
     case 0: hipLaunchKernelGGL((resize_kernel<PAT_PR, PAT_PC>), grid, dim3(THREADS), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((resize_kernel<PAT_PR, PAT_PC, 3>), grid, dim3(THREADS), 0, s, a); break;
     case 1: hipLaunchKernelGGL((resize_kernel<PAT_PR, PAT_PC, 1>), grid, dim3(THREADS), 0, s, a); break;
     default: hipLaunchKernelGGL((resize_kernel<PAT_PR, PAT_PC, 2>), grid, dim3(THREADS), 0, s, a); break;
   }

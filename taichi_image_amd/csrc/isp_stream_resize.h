@@ -61,13 +61,14 @@ MI_DEV int first_with_origin(int x, float s, int n_src, int n_dst) {
   return c < n_dst ? c : n_dst;
 }
 
-// LV: sensor levels (tile::Params::levels; strm::decode_row)
+// LV: sensor levels (tile::Params::levels; strm::decode_row), 3: per site with lens shading (strm::Shade)
 template <int PR, int PC, int LV = 0>
 __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
   typedef half_t E;
   const Params& p = a.t;
   __shared__ __attribute__((aligned(16))) uint4 ring_all[WAVES][RING][ROW_BYTES / 16];
   __shared__ float lut[4096];
+  __shared__ float sh_tab[LV == 3 ? WAVES : 1][128];  // lens shading: each wave's interpolated node row (strm::Shade)
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -101,14 +102,24 @@ __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
   };
   // the lane right of the band's last lane is inactive and decodes zeros - but the band's last lane needs the REAL two
   // pixels to its right: it takes them from its edge dword like lane 63 does (decode_row_edge below)
-  // (LV == 2: `lv` the levels of the row's parity; r_begin is even, so window slot q has the parity of q)
-  auto decode = [&](const uint32_t (&d)[4], WinRow& row, const tile::RowLevels& lv) {
+  // (LV >= 2: `lv` the levels of the row's parity; r_begin is even, so window slot q has the parity of q;
+  // LV == 3: `r` the image row, for the lens shading gain)
+  Shade sh;
+  auto decode = [&](const uint32_t (&d)[4], WinRow& row, const tile::RowLevels& lv, int r) {
     uint32_t v[8];
     tile::unpack12x8(d[0], d[1], d[2], false, v);
     const uint32_t w = lane == 0 ? d[3] >> 8 : d[3] & 0xFFFFFFu;
     float own[8];
     float x0, x1;
-    if constexpr (LV == 2) {
+    if constexpr (LV == 3) {
+      shade_row(sh, r, lane);
+      static_for<0, 8>([&](auto ic) {
+        constexpr int I = decltype(ic)::value;
+        own[I] = shade_px<E, I & 1>(sh, I, tile::level_x(v[I], (I & 1) ? lv.b1 : lv.b0, (I & 1) ? lv.k1 : lv.k0));
+      });
+      x0 = shade_px<E, 0>(sh, 8, tile::level_x(w & 0xFFFu, lv.b0, lv.k0));
+      x1 = shade_px<E, 1>(sh, 9, tile::level_x(w >> 12, lv.b1, lv.k1));
+    } else if constexpr (LV == 2) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) own[i] = tile::decode_level<E>(v[i], (i & 1) ? lv.b1 : lv.b0, (i & 1) ? lv.k1 : lv.k0);
       x0 = tile::decode_level<E>(w & 0xFFFu, lv.b0, lv.k0);
@@ -176,8 +187,9 @@ __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
   float wq[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) wq[i] = vgpr(wq_value(i));
-  const tile::RowLevels lv_even = LV == 2 ? tile::row_levels(p, 0) : tile::RowLevels{},
-                        lv_odd = LV == 2 ? tile::row_levels(p, 1) : tile::RowLevels{};
+  const tile::RowLevels lv_even = LV >= 2 ? tile::row_levels(p, 0) : tile::RowLevels{},
+                        lv_odd = LV >= 2 ? tile::row_levels(p, 1) : tile::RowLevels{};
+  if constexpr (LV == 3) shade_init(sh, p, sh_tab[wave], c0, lane);
   WinRow win[6];
   uint32_t raw[3][2][4];
   {
@@ -192,7 +204,7 @@ __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
     strm::fill_lut<E, LV>(lut, p);
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < 4; ++q) decode(pro[q], win[q], (q & 1) ? lv_odd : lv_even);
+    for (int q = 0; q < 4; ++q) decode(pro[q], win[q], (q & 1) ? lv_odd : lv_even, r_begin - 2 + q);
   }
   MI_SSTAMP(1);
   const bool is_left = col_ok && c0 == 0, is_right = col_ok && c0 + 8 == p.W;
@@ -284,8 +296,8 @@ __global__ __launch_bounds__(THREADS, 2) void resize_kernel(const RSArgs a) {
   auto body = [&](auto ph_c, int i) {
     constexpr int PH = decltype(ph_c)::value;
     const int r = r_begin + 2 * i;
-    decode(raw[PH][0], win[(2 * PH + 4) % 6], lv_even);
-    decode(raw[PH][1], win[(2 * PH + 5) % 6], lv_odd);
+    decode(raw[PH][0], win[(2 * PH + 4) % 6], lv_even, r + 2);
+    decode(raw[PH][1], win[(2 * PH + 5) % 6], lv_odd, r + 3);
     load_row(r + 8, raw[PH][0]);
     load_row(r + 9, raw[PH][1]);
     if (r > r_last) return;                            // wave-uniform

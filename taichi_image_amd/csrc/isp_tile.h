@@ -99,6 +99,14 @@ struct Params {
   int levels;
   int lv_black[4];
   float lv_k[4];
+  // lens shading (mi_isp_shading): 0 none, 1 a gain grid is set.  Shading always decodes through the per-site
+  // levels (levels 2 arithmetic; with no levels set lv_black = 0 and lv_k = k_decode, which is the plain decode), then
+  // multiplies the f32 value by the gain interpolated from sh_gain (sh_sites x sh_gh x sh_gw f32 on the device) before the
+  // cast.  sh_sy / sh_sx: f32((sh_gh - 1) / (H - 1)), f32((sh_gw - 1) / (W - 1)), computed in double on the host.
+  int shading;
+  const float* sh_gain;
+  int sh_sites, sh_gh, sh_gw;
+  float sh_sy, sh_sx;
 };
 
 // the distinct weight values of KW and their slot in Params::wq
@@ -212,6 +220,17 @@ MI_DEV RowLevels row_levels(const Params& p, int r) {
   return {odd ? p.lv_black[2] : p.lv_black[0], odd ? p.lv_black[3] : p.lv_black[1],
           odd ? p.lv_k[2] : p.lv_k[0], odd ? p.lv_k[3] : p.lv_k[1]};
 }
+// Lens shading: the f32 value a code has before the cast (levels arithmetic, decode_level without its rounding) ...
+MI_DEV float level_x(uint32_t v, int b, float k) {
+  const int d = (int)v - b;
+  return (float)(d > 0 ? d : 0) * k;
+}
+// ... times the gain of the pixel (shade_gain, isp_common.h)
+// the shaded decode of code v at raw pixel (r, c) with levels (b, k), rounded to E and widened back
+template <class E> MI_DEV float decode_shaded(uint32_t v, int b, float k, const Params& p, int r, int c) {
+  return (float)cast_out<E>(level_x(v, b, k) * shade_gain(p, r, c));
+}
+
 template <class E> MI_DEV void decode_levels8(const uint32_t (&v)[8], const Params& p, int r, float (&out)[8]) {
   const RowLevels l = row_levels(p, r);
   const int b0 = l.b0, b1 = l.b1;
@@ -250,7 +269,8 @@ MI_DEV void lds_store8(float* row, int lu, const float (&v)[8]) {
 // Out-of-image elements are zero (they contribute 0*w, an exact no-op, to the accumulators).
 // ---------------------------------------------------------------------------------------------
 // General packed path: any width / alignment, byte loads.
-template <class E, bool LV = false>
+// SH: lens shading (Params::shading; with LV)
+template <class E, bool LV = false, bool SH = false>
 MI_DEV void fill_packed(const Params& p, float* lds, int rb, int cb) {
   const uint8_t* base = static_cast<const uint8_t*>(p.src);
   const bool is16 = p.src_kind == SRC_PACKED16;
@@ -271,7 +291,11 @@ MI_DEV void fill_packed(const Params& p, float* lds, int rb, int cb) {
           const uint32_t w = q[3 * j] | (q[3 * j + 1] << 8) | (q[3 * j + 2] << 16);
           unpack_pair(w, ids, a, b);
         }
-        if constexpr (LV) {
+        if constexpr (SH) {
+          const RowLevels l = row_levels(p, r);
+          dst[lds_pos(lu * 8 + 2 * j)] = decode_shaded<E>(a, l.b0, l.k0, p, r, c + 2 * j);
+          dst[lds_pos(lu * 8 + 2 * j + 1)] = decode_shaded<E>(b, l.b1, l.k1, p, r, c + 2 * j + 1);
+        } else if constexpr (LV) {
           const RowLevels l = row_levels(p, r);
           dst[lds_pos(lu * 8 + 2 * j)] = decode_level<E>(a, l.b0, l.k0);
           dst[lds_pos(lu * 8 + 2 * j + 1)] = decode_level<E>(b, l.b1, l.k1);
@@ -285,7 +309,11 @@ MI_DEV void fill_packed(const Params& p, float* lds, int rb, int cb) {
       for (int j = 0; j < 8; ++j) {
         uint32_t a = 0;
         if (j < n) a = q[2 * j] | (q[2 * j + 1] << 8);
-        if constexpr (LV) {
+        if constexpr (SH) {
+          const RowLevels l = row_levels(p, r);
+          dst[lds_pos(lu * 8 + j)] = (j & 1) ? decode_shaded<E>(a, l.b1, l.k1, p, r, c + j)
+                                             : decode_shaded<E>(a, l.b0, l.k0, p, r, c + j);
+        } else if constexpr (LV) {
           const RowLevels l = row_levels(p, r);
           dst[lds_pos(lu * 8 + j)] = (j & 1) ? decode_level<E>(a, l.b1, l.k1) : decode_level<E>(a, l.b0, l.k0);
         } else {
@@ -300,7 +328,7 @@ MI_DEV void fill_packed(const Params& p, float* lds, int rb, int cb) {
 // outside.  All global loads of a lane (up to 3 units = 36/48 bytes) are issued before the first
 // use, so one memory latency is paid per tile instead of one per unit; an all-zero unit decodes to
 // zeros, so out-of-image units need no branch after the load.
-template <class E, bool LV = false>
+template <class E, bool LV = false, bool SH = false>
 MI_DEV void fill_packed_fast(const Params& p, float* lds, int rb, int cb) {
   constexpr int NUNITS = LDS_ROWS * UNITS;
   constexpr int NIT = (NUNITS + THREADS - 1) / THREADS;
@@ -312,6 +340,7 @@ MI_DEV void fill_packed_fast(const Params& p, float* lds, int rb, int cb) {
   uint4 raw[NIT];
   int off[NIT];
   int row[NIT];                                      // (LV only) the image row of the unit
+  int col[NIT];                                      // (SH only) its first image column
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int u = threadIdx.x + it * THREADS;
@@ -320,6 +349,7 @@ MI_DEV void fill_packed_fast(const Params& p, float* lds, int rb, int cb) {
     const int r = rb + lr, c = cb + lu * 8;
     off[it] = u < NUNITS ? lr * PITCH + lu * 4 : -1;
     row[it] = r;
+    col[it] = c;
     raw[it] = make_uint4(0, 0, 0, 0);
     if (u < NUNITS && r >= 0 && r < p.H && c >= 0 && c < p.W) {
       const uint8_t* rowp = base + (size_t)r * pitch;
@@ -343,8 +373,16 @@ MI_DEV void fill_packed_fast(const Params& p, float* lds, int rb, int cb) {
       v[4] = d.z & 0xFFFFu; v[5] = d.z >> 16; v[6] = d.w & 0xFFFFu; v[7] = d.w >> 16;
     }
     float out[8];
-    if constexpr (LV) decode_levels8<E>(v, p, row[it], out);
-    else decode_scaled8<E>(v, p.k_decode, out);
+    if constexpr (SH) {
+      const RowLevels l = row_levels(p, row[it]);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        out[i] = decode_shaded<E>(v[i], (i & 1) ? l.b1 : l.b0, (i & 1) ? l.k1 : l.k0, p, row[it], col[it] + i);
+    } else if constexpr (LV) {
+      decode_levels8<E>(v, p, row[it], out);
+    } else {
+      decode_scaled8<E>(v, p.k_decode, out);
+    }
     lds_store8(lds + off[it], 0, out);
   }
 }
@@ -405,7 +443,7 @@ MI_DEV void fill_plain(const Params& p, float* lds, int rb, int cb) {
   }
 }
 
-template <class E, bool LV = false>
+template <class E, bool LV = false, bool SH = false>
 MI_DEV void fill_tile(const Params& p, float* lds, int rb, int cb) {
   switch (p.src_kind) {
     case SRC_CFA_U8: fill_plain<uint8_t>(p, lds, rb, cb); break;
@@ -413,8 +451,8 @@ MI_DEV void fill_tile(const Params& p, float* lds, int rb, int cb) {
     case SRC_CFA_F16: fill_plain<half_t>(p, lds, rb, cb); break;
     case SRC_CFA_F32: fill_plain<float>(p, lds, rb, cb); break;
     default:
-      if (p.src_fast) fill_packed_fast<E, LV>(p, lds, rb, cb);
-      else fill_packed<E, LV>(p, lds, rb, cb);
+      if (p.src_fast) fill_packed_fast<E, LV, SH>(p, lds, rb, cb);
+      else fill_packed<E, LV, SH>(p, lds, rb, cb);
       break;
   }
 }
@@ -617,8 +655,9 @@ MI_DEV void store_row_dyn(const Params& p, int r, int c, const float (&v)[24], i
 #define MI_STAMP(i) do {} while (0)
 #endif
 template <class E> constexpr int dtype_code() { return sizeof(E) == 2 ? (int)MI_F16 : (int)MI_F32; }
-// LV: the packed source carries sensor levels (Params::levels != 0; HOT == 0 only)
-template <class E, int PR, int PC, int EPI, int HOT = 0, bool LV = false>
+// LV: the packed source carries sensor levels (Params::levels != 0; HOT == 0 only); SH: and a lens shading grid
+// (Params::shading; with LV)
+template <class E, int PR, int PC, int EPI, int HOT = 0, bool LV = false, bool SH = false>
 __global__ __launch_bounds__(THREADS) void tile_kernel(const Params p_in) {
   constexpr bool EXACT = sizeof(E) == 2;
   Params p = p_in;
@@ -657,7 +696,7 @@ __global__ __launch_bounds__(THREADS) void tile_kernel(const Params p_in) {
   MI_STAMP(0);
   if constexpr (HOT == 1) fill_packed_fast<E>(p, lds, r0 - 2, c0 - 8);
   else if constexpr (HOT >= 2) fill_cfa_fast<CfaT>(p, lds, r0 - 2, c0 - 8);
-  else if (!(MI_DEBUG_SKIP(p) & 1)) fill_tile<E, LV>(p, lds, r0 - 2, c0 - 8);
+  else if (!(MI_DEBUG_SKIP(p) & 1)) fill_tile<E, LV, SH>(p, lds, r0 - 2, c0 - 8);
   MI_STAMP(1);
   __syncthreads();
   MI_STAMP(2);

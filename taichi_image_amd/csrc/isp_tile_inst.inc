@@ -10,7 +10,8 @@ static int launch_e(const Params& p, int epi, hipStream_t s) {
   const dim3 grid(num_tiles(p.H, p.W)), block(THREADS);
   if (p.levels) {                  // a packed source with sensor levels (mi_isp_load_packed_levels): the general fill
     if (epi != EPI_STORE) { mi_set_error("tile: sensor levels take the store epilogue only"); return 1; }
-    hipLaunchKernelGGL((tile_kernel<E, PAT_PR, PAT_PC, EPI_STORE, 0, true>), grid, block, 0, s, p);
+    if (p.shading) hipLaunchKernelGGL((tile_kernel<E, PAT_PR, PAT_PC, EPI_STORE, 0, true, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((tile_kernel<E, PAT_PR, PAT_PC, EPI_STORE, 0, true>), grid, block, 0, s, p);
     MI_LAUNCH_CHECK();
     return 0;
   }
@@ -70,7 +71,10 @@ int PAT_FN(const Params& p, int work_dtype, int epi, hipStream_t s) {
 namespace rtile {
 int PAT_FN(const RParams& p, int work_dtype, hipStream_t s) {
   const dim3 grid(num_tiles(p.Hd, p.Wd)), block(THREADS);
-  if (p.t.levels) {
+  if (p.t.shading) {                 // lens shading (with the per-site levels decode): the general fill
+    if (work_dtype == MI_F16) hipLaunchKernelGGL((resize_tile_kernel<half_t, PAT_PR, PAT_PC, false, true, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((resize_tile_kernel<float, PAT_PR, PAT_PC, false, true, true>), grid, block, 0, s, p);
+  } else if (p.t.levels) {
     if (work_dtype == MI_F16) hipLaunchKernelGGL((resize_tile_kernel<half_t, PAT_PR, PAT_PC, false, true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((resize_tile_kernel<float, PAT_PR, PAT_PC, false, true>), grid, block, 0, s, p);
   } else if (hot_ok(p)) {

@@ -126,6 +126,9 @@ def build_parser() -> argparse.ArgumentParser:
     # level (default: 4095, the packed-12 full scale)
     tone.add_argument("--black-level", dest="black_level", type=int, nargs="+", default=None)
     tone.add_argument("--white-level", dest="white_level", type=int, default=None)
+    # lens shading (an extension): a (Gh, Gw) or (4, Gh, Gw) f32 gain grid saved with numpy.save
+    # (camera_isp.lens_shading_from_flat makes one from a flat-field capture)
+    tone.add_argument("--lens-shading", dest="lens_shading", type=Path, default=None)
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -144,12 +147,16 @@ def main(argv=None) -> int:
         raise ValueError(f"--black-level takes one value or four (one per CFA site), got {len(black)}")
     black = black[0] if black is not None and len(black) == 1 else black
     camera_isp._check_levels(black, args.white_level, 12)          # before any frame is read
+    shading = None
+    if args.lens_shading is not None:
+        shading = np.load(args.lens_shading, allow_pickle=False)
+        camera_isp._check_shading(shading)                          # (also before any frame is read)
     index = ScanIndex.of_scan(args.scan) if args.scan is not None else ScanIndex.of_directory(args.images)
     print(f"{len(index.cameras)} camera(s) {[c.name for c in index.cameras]}, {len(index.frames)} frame(s) each")
     device = torch.device(args.device)
     isp = camera_isp.Camera32(bayer.BayerPattern.RGGB, transform=args.transform, moving_alpha=args.moving_alpha,
                               resize_width=args.resize_width, correct_colors=args.correct_colors, device=device,
-                              black_level=black, white_level=args.white_level)
+                              black_level=black, white_level=args.white_level, lens_shading=shading)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
