@@ -83,12 +83,12 @@ def raw_x(codes, bits, black, white):
     return np.maximum(codes.astype(np.int64) - b, 0).astype(f32) * np.tile(k, (H // 2, W // 2))
 
 
-def ref_load(raw, bits, work, pattern, grid, black=None, white=None, resize_width=0, ids_format=False):
+def ref_load(raw, bits, work, pattern, grid, black=None, white=None, resize_width=0, ids_format=False, ccm=None):
     codes = O.decode12(raw, "u16", ids_format=ids_format) if bits == 12 else O.decode16(raw, "u16")
     x = raw_x(codes, bits, black, white)
     if grid is not None:
         x = x * pixel_gains(grid, *codes.shape)
-    rgb = O.bayer_to_rgb(O.cast_out(x, work), pattern)
+    rgb = O.bayer_to_rgb(O.cast_out(x, work), pattern, correct_colors=ccm)
     sz = O.isp_output_size(rgb.shape[0], rgb.shape[1], resize_width, None)
     return rgb if sz is None else O.resize_bilinear(rgb, sz[0], sz[1])
 
