@@ -391,7 +391,7 @@ int mi_isp_whole_frame_set_poll_limit(unsigned polls);
  * per remaining barrier; mi_isp_workspace_check also wipes the barrier records of the frames it reports.
  * mi_isp_whole_frame_set_sabotage(block): test hook - that block of every later launch does not post its record at the
  *   first barrier of the launch's first frame (what a block that is not resident looks like to the others); -1 = off.
- * The resident-grid kernels of the library (this one, the one-launch metering, the fused ISP tonemap) are launched in
+ * The resident-grid kernels of the library (this one, the one-launch metering, the camera group) are launched in
  * ONE order per device and process: a launch on another stream than the previous one waits for an event recorded behind
  * that one. */
 int mi_isp_whole_frame_set_sabotage(int block);
@@ -401,17 +401,6 @@ int mi_isp_whole_frame_set_sabotage(int block);
  * mi_isp_metering_set_poll_limit(polls): poll budget of the following launches (0 = default, ~1 s; tests use 1). */
 int mi_isp_metering_faults(int clear);
 int mi_isp_metering_set_poll_limit(unsigned polls);
-/* Experimental (off by default; MI_ISP_REINHARD_LAUNCHES=1 in the environment enables it): mi_isp_reinhard_batch
- * (reinhard_kernel of camera_isp.py:177-218 for a list of images) as ONE persistent launch when no orientation transform
- * is asked for, the buffers are 16-byte aligned, H * W is a multiple of 512 and an image's mapped values fit the chip's
- * registers (up to 3.1 MP per image pipelined, 6.3 MP one at a time): p is written in place as the reference does
- * (camera_isp.py:211) and kept on chip for the second pass.  Same results as the two launches, bit for bit; measured
- * slower than them, hence off.
- * Its one grid-wide wait (max_out, camera_isp.py:213) can time out like the others: fault word of the workspace +
- * mi_isp_reinhard_faults(clear), the device's mailbox word of this kernel (a plain host read); the outputs of that call
- * are then invalid.  mi_isp_reinhard_set_poll_limit(polls): poll budget of the following launches (0 = default). */
-int mi_isp_reinhard_faults(int clear);
-int mi_isp_reinhard_set_poll_limit(unsigned polls);
 
 /* The same for n_frames independent frames, frame i on streams_host[i % n_streams]
  * (one frame per stream in flight); ws_dev holds n_frames consecutive workspaces;

@@ -155,8 +155,20 @@ class MeteringTimeout(RuntimeError):
 
 
 class TonemapTimeout(RuntimeError):
-    """The grid-wide wait of an earlier one-launch tonemap_reinhard on this device (max_out, camera_isp.py:213) timed out:
+    """The grid-wide wait of an earlier one-launch process_packed12 on this device (max_out, camera_isp.py:213) timed out:
     the u8 outputs of that call are invalid.  Raised by the next metering / tonemap call (a host read of the mailbox)."""
+
+
+def _raise_resident_faults(L, device):
+    """MeteringTimeout / TonemapTimeout for a timeout an earlier resident-grid launch on `device` left in its mailbox word
+    (a host read each, no synchronisation; the words are cleared)."""
+    with torch.cuda.device(device):
+        if L.mi_isp_metering_faults(1):
+            raise MeteringTimeout("an earlier update_metering on this device timed out at its grid barrier: its "
+                                  "metrics were left unchanged and outputs tone-mapped with them are invalid")
+        if L.mi_isp_camera_group_faults(1):
+            raise TonemapTimeout("an earlier process_packed12 on this device timed out waiting for an image's "
+                                 "max_out: the outputs of that call are invalid")
 
 
 def _version_of(t):
@@ -584,16 +596,7 @@ def camera_isp(name: str, dtype=types.f32):
             ptrs = _native.ptr_array(images)
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
-            with torch.cuda.device(self.device):
-                if L.mi_isp_metering_faults(1):
-                    raise MeteringTimeout("an earlier update_metering on this device timed out at its grid barrier: its "
-                                          "metrics were left unchanged and outputs tone-mapped with them are invalid")
-                if L.mi_isp_reinhard_faults(1):
-                    raise TonemapTimeout("an earlier tonemap_reinhard on this device timed out waiting for an image's "
-                                         "max_out: the outputs of that call are invalid")
-                if L.mi_isp_camera_group_faults(1):
-                    raise TonemapTimeout("an earlier process_packed12 on this device timed out waiting for an image's "
-                                         "max_out: the outputs of that call are invalid")
+            _raise_resident_faults(L, self.device)
             if self.process_group is None:
                 # (the reference clones `prev` and lets the kernel update the clone, camera_isp.py:172-173; here the kernel
                 # reads `prev` and writes the new tensor: no copy kernel - 4 us - in front of every update)
@@ -737,13 +740,7 @@ def camera_isp(name: str, dtype=types.f32):
                 images = self.load_packed12_batch(frames, ids_format)
                 outputs = self.tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt)
                 return (outputs, images) if keep_images else outputs
-            with torch.cuda.device(self.device):
-                if L.mi_isp_metering_faults(1):
-                    raise MeteringTimeout("an earlier update_metering on this device timed out at its grid barrier: its "
-                                          "metrics were left unchanged and outputs tone-mapped with them are invalid")
-                if L.mi_isp_camera_group_faults(1):
-                    raise TonemapTimeout("an earlier process_packed12 on this device timed out waiting for an image's "
-                                         "max_out: the outputs of that call are invalid")
+            _raise_resident_faults(L, self.device)
             n = len(srcs)
             outputs = [torch.empty((h, w, 3), dtype=torch.uint8, device=self.device) for _ in srcs]
             images = [torch.empty((h, w, 3), dtype=torch_dtype, device=self.device) for _ in srcs] if keep_images else None

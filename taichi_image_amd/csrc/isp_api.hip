@@ -22,7 +22,7 @@ void mi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int mi_isp_version(void) { return 1200; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
+extern "C" int mi_isp_version(void) { return 1300; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
 extern "C" const char* mi_isp_last_error(void) { return g_err; }
 
 extern "C" int mi_isp_bayer_weights(int32_t out[4 * 13 * 3]) {
@@ -507,11 +507,9 @@ static int pipeline_frame_cached(tile::Params p, int pattern, int work_dtype, fl
 // direct launches on other streams.  Other PROCESSES on the same GPU are invisible to all of this: a foreign kernel that
 // holds CUs makes the barrier time out - which is what the fault word, the mailbox and the multi-pass fallback are for.
 // Round 4: the order, its lock, the event and the mailbox page are those of ALL resident-grid kernels of the library
-// (ew::resident_order, isp_elementwise.h) - the one-launch metering kernel takes part in the same order.
+// (ew::resident_launch, isp_elementwise.h) - the one-launch metering and the camera-group kernel take part in the same order.
 static struct {
-  int n_cus[16] = {};
   int per_cu[4] = {-1, -1, -1, -1};          // per CFA pattern: the allocator's outcome differs per instantiation
-  unsigned poll_limit = 0;                   // 0 = default
   int sabotage_block = -1;                   // tests: this block never posts at barrier 0 of a launch's first frame
   std::atomic<uint32_t> launches{0};         // the host's part of a launch's tag (isp_mega.h)
 } g_mega;
@@ -525,13 +523,9 @@ static bool mega_fits(const tile::Params& p, int work_dtype, const void* out, in
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
   std::lock_guard<std::mutex> lock(mega_mu());
   if (g_mega.per_cu[pattern] < 0) g_mega.per_cu[pattern] = mega::blocks_per_cu(pattern);
-  if (g_mega.n_cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-    g_mega.n_cus[dev] = n;
-  }
+  const int n_cus = ew::device_cus(dev);
   // fewer than two resident blocks per CU (a spilling or fatter instantiation) would deadlock the barrier: refuse
-  return g_mega.per_cu[pattern] >= 2 && mega::geometry(p.H, p.W, g_mega.n_cus[dev], a);
+  return n_cus > 0 && g_mega.per_cu[pattern] >= 2 && mega::geometry(p.H, p.W, n_cus, a);
 }
 
 // One launch for frames [0, n): same geometry and parameters, frame i reads srcs[i], writes dsts[i] and owns the workspace
@@ -545,44 +539,39 @@ static int mega_launch_frames(tile::Params p, strm::SArgs a, int pattern, float 
   int dev = 0;
   MI_HIP(hipGetDevice(&dev));
   MI_REQUIRE(dev >= 0 && dev < 16, "whole-frame kernel: device index %d out of range", dev);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &cap);
-  std::lock_guard<std::mutex> lock(mega_mu());
-  ew::ResidentOrder& ord = ew::resident_order();
-  if (int rc = ew::resident_mailbox_locked(dev)) return rc;
-  mega::MBatch mb = {};
-  mb.m.s = a;
-  mb.m.spin_limit = g_mega.poll_limit ? g_mega.poll_limit : 100000;   // ~100 ms of polling before a wave gives up
-  mb.m.l2_first = 1;
-  mb.m.poll_sleep = 0;                                       // extra 512-cycle naps between two polls (swept: 0 is best)
-  mb.m.mailbox = ord.mailbox_dev[dev] + ew::MAILBOX_WHOLE_FRAME;
-  mb.m.sabotage_block = g_mega.sabotage_block;
+  return ew::resident_launch(dev, s, ew::MAILBOX_WHOLE_FRAME, ew::CAPTURED_UNORDERED,
+                             [&](unsigned* mailbox, unsigned limit, bool direct) {
+    mega::MBatch mb = {};
+    mb.m.s = a;
+    mb.m.spin_limit = limit ? limit : 100000;                  // ~100 ms of polling before a wave gives up
+    mb.m.l2_first = 1;
+    mb.m.poll_sleep = 0;                                       // extra 512-cycle naps between two polls (swept: 0 is best)
+    mb.m.mailbox = mailbox;
+    mb.m.sabotage_block = g_mega.sabotage_block;
 #ifdef MI_ISP_MEASURE
-  if (getenv("MI_ISP_POLL_SLEEP")) mb.m.poll_sleep = (unsigned)atoi(getenv("MI_ISP_POLL_SLEEP"));
-  if (getenv("MI_ISP_L2_FIRST")) mb.m.l2_first = (unsigned)atoi(getenv("MI_ISP_L2_FIRST"));
+    if (getenv("MI_ISP_POLL_SLEEP")) mb.m.poll_sleep = (unsigned)atoi(getenv("MI_ISP_POLL_SLEEP"));
+    if (getenv("MI_ISP_L2_FIRST")) mb.m.l2_first = (unsigned)atoi(getenv("MI_ISP_L2_FIRST"));
 #endif
-  const bool direct = cap == hipStreamCaptureStatusNone;
-  if (direct) { if (int rc = ew::resident_enter_locked(dev, s)) return rc; }
-  const PassTimer tm0 = direct ? pass_timer(s, 1) : PassTimer{0, false, s};   // measurement aid: a launch as "pass 0"
-  for (int i0 = 0; i0 < n; i0 += mega::MAX_BATCH) {
-    mb.n_frames = n - i0 < mega::MAX_BATCH ? n - i0 : mega::MAX_BATCH;
-    // the host's part of the launch's tag: a block of an EARLIER launch that comes to life late (a foreign kernel held its
-    // CU) must not post records a later launch takes for its own (the workspace's own count covers graph replays, whose
-    // arguments are frozen)
-    mb.m.launch_id = g_mega.launches.fetch_add(1, std::memory_order_relaxed) + 1u;
-    for (int i = 0; i < mb.n_frames; ++i) {
-      mb.io[i].src = srcs[i0 + i];
-      mb.io[i].dst = dsts[i0 + i];
-      mb.io[i].ws = ws + (size_t)(i0 + i) * ws_floats;
+    const PassTimer tm0 = direct ? pass_timer(s, 1) : PassTimer{0, false, s};   // measurement aid: a launch as "pass 0"
+    for (int i0 = 0; i0 < n; i0 += mega::MAX_BATCH) {
+      mb.n_frames = n - i0 < mega::MAX_BATCH ? n - i0 : mega::MAX_BATCH;
+      // the host's part of the launch's tag: a block of an EARLIER launch that comes to life late (a foreign kernel held
+      // its CU) must not post records a later launch takes for its own (the workspace's own count covers graph replays,
+      // whose arguments are frozen)
+      mb.m.launch_id = g_mega.launches.fetch_add(1, std::memory_order_relaxed) + 1u;
+      for (int i = 0; i < mb.n_frames; ++i) {
+        mb.io[i].src = srcs[i0 + i];
+        mb.io[i].dst = dsts[i0 + i];
+        mb.io[i].ws = ws + (size_t)(i0 + i) * ws_floats;
+      }
+      // (events around the first launch of the call only: a call of more than 64 frames is several launches)
+      const PassTimer tm = i0 == 0 ? tm0 : PassTimer{0, false, s};
+      if (int rc = tm.begin(0)) return rc;
+      if (int rc = mega::launch(mb, pattern, s)) return rc;
+      if (int rc = tm.end(0)) return rc;
     }
-    // (events around the first launch of the call only: a call of more than 64 frames is several launches)
-    const PassTimer tm = i0 == 0 ? tm0 : PassTimer{0, false, s};
-    if (int rc = tm.begin(0)) return rc;
-    if (int rc = mega::launch(mb, pattern, s)) return rc;
-    if (int rc = tm.end(0)) return rc;
-  }
-  if (direct) { if (int rc = ew::resident_leave_locked(dev, s)) return rc; }
-  return 0;
+    return 0;
+  });
 }
 
 extern "C" size_t mi_isp_workspace_error_offset(int H, int W) {
@@ -590,11 +579,7 @@ extern "C" size_t mi_isp_workspace_error_offset(int H, int W) {
   return (size_t)mega::FP_ERROR * sizeof(float);
 }
 
-extern "C" int mi_isp_whole_frame_set_poll_limit(unsigned polls) {
-  std::lock_guard<std::mutex> lock(mega_mu());
-  g_mega.poll_limit = polls;
-  return 0;
-}
+extern "C" int mi_isp_whole_frame_set_poll_limit(unsigned polls) { return ew::set_poll_limit(ew::MAILBOX_WHOLE_FRAME, polls); }
 
 // Test hook: block `block` of every later whole-frame launch does not post its record at barrier 0 of the launch's first
 // frame (-1: off) - the one fault a test can provoke that looks like a block which is not resident: everybody else waits
@@ -605,17 +590,7 @@ extern "C" int mi_isp_whole_frame_set_sabotage(int block) {
   return 0;
 }
 
-extern "C" int mi_isp_whole_frame_faults(int clear) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
-  std::lock_guard<std::mutex> lock(mega_mu());
-  ew::ResidentOrder& ord = ew::resident_order();
-  if (!ord.mailbox_host[dev]) return 0;
-  volatile unsigned* mb = ord.mailbox_host[dev] + ew::MAILBOX_WHOLE_FRAME;
-  const unsigned v = *mb;
-  if (clear) *mb = 0;
-  return (int)v;
-}
+extern "C" int mi_isp_whole_frame_faults(int clear) { return ew::faults(ew::MAILBOX_WHOLE_FRAME, clear); }
 
 extern "C" int mi_isp_workspace_check(void* ws_dev, int n_frames, int H, int W, int* failed_host, int* n_failed,
                                       void* stream) {
@@ -868,7 +843,6 @@ extern "C" int mi_isp_camera_frame_batch(const uint8_t* const* packed, void* con
 // resident on the chip.  images == NULL: p is not stored (the bench drops it); else images[i] receives what the reference
 // leaves in the loaded image (camera_isp.py:211).
 static int g_cam_per_cu[3][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}};   // [levels][pattern]
-static unsigned g_cam_poll_limit = 0;
 
 // lv: the levels instantiation (tile::Params::levels) whose occupancy counts
 static bool camera_group_fits(int H, int W, int pattern, strm::SArgs& a, int lv = 0) {
@@ -881,12 +855,8 @@ static bool camera_group_fits(int H, int W, int pattern, strm::SArgs& a, int lv 
   std::lock_guard<std::mutex> lock(mega_mu());
   if (lv < 0 || lv > 2) return false;
   if (g_cam_per_cu[lv][pattern] < 0) g_cam_per_cu[lv][pattern] = mega::cam_blocks_per_cu(pattern, lv);
-  if (g_mega.n_cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-    g_mega.n_cus[dev] = n;
-  }
-  return g_cam_per_cu[lv][pattern] >= 2 && mega::geometry(H, W, g_mega.n_cus[dev], a);
+  const int n_cus = ew::device_cus(dev);
+  return n_cus > 0 && g_cam_per_cu[lv][pattern] >= 2 && mega::geometry(H, W, n_cus, a);
 }
 
 // the instantiation a call with these levels takes (0 without), or -1 for levels apply_levels refuses
@@ -913,23 +883,9 @@ extern "C" size_t mi_isp_camera_group_scratch_bytes(int n, int H, int W) {
   return (size_t)n * ((per + 255) / 256 * 256);
 }
 
-extern "C" int mi_isp_camera_group_set_poll_limit(unsigned polls) {
-  std::lock_guard<std::mutex> lock(mega_mu());
-  g_cam_poll_limit = polls;
-  return 0;
-}
+extern "C" int mi_isp_camera_group_set_poll_limit(unsigned polls) { return ew::set_poll_limit(ew::MAILBOX_CAMERA_GROUP, polls); }
 
-extern "C" int mi_isp_camera_group_faults(int clear) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
-  std::lock_guard<std::mutex> lock(mega_mu());
-  ew::ResidentOrder& ord = ew::resident_order();
-  if (!ord.mailbox_host[dev]) return 0;
-  volatile unsigned* mb = ord.mailbox_host[dev] + ew::MAILBOX_CAMERA_GROUP;
-  const unsigned v = *mb;
-  if (clear) *mb = 0;
-  return (int)v;
-}
+extern "C" int mi_isp_camera_group_faults(int clear) { return ew::faults(ew::MAILBOX_CAMERA_GROUP, clear); }
 
 // the frames' common parameters, checked per camera
 static int camera_group_params(tile::Params& p, const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n,
@@ -1004,33 +960,27 @@ static int camera_group_tonemap_impl(const uint8_t* const* packed, void* const* 
   int dev = 0;
   MI_HIP(hipGetDevice(&dev));
   MI_REQUIRE(dev >= 0 && dev < 16, "%s: device index %d out of range", who, dev);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &cap);
-  std::lock_guard<std::mutex> lock(mega_mu());
-  ew::ResidentOrder& ord = ew::resident_order();
-  if (int rc = ew::resident_mailbox_locked(dev)) return rc;
-  mega::CBatch cb = {};
-  cb.m.s = ma;
-  cb.m.spin_limit = g_cam_poll_limit ? g_cam_poll_limit : 100000;
-  cb.m.l2_first = 1;
-  cb.m.poll_sleep = 0;
-  cb.m.mailbox = ord.mailbox_dev[dev] + ew::MAILBOX_CAMERA_GROUP;
-  cb.m.sabotage_block = -1;
-  cb.m.launch_id = g_mega.launches.fetch_add(1, std::memory_order_relaxed) + 1u;
-  cb.state9 = state9;
-  cb.gamma_inv = 1.0f / gamma;
-  cb.n_frames = n;
-  for (int i = 0; i < n; ++i) {
-    cb.io[i].src = packed[i];
-    cb.io[i].p_out = images ? images[i] : nullptr;
-    cb.io[i].out = outs[i];
-    cb.io[i].ws = static_cast<float*>(ws) + (size_t)i * ws_floats;
-  }
-  const bool direct = cap == hipStreamCaptureStatusNone;
-  if (direct) { if (int rc = ew::resident_enter_locked(dev, s)) return rc; }
-  if (int rc = mega::launch_cam(cb, pattern, s)) return rc;
-  if (direct) { if (int rc = ew::resident_leave_locked(dev, s)) return rc; }
-  return 0;
+  return ew::resident_launch(dev, s, ew::MAILBOX_CAMERA_GROUP, ew::CAPTURED_UNORDERED,
+                             [&](unsigned* mailbox, unsigned limit, bool) {
+    mega::CBatch cb = {};
+    cb.m.s = ma;
+    cb.m.spin_limit = limit ? limit : 100000;
+    cb.m.l2_first = 1;
+    cb.m.poll_sleep = 0;
+    cb.m.mailbox = mailbox;
+    cb.m.sabotage_block = -1;
+    cb.m.launch_id = g_mega.launches.fetch_add(1, std::memory_order_relaxed) + 1u;
+    cb.state9 = state9;
+    cb.gamma_inv = 1.0f / gamma;
+    cb.n_frames = n;
+    for (int i = 0; i < n; ++i) {
+      cb.io[i].src = packed[i];
+      cb.io[i].p_out = images ? images[i] : nullptr;
+      cb.io[i].out = outs[i];
+      cb.io[i].ws = static_cast<float*>(ws) + (size_t)i * ws_floats;
+    }
+    return mega::launch_cam(cb, pattern, s);
+  });
 }
 
 extern "C" int mi_isp_camera_group_tonemap(const uint8_t* const* packed, void* const* images, uint8_t* const* outs, int n, int H,
@@ -1201,10 +1151,10 @@ extern "C" int mi_isp_pipeline12_graph_launch(void* handle, void* stream) {
     MI_HIP(hipGetDevice(&dev));
     MI_REQUIRE(dev >= 0 && dev < 16, "pipeline12_graph_launch: device index %d out of range", dev);
     hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(mega_mu());             // order, launch and record under one lock (see g_mega)
-    if (int rc = ew::resident_enter_locked(dev, s)) return rc;
-    MI_HIP(hipGraphLaunch(b->exec, s));
-    return ew::resident_leave_locked(dev, s);
+    return ew::resident_launch(dev, s, ew::MAILBOX_WHOLE_FRAME, ew::CAPTURED_UNORDERED, [&](unsigned*, unsigned, bool) {
+      MI_HIP(hipGraphLaunch(b->exec, s));
+      return 0;
+    });
   }
   MI_HIP(hipGraphLaunch(b->exec, (hipStream_t)stream));
   return 0;

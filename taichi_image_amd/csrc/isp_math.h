@@ -83,8 +83,8 @@ MI_DEV void reinhard_px(const float (&t)[3], const ReinhardK& k, float (&out)[3]
 // camera_isp.py:200: the ISP's normalisation, no clamp.  The value is ROUNDED where it is made (f32_rounded: an empty asm the
 // contraction pass cannot look through): under `contract(fast)` the product would otherwise be free to fuse with whatever
 // adds to it downstream - `ad + t` of reinhard_map, `t - g` of the colour adaptation - in one kernel and not in another,
-// and the kernels that map the same pixel (pass 1, the recomputing pass 2, the one-launch tonemap, the camera-group
-// kernel of isp_mega_cam.h) must agree to the bit.  (Round 4: pass 1 had fused, the camera-group kernel had not - p
+// and the kernels that map the same pixel (pass 1, the recomputing pass 2, the camera-group kernel of isp_mega_cam.h)
+// must agree to the bit.  (Round 4: pass 1 had fused, the camera-group kernel had not - p
 // differed in the last bit for ~1 pixel in 20 000 whenever the bounds were not exactly (0, 1).)
 MI_DEV float isp_norm(float x, float lo, float inv) { return f32_rounded((x - lo) * inv); }
 

@@ -97,25 +97,21 @@ def _scene_cut_premise(refs, m, bright, gamma, la, ca):
 @pytest.mark.parametrize("gamma", GAMMAS)
 @pytest.mark.parametrize("bright", [True, False], ids=["bright_state", "dark_state"])
 @pytest.mark.parametrize("shape", [(100, 1032), (96, 1024)], ids=["partial_bands", "whole_waves"])
-def test_scene_cut(ti, dev, monkeypatch, cam, gamma, bright, shape):
-    """A dark group after the state of a bright one (and the reverse) through the ISP tonemaps: Reinhard in two launches
-    and in one (taken when H * W % 512 == 0: the (96, 1024) shape), write_back=False, process_packed12 with and without
-    the images, and linear - each against the C oracle (powf of the negative bases below the bounds), and every Reinhard
-    path bit for bit against the two launches."""
+def test_scene_cut(ti, dev, cam, gamma, bright, shape):
+    """A dark group after the state of a bright one (and the reverse) through the ISP tonemaps: Reinhard in two launches,
+    write_back=False, process_packed12 with and without the images, and linear - each against the C oracle (powf of the
+    negative bases below the bounds), and every Reinhard path bit for bit against the two launches."""
     H, W = shape
     rng = np.random.default_rng(40 + GAMMAS.index(gamma))
     state = scene_cut_state(rng, H, W, bright, "f16" if cam == "Camera16" else "f32")
     frames = [torch.from_numpy(f).to(dev) for f in scene_cut_frames(rng, H, W, bright)]
-    paths = ["two_launches", "one_launch", "keep", "process", "process_keep", "linear"]
-    if (H * W) % 512:
-        paths.remove("one_launch")                  # (the one-launch kernel takes whole waves of whole groups only)
+    paths = ["two_launches", "keep", "process", "process_keep", "linear"]
     for la, ca in ((1.0, 0.0), (0.6, 0.4)):
         kw = dict(gamma=gamma, light_adapt=la, color_adapt=ca)
         two = None
         for path in paths:
             if path == "linear" and la != 1.0:
                 continue                            # (no light_adapt / color_adapt in the linear map)
-            monkeypatch.setenv("MI_ISP_REINHARD_LAUNCHES", "1" if path == "one_launch" else "2")
             isp, st = _seeded(ti, dev, cam, state)
             if path.startswith("process"):
                 res = isp.process_packed12(frames, keep_images=path == "process_keep", **kw)
