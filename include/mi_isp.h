@@ -266,6 +266,35 @@ int mi_isp_load_packed_batch_shading(const uint8_t* const* packed_host, void* co
  * mi_isp_load_convert_levels); shading takes every mode, x being the f32 value the mode converts. */
 int mi_isp_load_convert_shading(const void* src_dev, void* dst_dev, int H, int W, int mode, int out_dtype,
                                 const mi_isp_levels* levels_host, const mi_isp_shading* shading_host, void* stream);
+/* ---- defective pixel correction (hot, stuck or dead sites) -------------------------------------------------------------
+ * A defect map of one H x W raw frame: n (row, col) int32 pairs on the device and a bit mask of H rows x ceil(W / 32)
+ * uint32 words (bit (col & 31) of word row * ceil(W / 32) + (col >> 5) set for every listed site).  x(q) is the
+ * work-dtype value the loader gives raw pixel q (levels and shading included).  A listed site (r, c) reads
+ * y = cast_work(((x1 + x2) + x3 + x4) / f32(n)) over the candidates (r-2,c), (r+2,c), (r,c-2), (r,c+2) that are inside
+ * the frame and not listed - or, if none is, the four diagonals at distance 2 under the same rule - summed in that
+ * order in f32, the division correctly rounded; with no candidate y = x(r, c).  Everything downstream (demosaic, ccm,
+ * resize, metering subsample) reads y at listed sites.  The fix-ups run after the load on the same stream:
+ *  - mi_isp_defects_fix_packed recomputes, from the packed frame, the n_outputs output pixels listed in outputs_dev
+ *    (indices row * Wd + col of the loader's output, unique; every pixel whose value reads a listed site must be
+ *    listed - its 5 x 5 demosaic footprint, through the bilinear taps with scale > 0) and the metering subsample
+ *    entries among them (sub_dev, stride sub_stride; NULL: none).  The other arguments are the loader's.
+ *  - the _batch twin does it for n frames in one launch per 32 frames with outputs; defects_host[i] may be NULL.
+ *  - mi_isp_defects_fix_cfa corrects a work-dtype (MI_F16 / MI_F32) H x W CFA in place (load_16u / 16f / 32f).
+ * Host-side checks: NULL pointers with n > 0, negative counts, output counts beyond Hd x Wd. */
+typedef struct { const int32_t* coords_dev; int32_t n; const uint32_t* mask_dev; } mi_isp_defects;
+int mi_isp_defects_fix_packed(const uint8_t* packed_dev, void* rgb_dev, int H, int W, int bits, int ids_format,
+                              int pattern, const float* ccm9_host, int work_dtype, int Hd, int Wd, float scale,
+                              void* sub_dev, int sub_stride, const mi_isp_levels* levels_host,
+                              const mi_isp_shading* shading_host, const mi_isp_defects* defects_host,
+                              const int32_t* outputs_dev, int n_outputs, void* stream);
+int mi_isp_defects_fix_packed_batch(const uint8_t* const* packed_host, void* const* rgb_host, void* const* subs_host,
+                                    int n, int H, int W, int bits, int ids_format, int pattern, const float* ccm9_host,
+                                    int work_dtype, int Hd, int Wd, float scale, int sub_stride,
+                                    const mi_isp_levels* levels_host, const mi_isp_shading* shading_host,
+                                    const mi_isp_defects* const* defects_host, const int32_t* const* outputs_host,
+                                    const int32_t* n_outputs_host, void* stream);
+int mi_isp_defects_fix_cfa(void* cfa_dev, int H, int W, int work_dtype, const mi_isp_defects* defects_host,
+                           void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==

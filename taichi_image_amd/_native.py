@@ -30,6 +30,11 @@ class Shading(ctypes.Structure):
     _fields_ = [("gains_dev", c_void_p), ("sites", c_int32), ("grid_h", c_int32), ("grid_w", c_int32)]
 
 
+class Defects(ctypes.Structure):
+    """mi_isp_defects: a defect map on the device, n (row, col) int32 pairs and a bit mask of H rows x ceil(W / 32) u32."""
+    _fields_ = [("coords_dev", c_void_p), ("n", c_int32), ("mask_dev", c_void_p)]
+
+
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SIGNATURES = {
@@ -85,6 +90,14 @@ SIGNATURES = {
                                                  c_int, c_int, POINTER(c_float), c_int, c_int, c_int, c_float, c_int,
                                                  POINTER(Levels), POINTER(Shading), _P]),
     "mi_isp_load_convert_shading": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading), _P]),
+    "mi_isp_defects_fix_packed": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int, c_int,
+                                          c_float, _P, c_int, POINTER(Levels), POINTER(Shading), POINTER(Defects), _P,
+                                          c_int, _P]),
+    "mi_isp_defects_fix_packed_batch": (c_int, [POINTER(_P), POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int,
+                                                c_int, POINTER(c_float), c_int, c_int, c_int, c_float, c_int,
+                                                POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(_P),
+                                                POINTER(c_int32), _P]),
+    "mi_isp_defects_fix_cfa": (c_int, [_P, c_int, c_int, c_int, POINTER(Defects), _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,

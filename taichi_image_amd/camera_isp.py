@@ -13,12 +13,14 @@ Deliberate differences from the reference (see DESIGN.md "quirks"):
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional
 
 import numpy as np
 import torch
 
 from . import _native, bayer, interpolate, packed, types
+from . import defects as _defects
 from . import distributed as _dist
 
 default_cc = np.array([      # camera_isp.py:230-234
@@ -403,11 +405,12 @@ def camera_isp(name: str, dtype=types.f32):
             else:
                 return image
 
-        def _convert(self, image, mode, src_dtype):
+        def _convert(self, image, mode, src_dtype, defects=None):
             if not isinstance(image, torch.Tensor):
                 raise TypeError("image must be a torch.Tensor")
             assert image.ndim == 2, "image must be a 2-D CFA"
             assert image.dtype == src_dtype, f"image must be {src_dtype}, got {image.dtype}"
+            dm = _defects.check_defects(defects, tuple(image.shape))
             lv = self._levels(16)
             if lv is not None and mode != 0:
                 raise ValueError("black_level / white_level apply to raw codes (load_16u, load_packed12/16); "
@@ -426,21 +429,50 @@ def camera_isp(name: str, dtype=types.f32):
                 _native.check(_native.lib().mi_isp_load_convert_levels(src.data_ptr(), cfa.data_ptr(), image.shape[0],
                                                                        image.shape[1], mode, dtype.code, lv,
                                                                        _native.stream_ptr(self.device)))
+            if dm is not None:                           # defective pixels: the CFA's listed sites, in place
+                _native.check(_native.lib().mi_isp_defects_fix_cfa(cfa.data_ptr(), image.shape[0], image.shape[1],
+                                                                   dtype.code, dm._arg(self.device),
+                                                                   _native.stream_ptr(self.device)))
             return self._process_image(cfa)
 
-        def load_16u(self, image):
-            """camera_isp.py:318-321 (kernel :82-87)."""
-            return self._convert(image, 0, torch.uint16)
+        def load_16u(self, image, defects=None):
+            """camera_isp.py:318-321 (kernel :82-87).  defects (an extension): None or the DefectMap of this sensor."""
+            return self._convert(image, 0, torch.uint16, defects)
 
-        def load_16f(self, image):
+        def load_16f(self, image, defects=None):
             """camera_isp.py:323-326 (kernel :95-99: u16 converted numerically)."""
-            return self._convert(image, 2, torch.uint16)
+            return self._convert(image, 2, torch.uint16, defects)
 
-        def load_32f(self, image):
+        def load_32f(self, image, defects=None):
             """camera_isp.py:328-331 (kernel :89-93)."""
-            return self._convert(image, 1, torch.float32)
+            return self._convert(image, 1, torch.float32, defects)
 
-        def _load_packed(self, image_data, bits, ids_format):
+        def _fix_defects(self, srcs, rgbs, subs, maps, h, w, bits, ids_format, hd, wd, scale, lv, sh):
+            """The sparse fix-up after a packed load on the same stream: every output pixel of rgbs[i] (and its metering
+            subsample entry) that reads a site of maps[i] (None: none) recomputed from the packed frame; one launch."""
+            L = _native.lib()
+            stream = _native.stream_ptr(self.device)
+            ccm = _native.ccm_arg(self.color_correct_matrix)
+            st = self.metering_stride if subs is not None else 1
+            lists = [None if m is None else m._outputs(self.device, hd, wd, scale) for m in maps]
+            if len(srcs) == 1:
+                if lists[0][1] == 0:
+                    return
+                _native.check(L.mi_isp_defects_fix_packed(
+                    srcs[0].data_ptr(), rgbs[0].data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
+                    ccm, dtype.code, hd, wd, float(scale), None if subs is None else subs[0].data_ptr(), st, lv, sh,
+                    maps[0]._arg(self.device), lists[0][0].data_ptr(), lists[0][1], stream))
+                return
+            args = [None if m is None else m._arg(self.device) for m in maps]       # (kept alive through the call)
+            p_maps = (ctypes.c_void_p * len(maps))(*[None if a is None else ctypes.addressof(a) for a in args])
+            p_lists = (ctypes.c_void_p * len(maps))(*[None if l is None else l[0].data_ptr() for l in lists])
+            counts = (ctypes.c_int32 * len(maps))(*[0 if l is None else l[1] for l in lists])
+            _native.check(L.mi_isp_defects_fix_packed_batch(
+                _native.ptr_array(srcs), _native.ptr_array(rgbs), None if subs is None else _native.ptr_array(subs),
+                len(srcs), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value, ccm, dtype.code, hd, wd,
+                float(scale), st, lv, sh, p_maps, p_lists, counts, stream))
+
+        def _load_packed(self, image_data, bits, ids_format, defects=None):
             if not isinstance(image_data, torch.Tensor):
                 raise TypeError("image_data must be a torch.Tensor")
             assert image_data.ndim == 2 and image_data.dtype == torch.uint8, "image_data must be (H, bytes) uint8"
@@ -451,6 +483,7 @@ def camera_isp(name: str, dtype=types.f32):
                 w, h = (image_data.shape[1] // 2, image_data.shape[0])             # camera_isp.py:343
             assert w % 2 == 0 and h % 2 == 0, "image must be even size"
             lv = self._levels(bits)
+            dm = _defects.check_defects(defects, (h, w))
             src = image_data.to(self.device).contiguous()
             L = _native.lib()
             # with levels: the same calls through their *_levels twins (the same kernels' level-taking instantiations)
@@ -477,6 +510,8 @@ def camera_isp(name: str, dtype=types.f32):
                 _native.check(load(
                     src.data_ptr(), rgb.data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
                     _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, 0.0, _native.stream_ptr(self.device)))
+                if dm is not None:
+                    self._fix_defects([src], [rgb], None, [dm], h, w, bits, ids_format, hd, wd, 0.0, lv, sh)
                 return self.resize_image(rgb)
             st = self.metering_stride
             if fused or not L.mi_isp_load_packed_metered_is_fused(h, w, bits, int(bool(ids_format)), dtype.code, st):
@@ -484,6 +519,9 @@ def camera_isp(name: str, dtype=types.f32):
                     src.data_ptr(), rgb.data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
                     _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, float(scale) if fused else 0.0,
                     _native.stream_ptr(self.device)))
+                if dm is not None:
+                    self._fix_defects([src], [rgb], None, [dm], h, w, bits, ids_format, hd, wd,
+                                      float(scale) if fused else 0.0, lv, sh)
                 return rgb
             # the image and, on the way, the stride-subsampled copy update_metering will ask for (camera_isp.py:168-170):
             # the load kernel holds those pixels anyway, the strided gather over six 4K images costs 25 us per call
@@ -492,24 +530,40 @@ def camera_isp(name: str, dtype=types.f32):
                 src.data_ptr(), rgb.data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
                 _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, 0.0,
                 sub.data_ptr(), st, _native.stream_ptr(self.device)))
+            if dm is not None:
+                self._fix_defects([src], [rgb], [sub], [dm], h, w, bits, ids_format, hd, wd, 0.0, lv, sh)
             _tag_subsample(rgb, sub, st)
             return rgb
 
-        def load_packed12(self, image_data, ids_format=False):
-            """camera_isp.py:333-340: unpack + demosaic (+ccm) fused in one pass over the packed frame."""
-            return self._load_packed(image_data, 12, ids_format)
+        def load_packed12(self, image_data, ids_format=False, defects=None):
+            """camera_isp.py:333-340: unpack + demosaic (+ccm) fused in one pass over the packed frame.
+            defects (an extension): None or the DefectMap of this sensor ("Defective pixels")."""
+            return self._load_packed(image_data, 12, ids_format, defects)
 
-        def load_packed12_batch(self, images_data: List[torch.Tensor], ids_format=False) -> List[torch.Tensor]:
+        def load_packed12_batch(self, images_data: List[torch.Tensor], ids_format=False,
+                                defects=None) -> List[torch.Tensor]:
             """Extension (not in the reference): `[self.load_packed12(d, ids_format) for d in images_data]` for the cameras
             of one group - frames of one size - in ONE launch per 8 cameras (mi_isp_load_packed_batch): same results, bit
-            for bit, without the other launches' dispatch, table build and drain (config 3: 43.0 -> 39.5 us per frame)."""
-            return self._load_packed_batch(images_data, 12, ids_format)
+            for bit, without the other launches' dispatch, table build and drain (config 3: 43.0 -> 39.5 us per frame).
+            defects: None, or one entry per frame (a DefectMap or None); the fix-ups of all frames take one launch."""
+            return self._load_packed_batch(images_data, 12, ids_format, defects)
 
-        def load_packed16_batch(self, images_data: List[torch.Tensor]) -> List[torch.Tensor]:
+        def load_packed16_batch(self, images_data: List[torch.Tensor], defects=None) -> List[torch.Tensor]:
             """The same for `load_packed16` (camera_isp.py:342-347)."""
-            return self._load_packed_batch(images_data, 16, False)
+            return self._load_packed_batch(images_data, 16, False, defects)
 
-        def _load_packed_batch(self, images_data, bits, ids_format):
+        def _batch_defects(self, defects, n, shape):
+            """The per-frame maps of a batch call, None for each frame without one, all None for defects=None; ValueError
+            for a list of another length or a map of another frame shape."""
+            if defects is None:
+                return [None] * n
+            if not isinstance(defects, (list, tuple)):
+                raise ValueError(f"defects must be None or a list with one entry per frame, got {type(defects).__name__}")
+            if len(defects) != n:
+                raise ValueError(f"defects has {len(defects)} entries for {n} frames")
+            return [_defects.check_defects(d, shape) for d in defects]
+
+        def _load_packed_batch(self, images_data, bits, ids_format, defects=None):
             _typecheck("images_data", images_data, list)
             if len(images_data) == 0:
                 return []
@@ -524,6 +578,7 @@ def camera_isp(name: str, dtype=types.f32):
                 assert images_data[0].shape[1] % 3 == 0, "packed-12 rows must hold whole pixel pairs (bytes % 3 == 0)"
             assert w % 2 == 0 and h % 2 == 0, "image must be even size"
             lv = self._levels(bits)
+            maps = self._batch_defects(defects, len(images_data), (h, w))
             L = _native.lib()
             if self.resize_width > 0:
                 scale = self.resize_width / w
@@ -535,7 +590,7 @@ def camera_isp(name: str, dtype=types.f32):
                 scale, out_size = 0.0, (w, h)
             fused = scale > 0 and min(out_size) > 0 and L.mi_isp_load_packed_scale_supported(float(scale))
             if scale > 0 and not fused:                      # a scale the fused kernel does not take
-                return [self._load_packed(d, bits, ids_format) for d in images_data]
+                return [self._load_packed(d, bits, ids_format, m) for d, m in zip(images_data, maps)]
             wd, hd = out_size if fused else (w, h)
             srcs = [d.to(self.device).contiguous() for d in images_data]
             rgbs = [torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device) for _ in srcs]
@@ -553,14 +608,17 @@ def camera_isp(name: str, dtype=types.f32):
                 _native.check(L.mi_isp_load_packed_batch(*args, _native.stream_ptr(self.device)))
             else:
                 _native.check(L.mi_isp_load_packed_batch_levels(*args, lv, _native.stream_ptr(self.device)))
+            if any(m is not None for m in maps):
+                self._fix_defects(srcs, rgbs, subs, maps, h, w, bits, ids_format, hd, wd, float(scale) if fused else 0.0,
+                                  lv, sh)
             if subs is not None:
                 for rgb, sub in zip(rgbs, subs):
                     _tag_subsample(rgb, sub, st)
             return rgbs
 
-        def load_packed16(self, image_data):
+        def load_packed16(self, image_data, defects=None):
             """camera_isp.py:342-347."""
-            return self._load_packed(image_data, 16, False)
+            return self._load_packed(image_data, 16, False, defects)
 
         @property
         def color_correct_matrix(self) -> Optional[np.ndarray]:
@@ -694,7 +752,7 @@ def camera_isp(name: str, dtype=types.f32):
 
         def process_packed12(self, frames: List[torch.Tensor], gamma: float = 1.0, intensity: float = 1.0,
                              light_adapt: float = 1.0, color_adapt: float = 0.0, keep_images: bool = False,
-                             ids_format: bool = False):
+                             ids_format: bool = False, defects=None):
             """Extension (not in the reference): one step of the reference's own bench in one call -
             `Processor.__call__` of bench/camera_isp.py:23-27:
 
@@ -708,7 +766,9 @@ def camera_isp(name: str, dtype=types.f32):
             launch takes every camera from packed bytes to its u8 image (csrc/isp_mega_cam.h).  Everything else takes the
             two calls above.
             keep_images=True returns `(outputs, images)`, the images holding what the reference leaves in them (p,
-            camera_isp.py:211); by default only the outputs are returned, as the bench's Processor does."""
+            camera_isp.py:211); by default only the outputs are returned, as the bench's Processor does.
+            defects: None, or one entry per frame (a DefectMap or None); any map takes the two calls, the load with
+            `defects=`."""
             _typecheck("frames", frames, list)
             _typecheck("keep_images", keep_images, bool)
             for n, v in (("gamma", gamma), ("intensity", intensity), ("light_adapt", light_adapt),
@@ -718,8 +778,14 @@ def camera_isp(name: str, dtype=types.f32):
             L = _native.lib()
             f0 = frames[0]
             lv = self._levels(12)                            # (sensor levels: checked before anything runs)
+            if defects is not None:                          # (defect maps too)
+                if not (isinstance(f0, torch.Tensor) and f0.ndim == 2):
+                    raise TypeError("frames must be (H, bytes) uint8 tensors")
+                maps = self._batch_defects(defects, len(frames), (f0.shape[0], f0.shape[1] * 2 // 3))
+                defects = maps if any(m is not None for m in maps) else None
             fused = (dtype is types.f16 and not ids_format and self.resize_width == 0 and self.scale is None
                      and self._shading is None                # (lens shading: the two calls below)
+                     and defects is None                      # (defective pixels: the two calls below)
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8
                      and 1 <= len(frames) <= 64
                      and all(isinstance(f, torch.Tensor) and f.ndim == 2 and f.dtype == torch.uint8 and f.shape == f0.shape
@@ -737,7 +803,7 @@ def camera_isp(name: str, dtype=types.f32):
                     fused = bool(L.mi_isp_camera_group_fits(h, w, self._demosaic_pattern.value, dtype.code, 8) if lv is None
                                  else L.mi_isp_camera_group_fits_levels(h, w, self._demosaic_pattern.value, dtype.code, 8, lv))
             if not fused:
-                images = self.load_packed12_batch(frames, ids_format)
+                images = self.load_packed12_batch(frames, ids_format, defects=defects)
                 outputs = self.tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt)
                 return (outputs, images) if keep_images else outputs
             _raise_resident_faults(L, self.device)

@@ -10,6 +10,7 @@
 #include "isp_mega.h"
 #include "isp_mega_cam.h"
 #include "isp_stream_resize.h"
+#include "isp_defects.h"
 #include <mutex>
 #include <atomic>
 
@@ -22,7 +23,7 @@ void mi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int mi_isp_version(void) { return 1300; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
+extern "C" int mi_isp_version(void) { return 1400; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
 extern "C" const char* mi_isp_last_error(void) { return g_err; }
 
 extern "C" int mi_isp_bayer_weights(int32_t out[4 * 13 * 3]) {
@@ -356,6 +357,101 @@ extern "C" int mi_isp_load_packed_metered_shading(const uint8_t* packed, void* r
 }
 
 extern "C" int mi_isp_load_packed_scale_supported(float scale) { return rtile::scales_fit(scale, scale) ? 1 : 0; }
+
+// ---- defective pixel correction (mi_isp_defects) ---------------------------------------------------------
+static int check_defects(const mi_isp_defects* d, const char* who) {
+  MI_REQUIRE(d, "%s: null defect map", who);
+  MI_REQUIRE(d->n >= 0, "%s: negative defect count %d", who, (int)d->n);
+  MI_REQUIRE(d->n == 0 || (d->coords_dev && d->mask_dev), "%s: %d defects without coordinates or mask", who, (int)d->n);
+  return 0;
+}
+
+// the fix-up of n packed frames sharing one geometry: camera i (maps[i] may be NULL: no correction) recomputes the
+// n_outputs[i] pixels of outputs[i]; one launch per MAX_CAMS cameras that have outputs
+static int defects_fix_packed_impl(const uint8_t* const* packed, void* const* rgb, void* const* subs, int n, int H, int W,
+                                   int bits, int ids_format, int pattern, const float* ccm9, int work_dtype, int Hd,
+                                   int Wd, float scale, int sub_stride, const mi_isp_levels* lv, const mi_isp_shading* sh,
+                                   const mi_isp_defects* const* maps, const int32_t* const* outputs,
+                                   const int32_t* n_outputs, void* stream, const char* who) {
+  MI_REQUIRE(n >= 0, "%s: negative frame count", who);
+  if (n == 0) return 0;
+  MI_REQUIRE(packed && rgb && maps && outputs && n_outputs, "%s: null pointer", who);
+  if (sh)
+    if (int rc = check_shading(sh, who)) return rc;
+  dfx::Args a = {};
+  if (int rc = fill_common(a.t, H, W, pattern, ccm9, who)) return rc;
+  if (int rc = packed_params(a.t, packed[0], H, W, bits, ids_format, work_dtype, who)) return rc;
+  if (int rc = apply_levels_shading(a.t, lv, sh, bits, who)) return rc;
+  if (a.t.levels == 0)                                     // the plain decode through the per-site arrays
+    for (int s = 0; s < 4; ++s) { a.t.lv_black[s] = 0; a.t.lv_k[s] = a.t.k_decode; }
+  MI_REQUIRE(Hd > 0 && Wd > 0, "%s: bad output shape %dx%d", who, Hd, Wd);
+  MI_REQUIRE(scale > 0.f || (Hd == H && Wd == W), "%s: output shape must equal the frame when scale <= 0", who);
+  MI_REQUIRE(!subs || sub_stride >= 1, "%s: bad subsample stride %d", who, sub_stride);
+  a.Hd = Hd; a.Wd = Wd; a.resize = scale > 0.f; a.s = scale;
+  a.st = subs ? sub_stride : 1; a.sub_w = subs ? (Wd + sub_stride - 1) / sub_stride : 0;
+  a.pr = pattern >> 1; a.pc = pattern & 1;                 // RGGB 0, GRBG 1, GBRG 2, BGGR 3
+  a.mask_w = (W + 31) / 32;
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(packed[i] && rgb[i] && (!subs || subs[i]), "%s: frame %d has a null buffer", who, i);
+    if (!maps[i]) continue;
+    if (int rc = check_defects(maps[i], who)) return rc;
+    MI_REQUIRE(n_outputs[i] >= 0 && (int64_t)n_outputs[i] <= (int64_t)Hd * Wd, "%s: frame %d lists %d outputs of %dx%d",
+               who, i, (int)n_outputs[i], Hd, Wd);
+    MI_REQUIRE(n_outputs[i] == 0 || (outputs[i] && maps[i]->n > 0), "%s: frame %d lists outputs without them or a map",
+               who, i);
+  }
+  for (int i = 0; i < n; ++i) {
+    if (maps[i] && n_outputs[i] > 0) {
+      dfx::Cam& c = a.cam[a.n_cams++];
+      c.src = packed[i]; c.dst = rgb[i]; c.sub = subs ? subs[i] : nullptr; c.mask = maps[i]->mask_dev;
+      c.list = outputs[i]; c.start = a.total; c.n = n_outputs[i];
+      MI_REQUIRE((int64_t)a.total + c.n < (int64_t)INT32_MAX, "%s: too many outputs in one launch", who);
+      a.total += c.n;
+    }
+    if (a.n_cams == dfx::MAX_CAMS || (i == n - 1 && a.n_cams > 0)) {
+      if (int rc = dfx::launch_packed(a, work_dtype, (hipStream_t)stream)) return rc;
+      a.n_cams = 0; a.total = 0;
+    }
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_defects_fix_packed(const uint8_t* packed, void* rgb, int H, int W, int bits, int ids_format,
+                                         int pattern, const float* ccm9, int work_dtype, int Hd, int Wd, float scale,
+                                         void* sub, int sub_stride, const mi_isp_levels* levels,
+                                         const mi_isp_shading* shading, const mi_isp_defects* defects,
+                                         const int32_t* outputs, int n_outputs, void* stream) {
+  MI_REQUIRE(packed && rgb, "defects_fix_packed: null pointer");
+  if (int rc = check_defects(defects, "defects_fix_packed")) return rc;
+  void* const subs[1] = {sub};
+  const mi_isp_defects* const maps[1] = {defects};
+  const int32_t* const outs[1] = {outputs};
+  const int32_t counts[1] = {n_outputs};
+  return defects_fix_packed_impl(&packed, &rgb, sub ? subs : nullptr, 1, H, W, bits, ids_format, pattern, ccm9,
+                                 work_dtype, Hd, Wd, scale, sub_stride, levels, shading, maps, outs, counts, stream,
+                                 "defects_fix_packed");
+}
+
+extern "C" int mi_isp_defects_fix_packed_batch(const uint8_t* const* packed, void* const* rgb, void* const* subs, int n,
+                                               int H, int W, int bits, int ids_format, int pattern, const float* ccm9,
+                                               int work_dtype, int Hd, int Wd, float scale, int sub_stride,
+                                               const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                               const mi_isp_defects* const* defects, const int32_t* const* outputs,
+                                               const int32_t* n_outputs, void* stream) {
+  return defects_fix_packed_impl(packed, rgb, subs, n, H, W, bits, ids_format, pattern, ccm9, work_dtype, Hd, Wd, scale,
+                                 sub_stride, levels, shading, defects, outputs, n_outputs, stream,
+                                 "defects_fix_packed_batch");
+}
+
+extern "C" int mi_isp_defects_fix_cfa(void* cfa, int H, int W, int work_dtype, const mi_isp_defects* defects,
+                                      void* stream) {
+  MI_REQUIRE(cfa, "defects_fix_cfa: null pointer");
+  MI_REQUIRE(H > 0 && W > 0, "defects_fix_cfa: bad shape %dx%d", H, W);
+  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "defects_fix_cfa: work dtype must be f16 or f32");
+  if (int rc = check_defects(defects, "defects_fix_cfa")) return rc;
+  MI_REQUIRE((int64_t)defects->n <= (int64_t)H * W, "defects_fix_cfa: %d defects in a %dx%d frame", (int)defects->n, H, W);
+  return dfx::launch_cfa(cfa, H, W, work_dtype, defects->coords_dev, defects->n, defects->mask_dev, (hipStream_t)stream);
+}
 
 // ---- measurement aid: HIP events around each data pass, on the stream it runs on ---------------------
 #include <vector>

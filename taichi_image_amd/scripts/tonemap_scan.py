@@ -99,6 +99,30 @@ def write_png(path, image: np.ndarray) -> None:
                 chunk(b"IDAT", zlib.compress(scanlines, 3)) + chunk(b"IEND", b""))
 
 
+def load_defect_pixels(directory, cameras: Sequence[Path], width: int) -> Dict[str, np.ndarray]:
+    """--defect-pixels: `directory/<camera folder name>.npy` holds one camera's (N, 2) integer (row, col) defect
+    coordinates; a camera without a file gets no correction.  Checked before any frame is read: ValueError for a file of
+    another shape or dtype, a coordinate outside the frame width, or a file that names no camera of the scan (the rows
+    are checked against the frame height when the first frame is read)."""
+    directory = Path(directory)
+    if not directory.is_dir():
+        raise FileNotFoundError(f"--defect-pixels: {directory} does not exist or is not a directory")
+    names = {c.name for c in cameras}
+    maps = {}
+    for f in sorted(directory.glob("*.npy"), key=lambda p: natural_key(p.name)):
+        if f.stem not in names:
+            raise ValueError(f"--defect-pixels: {f.name} names no camera of the scan ({sorted(names)})")
+        c = np.load(f, allow_pickle=False)
+        if c.size == 0:
+            c = np.zeros((0, 2), np.int64)
+        if c.ndim != 2 or c.shape[1] != 2 or c.dtype == np.bool_ or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError(f"--defect-pixels: {f.name} must hold (N, 2) integer (row, col), got {c.dtype} {c.shape}")
+        if len(c) and (c.min() < 0 or c[:, 1].max() >= width):
+            raise ValueError(f"--defect-pixels: {f.name} has a coordinate outside a frame {width} pixels wide")
+        maps[f.stem] = c
+    return maps
+
+
 def build_parser() -> argparse.ArgumentParser:
     """The argument surface of scripts/tonemap_scan.py:104-128 (+ --device, --ids_format)."""
     from ..interpolate import ImageTransform
@@ -129,6 +153,9 @@ def build_parser() -> argparse.ArgumentParser:
     # lens shading (an extension): a (Gh, Gw) or (4, Gh, Gw) f32 gain grid saved with numpy.save
     # (camera_isp.lens_shading_from_flat makes one from a flat-field capture)
     tone.add_argument("--lens-shading", dest="lens_shading", type=Path, default=None)
+    # defective pixels (an extension): a directory of <camera folder name>.npy files, (N, 2) int (row, col) each
+    # (defects.find_defects makes one from dark or flat frames)
+    tone.add_argument("--defect-pixels", dest="defect_pixels", type=Path, default=None)
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -139,6 +166,7 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     from functools import partial
     from .. import bayer, camera_isp, ingest
+    from ..defects import DefectMap
     args = build_parser().parse_args(argv)
     if args.scan is None and args.images is None:
         raise ValueError("No --scan or --images specified")
@@ -152,6 +180,8 @@ def main(argv=None) -> int:
         shading = np.load(args.lens_shading, allow_pickle=False)
         camera_isp._check_shading(shading)                          # (also before any frame is read)
     index = ScanIndex.of_scan(args.scan) if args.scan is not None else ScanIndex.of_directory(args.images)
+    coords = {} if args.defect_pixels is None else load_defect_pixels(args.defect_pixels, index.cameras, args.width)
+    maps = None                                                     # one DefectMap per camera, once the height is known
     print(f"{len(index.cameras)} camera(s) {[c.name for c in index.cameras]}, {len(index.frames)} frame(s) each")
     device = torch.device(args.device)
     isp = camera_isp.Camera32(bayer.BayerPattern.RGGB, transform=args.transform, moving_alpha=args.moving_alpha,
@@ -164,7 +194,11 @@ def main(argv=None) -> int:
     for name, raws in index.groups(partial(ingest.load_raw_bytes, device=device), args.reverse):
         for raw in raws:
             assert raw.numel() % row_bytes == 0, f"{name}: {raw.numel()} bytes is not a whole number of {row_bytes}-byte rows"
-        images = [isp.load_packed12(raw.view(-1, row_bytes), ids_format=args.ids_format) for raw in raws]
+        frames = [raw.view(-1, row_bytes) for raw in raws]
+        if maps is None:
+            shape = (frames[0].shape[0], args.width)
+            maps = [DefectMap(coords[c.name], shape) if c.name in coords else None for c in index.cameras]
+        images = [isp.load_packed12(f, ids_format=args.ids_format, defects=m) for f, m in zip(frames, maps)]
         outputs = isp.tonemap_reinhard(images, gamma=args.gamma, intensity=args.intensity,
                                        color_adapt=args.color_adapt, light_adapt=args.light_adapt)
         if args.write is not None:
