@@ -295,6 +295,42 @@ int mi_isp_defects_fix_packed_batch(const uint8_t* const* packed_host, void* con
                                     const int32_t* n_outputs_host, void* stream);
 int mi_isp_defects_fix_cfa(void* cfa_dev, int H, int W, int work_dtype, const mi_isp_defects* defects_host,
                            void* stream);
+/* ---- lens distortion correction (geometric undistortion, a bilinear remap) ------------------------------------------
+ * OpenCV's pinhole model: K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] of the distorted source (fx, fy > 0, no skew),
+ * new_K = [[fx', 0, cx'], [0, fy', cy'], [0, 0, 1]] of the undistorted output, dist in OpenCV order: (k1, k2, p1, p2),
+ * (k1, k2, p1, p2, k3) or the rational (k1, k2, p1, p2, k3, k4, k5, k6) (n_dist 4, 5 or 8; unused entries ignored).
+ * Every value must be finite.  The library rounds each once from double to f32, and ifx' = 1 / fx', ify' = 1 / fy' are
+ * computed in double and rounded.  Output pixel (r, c) of an Hd x Wd image at output scale (s0, s1) (1 without a
+ * resize; no half-pixel offset) reads, every step one f32 operation rounded to nearest, left to right, never contracted:
+ *   u = f32(c) / s1, v = f32(r) / s0;  x = (u - cx') * ifx', y = (v - cy') * ify';  r2 = x*x + y*y
+ *   num = 1 + r2*(k1 + r2*(k2 + r2*k3));  radial = num, or rational: num / (1 + r2*(k4 + r2*(k5 + r2*k6)))
+ *   xd = x*radial + (2*p1)*x*y + p2*(r2 + 2*x*x);  yd = y*radial + p1*(r2 + 2*y*y) + (2*p2)*x*y
+ *   us = fx*xd + cx, vs = fy*yd + cy
+ * and samples the H x W source RGB at (us, vs): border MI_BORDER_CONSTANT gives 0 outside [0, H-1] x [0, W-1] (and for
+ * NaN); MI_BORDER_REPLICATE clamps vs and us into that range first (NaN to 0).  i = floor(vs), fr = vs - f32(i), j and fc
+ * the same; taps i, i+1, j, j+1 with the +1 taps clamped to the frame; mix(x, y, a) = x*(1-a) + y*a over rows, then
+ * columns, then * scale(out) / scale(in) and the cast - the bilinear resize's arithmetic (mi_isp_resize_bilinear).
+ *  - mi_isp_undistort: one image; mi_isp_undistort_batch: n images of one geometry, each with its own lens (one launch
+ *    per 32 images and border mode); lens_host[i] must not be NULL.
+ *  - mi_isp_remap: the table form - map_dev holds Hd x Wd (us, vs) f32 pairs (OpenCV's map_x / map_y interleaved),
+ *    8-byte aligned - sampled by the same rule.
+ * Host-side checks (error text names "lens"): NULL pointers, shapes, dtypes, border, n_dist, non-finite values,
+ * non-positive focal lengths or output scales. */
+enum { MI_BORDER_CONSTANT = 0, MI_BORDER_REPLICATE = 1 };
+typedef struct {
+  double fx, fy, cx, cy;                  /* K */
+  double new_fx, new_fy, new_cx, new_cy;  /* new_K */
+  double dist[8];                         /* k1, k2, p1, p2, k3, k4, k5, k6 */
+  int32_t n_dist;                         /* 4, 5 or 8 */
+  int32_t border;                         /* MI_BORDER_* */
+} mi_isp_lens;
+int mi_isp_undistort(const void* src_dev, void* dst_dev, int H, int W, int Hd, int Wd, float s0, float s1, int in_dtype,
+                     int out_dtype, const mi_isp_lens* lens_host, void* stream);
+int mi_isp_undistort_batch(const void* const* src_host, void* const* dst_host, int n, int H, int W, int Hd, int Wd,
+                           float s0, float s1, int in_dtype, int out_dtype, const mi_isp_lens* const* lens_host,
+                           void* stream);
+int mi_isp_remap(const void* src_dev, void* dst_dev, const float* map_dev, int H, int W, int Hd, int Wd, int in_dtype,
+                 int out_dtype, int border, void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p, POINTER
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p, POINTER
 
 import numpy as np
 import torch
@@ -33,6 +33,14 @@ class Shading(ctypes.Structure):
 class Defects(ctypes.Structure):
     """mi_isp_defects: a defect map on the device, n (row, col) int32 pairs and a bit mask of H rows x ceil(W / 32) u32."""
     _fields_ = [("coords_dev", c_void_p), ("n", c_int32), ("mask_dev", c_void_p)]
+
+
+class Lens(ctypes.Structure):
+    """mi_isp_lens: K, new_K, up to 8 distortion coefficients in OpenCV order (k1, k2, p1, p2, k3, k4, k5, k6), how many
+    of them (4, 5 or 8) and the border mode (MI_BORDER_CONSTANT 0, MI_BORDER_REPLICATE 1)."""
+    _fields_ = [("fx", c_double), ("fy", c_double), ("cx", c_double), ("cy", c_double),
+                ("new_fx", c_double), ("new_fy", c_double), ("new_cx", c_double), ("new_cy", c_double),
+                ("dist", c_double * 8), ("n_dist", c_int32), ("border", c_int32)]
 
 
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
@@ -98,6 +106,10 @@ SIGNATURES = {
                                                 POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(_P),
                                                 POINTER(c_int32), _P]),
     "mi_isp_defects_fix_cfa": (c_int, [_P, c_int, c_int, c_int, POINTER(Defects), _P]),
+    "mi_isp_undistort": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, POINTER(Lens), _P]),
+    "mi_isp_undistort_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
+                                       c_int, POINTER(_P), _P]),
+    "mi_isp_remap": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,

@@ -21,6 +21,7 @@ import torch
 
 from . import _native, bayer, interpolate, packed, types
 from . import defects as _defects
+from . import lens as _lens
 from . import distributed as _dist
 
 default_cc = np.array([      # camera_isp.py:230-234
@@ -405,12 +406,13 @@ def camera_isp(name: str, dtype=types.f32):
             else:
                 return image
 
-        def _convert(self, image, mode, src_dtype, defects=None):
+        def _convert(self, image, mode, src_dtype, defects=None, undistort=None):
             if not isinstance(image, torch.Tensor):
                 raise TypeError("image must be a torch.Tensor")
             assert image.ndim == 2, "image must be a 2-D CFA"
             assert image.dtype == src_dtype, f"image must be {src_dtype}, got {image.dtype}"
             dm = _defects.check_defects(defects, tuple(image.shape))
+            lens = self._check_lens(undistort, *image.shape)
             lv = self._levels(16)
             if lv is not None and mode != 0:
                 raise ValueError("black_level / white_level apply to raw codes (load_16u, load_packed12/16); "
@@ -433,19 +435,63 @@ def camera_isp(name: str, dtype=types.f32):
                 _native.check(_native.lib().mi_isp_defects_fix_cfa(cfa.data_ptr(), image.shape[0], image.shape[1],
                                                                    dtype.code, dm._arg(self.device),
                                                                    _native.stream_ptr(self.device)))
-            return self._process_image(cfa)
+            return self._process_image(cfa, lens)
 
-        def load_16u(self, image, defects=None):
-            """camera_isp.py:318-321 (kernel :82-87).  defects (an extension): None or the DefectMap of this sensor."""
-            return self._convert(image, 0, torch.uint16, defects)
+        def load_16u(self, image, defects=None, undistort=None):
+            """camera_isp.py:318-321 (kernel :82-87).  defects (an extension): None or the DefectMap of this sensor.
+            undistort (an extension): None or the lens.LensDistortion of this camera ("Lens distortion")."""
+            return self._convert(image, 0, torch.uint16, defects, undistort)
 
-        def load_16f(self, image, defects=None):
+        def load_16f(self, image, defects=None, undistort=None):
             """camera_isp.py:323-326 (kernel :95-99: u16 converted numerically)."""
-            return self._convert(image, 2, torch.uint16, defects)
+            return self._convert(image, 2, torch.uint16, defects, undistort)
 
-        def load_32f(self, image, defects=None):
+        def load_32f(self, image, defects=None, undistort=None):
             """camera_isp.py:328-331 (kernel :89-93)."""
-            return self._convert(image, 1, torch.float32, defects)
+            return self._convert(image, 1, torch.float32, defects, undistort)
+
+        def _lens_geometry(self, h, w):
+            """(Hd, Wd, scale) of the output of an h x w frame: resize_image's size and scale, or the frame at scale 1."""
+            if self.resize_width > 0:
+                scale = self.resize_width / w
+                return round(h * scale), self.resize_width, scale
+            if self.scale is not None:
+                return round(h * self.scale), round(w * self.scale), self.scale
+            return h, w, 1.0
+
+        def _check_lens(self, undistort, h, w):
+            """The lens of an h x w frame (None: none); ValueError for another frame shape or a table of another output
+            shape than the loader's."""
+            if undistort is None:
+                return None
+            return _lens.check_lens(undistort, (h, w), self._lens_geometry(h, w)[:2])
+
+        def _undistort(self, rgbs, lenses, h, w):
+            """The full-resolution work-dtype images rgbs remapped through lenses (one each, none None) into new images
+            at the ISP's resize geometry (one launch for the analytic lenses)."""
+            hd, wd, scale = self._lens_geometry(h, w)
+            outs = [torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device) for _ in rgbs]
+            if hd * wd:
+                _lens.apply(lenses, rgbs, outs, h, w, hd, wd, scale, scale, dtype.code, dtype.code, self.device)
+            return outs
+
+        def _load_full(self, srcs, h, w, bits, ids_format, lv, sh, maps):
+            """The frames loaded at full resolution (levels, shading and defect fix-ups at scale 0) in one batch launch,
+            without a metering subsample: the source of a lens remap."""
+            L = _native.lib()
+            rgbs = [torch.empty((h, w, 3), dtype=torch_dtype, device=self.device) for _ in srcs]
+            args = (_native.ptr_array(srcs), _native.ptr_array(rgbs), None, len(srcs), h, w, bits, int(bool(ids_format)),
+                    self._demosaic_pattern.value, _native.ccm_arg(self.color_correct_matrix), dtype.code, h, w, 0.0,
+                    self.metering_stride)
+            if sh is not None:
+                _native.check(L.mi_isp_load_packed_batch_shading(*args, lv, sh, _native.stream_ptr(self.device)))
+            elif lv is None:
+                _native.check(L.mi_isp_load_packed_batch(*args, _native.stream_ptr(self.device)))
+            else:
+                _native.check(L.mi_isp_load_packed_batch_levels(*args, lv, _native.stream_ptr(self.device)))
+            if any(m is not None for m in maps):
+                self._fix_defects(srcs, rgbs, None, maps, h, w, bits, ids_format, h, w, 0.0, lv, sh)
+            return rgbs
 
         def _fix_defects(self, srcs, rgbs, subs, maps, h, w, bits, ids_format, hd, wd, scale, lv, sh):
             """The sparse fix-up after a packed load on the same stream: every output pixel of rgbs[i] (and its metering
@@ -472,7 +518,7 @@ def camera_isp(name: str, dtype=types.f32):
                 len(srcs), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value, ccm, dtype.code, hd, wd,
                 float(scale), st, lv, sh, p_maps, p_lists, counts, stream))
 
-        def _load_packed(self, image_data, bits, ids_format, defects=None):
+        def _load_packed(self, image_data, bits, ids_format, defects=None, undistort=None):
             if not isinstance(image_data, torch.Tensor):
                 raise TypeError("image_data must be a torch.Tensor")
             assert image_data.ndim == 2 and image_data.dtype == torch.uint8, "image_data must be (H, bytes) uint8"
@@ -484,7 +530,11 @@ def camera_isp(name: str, dtype=types.f32):
             assert w % 2 == 0 and h % 2 == 0, "image must be even size"
             lv = self._levels(bits)
             dm = _defects.check_defects(defects, (h, w))
+            lens = self._check_lens(undistort, h, w)
             src = image_data.to(self.device).contiguous()
+            if lens is not None:                         # lens distortion: a full-resolution load, then the remap
+                rgb = self._load_full([src], h, w, bits, ids_format, lv, _native.shading_arg(self._shading), [dm])
+                return self._undistort(rgb, [lens], h, w)[0]
             L = _native.lib()
             # with levels: the same calls through their *_levels twins (the same kernels' level-taking instantiations)
             load = L.mi_isp_load_packed if lv is None else (lambda *a: L.mi_isp_load_packed_levels(*a[:-1], lv, a[-1]))
@@ -535,22 +585,36 @@ def camera_isp(name: str, dtype=types.f32):
             _tag_subsample(rgb, sub, st)
             return rgb
 
-        def load_packed12(self, image_data, ids_format=False, defects=None):
+        def load_packed12(self, image_data, ids_format=False, defects=None, undistort=None):
             """camera_isp.py:333-340: unpack + demosaic (+ccm) fused in one pass over the packed frame.
-            defects (an extension): None or the DefectMap of this sensor ("Defective pixels")."""
-            return self._load_packed(image_data, 12, ids_format, defects)
+            defects (an extension): None or the DefectMap of this sensor ("Defective pixels").
+            undistort (an extension): None or the lens.LensDistortion of this camera ("Lens distortion"): the
+            frame is loaded at full resolution, then remapped at the resize geometry (the fused resize is not used)."""
+            return self._load_packed(image_data, 12, ids_format, defects, undistort)
 
         def load_packed12_batch(self, images_data: List[torch.Tensor], ids_format=False,
-                                defects=None) -> List[torch.Tensor]:
+                                defects=None, undistort=None) -> List[torch.Tensor]:
             """Extension (not in the reference): `[self.load_packed12(d, ids_format) for d in images_data]` for the cameras
             of one group - frames of one size - in ONE launch per 8 cameras (mi_isp_load_packed_batch): same results, bit
             for bit, without the other launches' dispatch, table build and drain (config 3: 43.0 -> 39.5 us per frame).
-            defects: None, or one entry per frame (a DefectMap or None); the fix-ups of all frames take one launch."""
-            return self._load_packed_batch(images_data, 12, ids_format, defects)
+            defects: None, or one entry per frame (a DefectMap or None); the fix-ups of all frames take one launch.
+            undistort: None, or one entry per frame (a LensDistortion or None); the analytic remaps take one launch."""
+            return self._load_packed_batch(images_data, 12, ids_format, defects, undistort)
 
-        def load_packed16_batch(self, images_data: List[torch.Tensor], defects=None) -> List[torch.Tensor]:
+        def load_packed16_batch(self, images_data: List[torch.Tensor], defects=None,
+                                undistort=None) -> List[torch.Tensor]:
             """The same for `load_packed16` (camera_isp.py:342-347)."""
-            return self._load_packed_batch(images_data, 16, False, defects)
+            return self._load_packed_batch(images_data, 16, False, defects, undistort)
+
+        def _batch_lenses(self, undistort, n, h, w):
+            """The per-frame lenses of a batch call, None for each frame without one; ValueError as _batch_defects."""
+            if undistort is None:
+                return [None] * n
+            if not isinstance(undistort, (list, tuple)):
+                raise ValueError(f"undistort must be None or a list with one entry per frame, got {type(undistort).__name__}")
+            if len(undistort) != n:
+                raise ValueError(f"undistort has {len(undistort)} entries for {n} frames")
+            return [self._check_lens(m, h, w) for m in undistort]
 
         def _batch_defects(self, defects, n, shape):
             """The per-frame maps of a batch call, None for each frame without one, all None for defects=None; ValueError
@@ -563,7 +627,7 @@ def camera_isp(name: str, dtype=types.f32):
                 raise ValueError(f"defects has {len(defects)} entries for {n} frames")
             return [_defects.check_defects(d, shape) for d in defects]
 
-        def _load_packed_batch(self, images_data, bits, ids_format, defects=None):
+        def _load_packed_batch(self, images_data, bits, ids_format, defects=None, undistort=None):
             _typecheck("images_data", images_data, list)
             if len(images_data) == 0:
                 return []
@@ -579,6 +643,19 @@ def camera_isp(name: str, dtype=types.f32):
             assert w % 2 == 0 and h % 2 == 0, "image must be even size"
             lv = self._levels(bits)
             maps = self._batch_defects(defects, len(images_data), (h, w))
+            lenses = self._batch_lenses(undistort, len(images_data), h, w)
+            if any(m is not None for m in lenses):
+                # lens distortion: the frames without a lens as the call without lenses, the others loaded at full
+                # resolution in one launch and remapped
+                plain = [i for i, m in enumerate(lenses) if m is None]
+                out = dict(zip(plain, self._load_packed_batch([images_data[i] for i in plain], bits, ids_format,
+                                                              [maps[i] for i in plain]) if plain else []))
+                rest = [i for i, m in enumerate(lenses) if m is not None]
+                srcs = [images_data[i].to(self.device).contiguous() for i in rest]
+                rgbs = self._load_full(srcs, h, w, bits, ids_format, lv, _native.shading_arg(self._shading),
+                                       [maps[i] for i in rest])
+                out.update(zip(rest, self._undistort(rgbs, [lenses[i] for i in rest], h, w)))
+                return [out[i] for i in range(len(images_data))]
             L = _native.lib()
             if self.resize_width > 0:
                 scale = self.resize_width / w
@@ -616,9 +693,9 @@ def camera_isp(name: str, dtype=types.f32):
                     _tag_subsample(rgb, sub, st)
             return rgbs
 
-        def load_packed16(self, image_data, defects=None):
+        def load_packed16(self, image_data, defects=None, undistort=None):
             """camera_isp.py:342-347."""
-            return self._load_packed(image_data, 16, False, defects)
+            return self._load_packed(image_data, 16, False, defects, undistort)
 
         @property
         def color_correct_matrix(self) -> Optional[np.ndarray]:
@@ -629,9 +706,11 @@ def camera_isp(name: str, dtype=types.f32):
                 return cc
             return None
 
-        def _process_image(self, cfa):
-            """camera_isp.py:371-373."""
+        def _process_image(self, cfa, lens=None):
+            """camera_isp.py:371-373; with a lens the full-resolution image is remapped at the resize geometry."""
             rgb = bayer.bayer_to_rgb(cfa, pattern=self._demosaic_pattern, correct_colors=self.color_correct_matrix)
+            if lens is not None:
+                return self._undistort([rgb], [lens], *cfa.shape)[0]
             return self.resize_image(rgb)
 
         def _metering_images(self, images, t, prev, stride=None):
@@ -752,7 +831,7 @@ def camera_isp(name: str, dtype=types.f32):
 
         def process_packed12(self, frames: List[torch.Tensor], gamma: float = 1.0, intensity: float = 1.0,
                              light_adapt: float = 1.0, color_adapt: float = 0.0, keep_images: bool = False,
-                             ids_format: bool = False, defects=None):
+                             ids_format: bool = False, defects=None, undistort=None):
             """Extension (not in the reference): one step of the reference's own bench in one call -
             `Processor.__call__` of bench/camera_isp.py:23-27:
 
@@ -768,7 +847,7 @@ def camera_isp(name: str, dtype=types.f32):
             keep_images=True returns `(outputs, images)`, the images holding what the reference leaves in them (p,
             camera_isp.py:211); by default only the outputs are returned, as the bench's Processor does.
             defects: None, or one entry per frame (a DefectMap or None); any map takes the two calls, the load with
-            `defects=`."""
+            `defects=`.  undistort: the same for lenses (a LensDistortion or None per frame)."""
             _typecheck("frames", frames, list)
             _typecheck("keep_images", keep_images, bool)
             for n, v in (("gamma", gamma), ("intensity", intensity), ("light_adapt", light_adapt),
@@ -783,9 +862,15 @@ def camera_isp(name: str, dtype=types.f32):
                     raise TypeError("frames must be (H, bytes) uint8 tensors")
                 maps = self._batch_defects(defects, len(frames), (f0.shape[0], f0.shape[1] * 2 // 3))
                 defects = maps if any(m is not None for m in maps) else None
+            if undistort is not None:                        # (lenses too)
+                if not (isinstance(f0, torch.Tensor) and f0.ndim == 2):
+                    raise TypeError("frames must be (H, bytes) uint8 tensors")
+                lenses = self._batch_lenses(undistort, len(frames), f0.shape[0], f0.shape[1] * 2 // 3)
+                undistort = lenses if any(m is not None for m in lenses) else None
             fused = (dtype is types.f16 and not ids_format and self.resize_width == 0 and self.scale is None
                      and self._shading is None                # (lens shading: the two calls below)
                      and defects is None                      # (defective pixels: the two calls below)
+                     and undistort is None                    # (lens distortion: the two calls below)
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8
                      and 1 <= len(frames) <= 64
                      and all(isinstance(f, torch.Tensor) and f.ndim == 2 and f.dtype == torch.uint8 and f.shape == f0.shape
@@ -803,7 +888,7 @@ def camera_isp(name: str, dtype=types.f32):
                     fused = bool(L.mi_isp_camera_group_fits(h, w, self._demosaic_pattern.value, dtype.code, 8) if lv is None
                                  else L.mi_isp_camera_group_fits_levels(h, w, self._demosaic_pattern.value, dtype.code, 8, lv))
             if not fused:
-                images = self.load_packed12_batch(frames, ids_format, defects=defects)
+                images = self.load_packed12_batch(frames, ids_format, defects=defects, undistort=undistort)
                 outputs = self.tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt)
                 return (outputs, images) if keep_images else outputs
             _raise_resident_faults(L, self.device)

@@ -2,6 +2,7 @@
 // library-wide plumbing (version, error string, workspace size).
 #include <stdarg.h>
 #include <stdlib.h>
+#include <cmath>
 
 #include "isp_elementwise.h"
 #include "isp_tile.h"
@@ -11,6 +12,7 @@
 #include "isp_mega_cam.h"
 #include "isp_stream_resize.h"
 #include "isp_defects.h"
+#include "isp_lens.h"
 #include <mutex>
 #include <atomic>
 
@@ -23,7 +25,7 @@ void mi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int mi_isp_version(void) { return 1400; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
+extern "C" int mi_isp_version(void) { return 1500; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
 extern "C" const char* mi_isp_last_error(void) { return g_err; }
 
 extern "C" int mi_isp_bayer_weights(int32_t out[4 * 13 * 3]) {
@@ -451,6 +453,103 @@ extern "C" int mi_isp_defects_fix_cfa(void* cfa, int H, int W, int work_dtype, c
   if (int rc = check_defects(defects, "defects_fix_cfa")) return rc;
   MI_REQUIRE((int64_t)defects->n <= (int64_t)H * W, "defects_fix_cfa: %d defects in a %dx%d frame", (int)defects->n, H, W);
   return dfx::launch_cfa(cfa, H, W, work_dtype, defects->coords_dev, defects->n, defects->mask_dev, (hipStream_t)stream);
+}
+
+// ---- lens distortion correction (mi_isp_lens) ------------------------------------------------------------
+static int check_remap_shape(int H, int W, int Hd, int Wd, int in_dtype, int out_dtype, const char* who) {
+  MI_REQUIRE(H > 0 && W > 0 && Hd >= 0 && Wd >= 0, "%s: bad lens shape %dx%d -> %dx%d", who, H, W, Hd, Wd);
+  MI_REQUIRE(H < (1 << 24) && W < (1 << 24), "%s: lens source %dx%d too large", who, H, W);
+  MI_REQUIRE((int64_t)Hd * Wd < ((int64_t)1 << 31) / 3, "%s: lens output %dx%d too large", who, Hd, Wd);
+  MI_REQUIRE(mi_valid_dtype(in_dtype) && mi_valid_dtype(out_dtype), "%s: bad lens dtype %d -> %d", who, in_dtype,
+             out_dtype);
+  return 0;
+}
+
+// the f32 model of a lens (every value rounded once from double; 1 / fx', 1 / fy' in double, then rounded)
+static int lens_model(const mi_isp_lens* l, lens::Model& m, const char* who) {
+  MI_REQUIRE(l, "%s: null lens", who);
+  MI_REQUIRE(l->n_dist == 4 || l->n_dist == 5 || l->n_dist == 8, "%s: lens takes 4, 5 or 8 distortion coefficients, "
+             "got %d", who, (int)l->n_dist);
+  MI_REQUIRE(l->border == MI_BORDER_CONSTANT || l->border == MI_BORDER_REPLICATE, "%s: bad lens border %d", who,
+             (int)l->border);
+  const double k[8] = {l->fx, l->fy, l->cx, l->cy, l->new_fx, l->new_fy, l->new_cx, l->new_cy};
+  for (double v : k) MI_REQUIRE(std::isfinite(v) && std::isfinite((float)v), "%s: lens camera matrix value %g is not finite", who, v);
+  for (int i = 0; i < l->n_dist; ++i)
+    MI_REQUIRE(std::isfinite(l->dist[i]) && std::isfinite((float)l->dist[i]), "%s: lens coefficient %d (%g) is not finite", who, i,
+               l->dist[i]);
+  MI_REQUIRE(l->fx > 0 && l->fy > 0 && l->new_fx > 0 && l->new_fy > 0 && (float)l->fx > 0.f && (float)l->fy > 0.f,
+             "%s: lens focal lengths must be positive (fx %g, fy %g, fx' %g, fy' %g)", who, l->fx, l->fy, l->new_fx,
+             l->new_fy);
+  const double ifx = 1.0 / l->new_fx, ify = 1.0 / l->new_fy;
+  MI_REQUIRE(std::isfinite((float)ifx) && std::isfinite((float)ify), "%s: lens focal length too small", who);
+  m = {};
+  m.fx = (float)l->fx; m.fy = (float)l->fy; m.cx = (float)l->cx; m.cy = (float)l->cy;
+  m.ncx = (float)l->new_cx; m.ncy = (float)l->new_cy; m.ifx = (float)ifx; m.ify = (float)ify;
+  m.k1 = (float)l->dist[0]; m.k2 = (float)l->dist[1]; m.p1 = (float)l->dist[2]; m.p2 = (float)l->dist[3];
+  m.k3 = l->n_dist >= 5 ? (float)l->dist[4] : 0.f;
+  m.rational = l->n_dist == 8;
+  if (m.rational) { m.k4 = (float)l->dist[5]; m.k5 = (float)l->dist[6]; m.k6 = (float)l->dist[7]; }
+  return 0;
+}
+
+static int undistort_impl(const void* const* src, void* const* dst, int n, int H, int W, int Hd, int Wd, float s0,
+                          float s1, int in_dtype, int out_dtype, const mi_isp_lens* const* lenses, void* stream,
+                          const char* who) {
+  MI_REQUIRE(n >= 0, "%s: negative lens frame count %d", who, n);
+  if (n == 0) return 0;
+  MI_REQUIRE(src && dst && lenses, "%s: null lens argument", who);
+  if (int rc = check_remap_shape(H, W, Hd, Wd, in_dtype, out_dtype, who)) return rc;
+  MI_REQUIRE(s0 > 0.f && s1 > 0.f && std::isfinite(s0) && std::isfinite(s1), "%s: lens output scale (%g, %g) must be positive", who,
+             s0, s1);
+  lens::Args a[2] = {};                                    // per border mode
+  for (int b = 0; b < 2; ++b) {
+    a[b].H = H; a[b].W = W; a[b].Hd = Hd; a[b].Wd = Wd; a[b].s0 = s0; a[b].s1 = s1;
+    a[b].intensity = (float)((double)mi_scale_factor(out_dtype) / (double)mi_scale_factor(in_dtype));
+  }
+  for (int i = 0; i < n; ++i) {                            // every check before the first launch
+    MI_REQUIRE(src[i] && dst[i], "%s: lens frame %d has a null buffer", who, i);
+    lens::Model m;
+    if (int rc = lens_model(lenses[i], m, who)) return rc;
+  }
+  if ((int64_t)Hd * Wd == 0) return 0;
+  for (int i = 0; i < n; ++i) {
+    lens::Args& g = a[lenses[i]->border];
+    lens::Cam& c = g.cam[g.n_cams++];
+    c.src = src[i]; c.dst = dst[i]; c.table = nullptr;
+    lens_model(lenses[i], c.m, who);
+    for (int b = 0; b < 2; ++b)
+      if (a[b].n_cams == lens::MAX_CAMS || (i == n - 1 && a[b].n_cams > 0)) {
+        if (int rc = lens::launch(a[b], in_dtype, out_dtype, false, b, (hipStream_t)stream)) return rc;
+        a[b].n_cams = 0;
+      }
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_undistort(const void* src, void* dst, int H, int W, int Hd, int Wd, float s0, float s1, int in_dtype,
+                                int out_dtype, const mi_isp_lens* lens, void* stream) {
+  MI_REQUIRE(lens, "undistort: null lens");
+  return undistort_impl(&src, &dst, 1, H, W, Hd, Wd, s0, s1, in_dtype, out_dtype, &lens, stream, "undistort");
+}
+
+extern "C" int mi_isp_undistort_batch(const void* const* src, void* const* dst, int n, int H, int W, int Hd, int Wd,
+                                      float s0, float s1, int in_dtype, int out_dtype, const mi_isp_lens* const* lenses,
+                                      void* stream) {
+  return undistort_impl(src, dst, n, H, W, Hd, Wd, s0, s1, in_dtype, out_dtype, lenses, stream, "undistort_batch");
+}
+
+extern "C" int mi_isp_remap(const void* src, void* dst, const float* map, int H, int W, int Hd, int Wd, int in_dtype,
+                            int out_dtype, int border, void* stream) {
+  MI_REQUIRE(src && dst && map, "remap: null lens argument");
+  if (int rc = check_remap_shape(H, W, Hd, Wd, in_dtype, out_dtype, "remap")) return rc;
+  MI_REQUIRE(border == MI_BORDER_CONSTANT || border == MI_BORDER_REPLICATE, "remap: bad lens border %d", border);
+  MI_REQUIRE(mi_aligned(map, 8), "remap: the lens table must be 8-byte aligned");
+  lens::Args a = {};
+  a.H = H; a.W = W; a.Hd = Hd; a.Wd = Wd; a.s0 = 1.f; a.s1 = 1.f;
+  a.intensity = (float)((double)mi_scale_factor(out_dtype) / (double)mi_scale_factor(in_dtype));
+  a.n_cams = 1;
+  a.cam[0].src = src; a.cam[0].dst = dst; a.cam[0].table = map;
+  return lens::launch(a, in_dtype, out_dtype, true, border, (hipStream_t)stream);
 }
 
 // ---- measurement aid: HIP events around each data pass, on the stream it runs on ---------------------

@@ -95,3 +95,50 @@ def scale_bilinear(src, scale, dtype=None):
     sw, sh = _scale2(scale)
     size = (int(np.float32(w) * np.float32(sw)), int(np.float32(h) * np.float32(sh)))
     return resize_bilinear(src, size, scale, dtype=dtype)
+
+
+def undistort(src, lens, size=None, scale=None, dtype=None):
+    """Lens distortion correction of an (H, W, 3) image (an extension; DESIGN.md 3, "Lens distortion"): every output pixel
+    sampled bilinearly at the source coordinates of `lens` (a lens.LensDistortion of an (H, W) frame), as
+    resize_bilinear samples.  size = (w, h) and scale (scalar or (row, col)) of the output as in resize_bilinear: both
+    None gives the source size at scale 1; a size alone takes scale (h / H, w / W); a scale alone takes size
+    (round(W * s_col), round(H * s_row)).  A table lens gives its table's size and takes no scale.  The container rule and
+    the dtype handling are resize_bilinear's."""
+    from . import lens as _lens
+    in_dtype = types.ti_type(src)
+    out_dtype = in_dtype if dtype is None else as_dtype(dtype)
+    dev = types.to_device(src)
+    assert dev.ndim == 3 and dev.shape[2] == 3, "image must be (H, W, 3)"
+    Hs, Ws = dev.shape[:2]
+    if not isinstance(lens, _lens.LensDistortion):
+        raise ValueError(f"lens must be a LensDistortion, got {type(lens).__name__}")
+    if lens.is_table:
+        if scale is not None:
+            raise ValueError("a lens table gives its own output size: it takes no scale")
+        Hd, Wd = lens.table_shape
+        if size is not None and (int(size[1]), int(size[0])) != (Hd, Wd):
+            raise ValueError(f"size {tuple(size)} is not the lens table's ({Wd}, {Hd})")
+        s0 = s1 = 1.0
+    elif size is None:
+        s0, s1 = (1.0, 1.0) if scale is None else _lens._scale2(scale)
+        Hd, Wd = (Hs, Ws) if scale is None else (round(Hs * s0), round(Ws * s1))
+    else:
+        Wd, Hd = int(size[0]), int(size[1])
+        s0, s1 = (Hd / Hs, Wd / Ws) if scale is None else _lens._scale2(scale)
+        if Wd < 0 or Hd < 0:
+            raise ValueError(f"size {tuple(size)} must not be negative")
+    _lens.check_lens(lens, (Hs, Ws), (Hd, Wd))
+    dst = torch.empty((Hd, Wd, 3), dtype=out_dtype.torch, device=dev.device)
+    if Hd * Wd:
+        if not lens.is_table:
+            _lens._scale2((s0, s1))
+        _lens.apply([lens], [dev], [dst], Hs, Ws, Hd, Wd, s0, s1, in_dtype.code, out_dtype.code, dev.device)
+    return types.from_device(dst, src)
+
+
+def remap(src, map_xy, dtype=None, border="constant"):
+    """The table form of undistort: `map_xy` an (Hd, Wd, 2) f32 array of source coordinates (us, vs) (OpenCV's map_x /
+    map_y order) for the (H, W, 3) image src; out-of-frame coordinates read 0 (border="constant") or the edge
+    ("replicate").  For repeated use keep a lens.LensDistortion.from_map, which caches the table on the device."""
+    from . import lens as _lens
+    return undistort(src, _lens.LensDistortion.from_map(map_xy, tuple(src.shape[:2]), border), dtype=dtype)

@@ -13,6 +13,7 @@ from __future__ import annotations
 import argparse
 import re
 import struct
+import zipfile
 import zlib
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -123,6 +124,38 @@ def load_defect_pixels(directory, cameras: Sequence[Path], width: int) -> Dict[s
     return maps
 
 
+def load_lens_distortion(directory, cameras: Sequence[Path]) -> Dict[str, dict]:
+    """--lens-distortion: `directory/<camera folder name>.npz` holds one camera's calibration: `K` (3 x 3), `dist` (4, 5 or
+    8 coefficients in OpenCV order) and optionally `new_K`; a camera without a file is not undistorted.  Checked before any
+    frame is read: ValueError for a file that is no such archive, holds other arrays or invalid values, or names no camera
+    of the scan.  Returns the keyword arguments of lens.LensDistortion per camera (the frame shape is added once known)."""
+    from ..lens import LensDistortion
+    directory = Path(directory)
+    if not directory.is_dir():
+        raise FileNotFoundError(f"--lens-distortion: {directory} does not exist or is not a directory")
+    names = {c.name for c in cameras}
+    lenses = {}
+    for f in sorted(directory.iterdir(), key=lambda p: natural_key(p.name)):
+        if f.suffix != ".npz":
+            continue
+        if f.stem not in names:
+            raise ValueError(f"--lens-distortion: {f.name} names no camera of the scan ({sorted(names)})")
+        try:
+            with np.load(f, allow_pickle=False) as z:
+                arrays = {k: z[k] for k in z.files}
+        except (OSError, ValueError, zipfile.BadZipFile) as e:
+            raise ValueError(f"--lens-distortion: {f.name} is not a readable .npz archive ({e})") from None
+        if not {"K", "dist"} <= set(arrays) or not set(arrays) <= {"K", "dist", "new_K"}:
+            raise ValueError(f"--lens-distortion: {f.name} must hold K, dist and optionally new_K, got {sorted(arrays)}")
+        kw = {"K": arrays["K"], "dist": arrays["dist"], "new_K": arrays.get("new_K")}
+        try:
+            LensDistortion(shape=(2, 2), **kw)                         # (the calibration's own checks)
+        except ValueError as e:
+            raise ValueError(f"--lens-distortion: {f.name}: {e}") from None
+        lenses[f.stem] = kw
+    return lenses
+
+
 def build_parser() -> argparse.ArgumentParser:
     """The argument surface of scripts/tonemap_scan.py:104-128 (+ --device, --ids_format)."""
     from ..interpolate import ImageTransform
@@ -156,6 +189,9 @@ def build_parser() -> argparse.ArgumentParser:
     # defective pixels (an extension): a directory of <camera folder name>.npy files, (N, 2) int (row, col) each
     # (defects.find_defects makes one from dark or flat frames)
     tone.add_argument("--defect-pixels", dest="defect_pixels", type=Path, default=None)
+    # lens distortion (an extension): a directory of <camera folder name>.npz files holding K, dist (OpenCV order) and
+    # optionally new_K
+    tone.add_argument("--lens-distortion", dest="lens_distortion", type=Path, default=None)
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -167,6 +203,7 @@ def main(argv=None) -> int:
     from functools import partial
     from .. import bayer, camera_isp, ingest
     from ..defects import DefectMap
+    from ..lens import LensDistortion
     args = build_parser().parse_args(argv)
     if args.scan is None and args.images is None:
         raise ValueError("No --scan or --images specified")
@@ -181,7 +218,9 @@ def main(argv=None) -> int:
         camera_isp._check_shading(shading)                          # (also before any frame is read)
     index = ScanIndex.of_scan(args.scan) if args.scan is not None else ScanIndex.of_directory(args.images)
     coords = {} if args.defect_pixels is None else load_defect_pixels(args.defect_pixels, index.cameras, args.width)
+    calib = {} if args.lens_distortion is None else load_lens_distortion(args.lens_distortion, index.cameras)
     maps = None                                                     # one DefectMap per camera, once the height is known
+    lenses = None                                                   # (and one LensDistortion)
     print(f"{len(index.cameras)} camera(s) {[c.name for c in index.cameras]}, {len(index.frames)} frame(s) each")
     device = torch.device(args.device)
     isp = camera_isp.Camera32(bayer.BayerPattern.RGGB, transform=args.transform, moving_alpha=args.moving_alpha,
@@ -198,7 +237,9 @@ def main(argv=None) -> int:
         if maps is None:
             shape = (frames[0].shape[0], args.width)
             maps = [DefectMap(coords[c.name], shape) if c.name in coords else None for c in index.cameras]
-        images = [isp.load_packed12(f, ids_format=args.ids_format, defects=m) for f, m in zip(frames, maps)]
+            lenses = [LensDistortion(shape=shape, **calib[c.name]) if c.name in calib else None for c in index.cameras]
+        images = [isp.load_packed12(f, ids_format=args.ids_format, defects=m, undistort=ln)
+                  for f, m, ln in zip(frames, maps, lenses)]
         outputs = isp.tonemap_reinhard(images, gamma=args.gamma, intensity=args.intensity,
                                        color_adapt=args.color_adapt, light_adapt=args.light_adapt)
         if args.write is not None:
