@@ -331,6 +331,34 @@ int mi_isp_undistort_batch(const void* const* src_host, void* const* dst_host, i
                            void* stream);
 int mi_isp_remap(const void* src_dev, void* dst_dev, const float* map_dev, int H, int W, int Hd, int Wd, int in_dtype,
                  int out_dtype, int border, void* stream);
+/* ---- automatic white balance (gray world; DESIGN.md 3, "Auto white balance") ----------------------------------------
+ * Statistics: a quad is the 2x2 block at raw rows 2a, 2a+1 and columns 2b, 2b+1, sampled when a % stride == 0 and
+ * b % stride == 0.  x of each pixel is the f32 value the loader rounds to the work dtype without shading (the decode and
+ * levels of a packed source; the conversion of mi_isp_load_convert_shading for a CFA), xs = f32(x * g) with g the
+ * pixel's gain under shading_host (1 for NULL).  A quad is kept when all four x < clip and max(x) >= floor (f32 compares:
+ * a NaN quad drops out); it adds u64(rint(min(max(xs, 0), 2^15) * 2^24)) to P[s] of each site s = (row & 1) * 2 +
+ * (col & 1), and 1 to n.  pending_dev holds P[0..3], n as u64 and is added to with integer atomics (exact, order-free).
+ *  - mi_isp_awb_stats_packed: n packed frames (12 or 16 bits, as mi_isp_load_packed_batch_shading) in one launch per 32.
+ *  - mi_isp_awb_stats_cfa: one H x W CFA of mode MI_LOAD_16U / 32F / 16F (levels with MI_LOAD_16U only).
+ * Update: gathered_dev holds world rows of 5 i64 (P, n; the ranks' pending rows, or pending_dev itself); their sum with
+ * n == 0 changes nothing, otherwise in f64: m_s = (P_s * 2^-24) / n, R = m of the pattern's red site, G = the mean of
+ * its two green sites' m, B likewise; S = c + t' * (S_prev - c) with t' = t after the first update (state_dev[3] != 0)
+ * and 0 before; g_R = f32(clamp(S_G / S_R, 1/8, 8)), g_B the same, g_G = 1, a gain whose S_c or S_G is <= 0 kept.
+ * pending_dev is zeroed.  state_dev: S_R, S_G, S_B, valid (f64); gains_dev: g_R, g_G, g_B (f32).
+ * Both the update and mi_isp_awb_rebuild write effective_dev = E[s][i][j] = f32(U[s'][i][j] * g_colour(s)), 4 x Gh x Gw
+ * f32, with U the user's grid (s' = s for 4 sites, 0 for 1) or a 2 x 2 grid of ones for NULL.  One workgroup each.
+ * Host-side checks (error text names "awb"): NULL pointers, shapes, bits, modes, levels, grids, stride >= 1,
+ * 0 < floor < clip (finite), world >= 1, pattern, a finite t. */
+int mi_isp_awb_stats_packed(const uint8_t* const* packed_host, int n, int H, int W, int bits, int ids_format,
+                            const mi_isp_levels* levels_host, const mi_isp_shading* shading_host, float clip,
+                            float floor_, int stride, void* pending_dev, void* stream);
+int mi_isp_awb_stats_cfa(const void* cfa_dev, int H, int W, int mode, const mi_isp_levels* levels_host,
+                         const mi_isp_shading* shading_host, float clip, float floor_, int stride, void* pending_dev,
+                         void* stream);
+int mi_isp_awb_update(const int64_t* gathered_dev, int world, void* pending_dev, int pattern, double t, double* state_dev,
+                      float* gains_dev, const mi_isp_shading* user_host, float* effective_dev, void* stream);
+int mi_isp_awb_rebuild(int pattern, float* gains_dev, const mi_isp_shading* user_host, float* effective_dev,
+                       void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==

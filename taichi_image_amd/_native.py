@@ -110,6 +110,12 @@ SIGNATURES = {
     "mi_isp_undistort_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
                                        c_int, POINTER(_P), _P]),
     "mi_isp_remap": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "mi_isp_awb_stats_packed": (c_int, [POINTER(_P), c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading),
+                                        c_float, c_float, c_int, _P, _P]),
+    "mi_isp_awb_stats_cfa": (c_int, [_P, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading), c_float, c_float, c_int,
+                                     _P, _P]),
+    "mi_isp_awb_update": (c_int, [_P, c_int, _P, c_int, c_double, _P, _P, POINTER(Shading), _P, _P]),
+    "mi_isp_awb_rebuild": (c_int, [c_int, _P, POINTER(Shading), _P, _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,

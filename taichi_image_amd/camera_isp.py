@@ -22,6 +22,7 @@ import torch
 from . import _native, bayer, interpolate, packed, types
 from . import defects as _defects
 from . import lens as _lens
+from . import white_balance as _wb
 from . import distributed as _dist
 
 default_cc = np.array([      # camera_isp.py:230-234
@@ -274,7 +275,8 @@ def camera_isp(name: str, dtype=types.f32):
                      reference_quirks: bool = False,
                      black_level=None,
                      white_level: Optional[int] = None,
-                     lens_shading=None):
+                     lens_shading=None,
+                     auto_white_balance=False):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -287,6 +289,9 @@ def camera_isp(name: str, dtype=types.f32):
             assert scale is None or resize_width == 0, "Cannot specify both scale and resize_width"
             _check_levels(black_level, white_level)
             shading = None if lens_shading is None else _check_shading(lens_shading)
+            awb = _wb.check_auto_white_balance(auto_white_balance)
+            if awb is not None:
+                _wb.check_seed(white_balance)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -319,6 +324,16 @@ def camera_isp(name: str, dtype=types.f32):
             self._shading_retired = []
             # one-process-per-GPU sharding: statistics are all-reduced over this group (RCCL)
             self.process_group = process_group
+            # auto white balance (an extension): the AutoWhiteBalance in effect, or None.  On, it owns four device tensors:
+            # the pending statistics (5 i64: the sums of the four CFA sites and the quad count), the gray-world state (4
+            # f64: S_R, S_G, S_B, valid), the gains (3 f32) and the effective grid E (4 x Gh x Gw f32) that the loaders
+            # apply in place of the user's grid.  Replaced or dropped tensors stay referenced in _awb_retired for the
+            # ISP's lifetime, as _shading_retired.  DESIGN.md 3, "Auto white balance".
+            self._awb = None
+            self._awb_E = None
+            self._awb_retired = []
+            if awb is not None:
+                self._awb_seed(awb)
 
         @property
         def _demosaic_pattern(self):
@@ -330,16 +345,23 @@ def camera_isp(name: str, dtype=types.f32):
                 white_balance: Optional[np.ndarray] = None,
                 color_correction: Optional[np.ndarray] = None,
                 transform: Optional[interpolate.ImageTransform] = None,
-                black_level=None, white_level: Optional[int] = None, lens_shading=None):
+                black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
             graph reads the new ones at its next replay); a grid of another shape gets a new device tensor and the old
-            one stays allocated while the ISP lives."""
+            one stays allocated while the ISP lives.
+            auto_white_balance (the extension): None leaves it; False turns it off (the ISP then computes exactly what
+            one that never had it does); True or an AutoWhiteBalance turns it on and seeds it: gains f32(white_balance),
+            no state, no pending statistics.  white_balance= while it is on seeds it again; lens_shading= while it is on
+            rebuilds the effective grid from the new grid and the current gains on the device."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
             shading = None if lens_shading is None or lens_shading is False else _check_shading(lens_shading)
+            awb = self._awb if auto_white_balance is None else _wb.check_auto_white_balance(auto_white_balance)
+            if awb is not None and (auto_white_balance is not None or white_balance is not None):
+                _wb.check_seed(self.white_balance if white_balance is None else white_balance)
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -380,6 +402,87 @@ def camera_isp(name: str, dtype=types.f32):
                     if self._shading is not None:
                         self._shading_retired.append(self._shading)
                     self._shading = new.to(self.device)
+            if auto_white_balance is not None:
+                if awb is None:
+                    self._awb_off()
+                else:
+                    self._awb_seed(awb)
+            elif self._awb is not None and white_balance is not None:
+                self._awb_seed(self._awb)
+            elif self._awb is not None and lens_shading is not None:
+                self._awb_rebuild()
+
+        def _awb_seed(self, awb):
+            """AWB on with settings awb: the gains f32(white_balance), the state and the pending sums cleared (in place
+            when it was on already), E rebuilt."""
+            seed = torch.from_numpy(_wb.check_seed(self.white_balance))
+            if self._awb is None:
+                self._awb_pending = torch.zeros(5, dtype=torch.int64, device=self.device)
+                self._awb_state = torch.zeros(4, dtype=torch.float64, device=self.device)
+                self._awb_gains = seed.to(self.device)
+            else:
+                with torch.cuda.device(self.device):
+                    self._awb_pending.zero_()
+                    self._awb_state.zero_()
+                    self._awb_gains.copy_(seed)
+            self._awb = awb
+            self._awb_rebuild()
+
+        def _awb_off(self):
+            if self._awb is not None:
+                self._awb_retired += [self._awb_pending, self._awb_state, self._awb_gains, self._awb_E]
+            self._awb = None
+            self._awb_E = None
+
+        def _awb_rebuild(self):
+            """E from the user's grid and the current gains, on the device (a new tensor when its shape changes)."""
+            shape = (4,) + (tuple(self._shading.shape[1:]) if self._shading is not None else (2, 2))
+            if self._awb_E is None or tuple(self._awb_E.shape) != shape:
+                if self._awb_E is not None:
+                    self._awb_retired.append(self._awb_E)
+                self._awb_E = torch.empty(shape, dtype=torch.float32, device=self.device)
+            _native.check(_native.lib().mi_isp_awb_rebuild(
+                self._demosaic_pattern.value, self._awb_gains.data_ptr(), _native.shading_arg(self._shading),
+                self._awb_E.data_ptr(), _native.stream_ptr(self.device)))
+
+        def _applied_shading(self):
+            """The grid the loaders apply: E with AWB on, else the user's grid (or None)."""
+            return self._awb_E if self._awb is not None else self._shading
+
+        def _awb_stats_packed(self, images_data, bits, ids_format):
+            """Add the AWB statistics of packed frames (one shape) to the pending sums; nothing with AWB off."""
+            if self._awb is None or not images_data:
+                return
+            srcs = [d.to(self.device).contiguous() for d in images_data]
+            h = srcs[0].shape[0]
+            w = srcs[0].shape[1] * 2 // 3 if bits == 12 else srcs[0].shape[1] // 2
+            _native.check(_native.lib().mi_isp_awb_stats_packed(
+                _native.ptr_array(srcs), len(srcs), h, w, bits, int(bool(ids_format)), self._levels(bits),
+                _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor), int(self._awb.stride),
+                self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
+
+        @property
+        def auto_white_balance(self):
+            """The AutoWhiteBalance in effect, or None."""
+            return self._awb
+
+        @property
+        def white_balance_gains(self) -> Optional[torch.Tensor]:
+            """The AWB gains (g_R, g_G, g_B), a (3,) f32 device tensor the loaders apply from the next load on (do not
+            write it), or None with AWB off."""
+            return self._awb_gains if self._awb is not None else None
+
+        def update_white_balance(self):
+            """One AWB update from the statistics of every load since the last one (all-gathered over process_group):
+            the gray-world state, the gains and E move on the device, the pending sums are cleared.  update_metering (so
+            every tonemap and process_packed12) runs it; a no-op with AWB off.  No host synchronisation without a group."""
+            if self._awb is None:
+                return
+            gathered = _dist.all_gather_rows(self._awb_pending, self.process_group)
+            _native.check(_native.lib().mi_isp_awb_update(
+                gathered.data_ptr(), gathered.shape[0], self._awb_pending.data_ptr(), self._demosaic_pattern.value,
+                float(1.0 - self.moving_alpha), self._awb_state.data_ptr(), self._awb_gains.data_ptr(),
+                _native.shading_arg(self._shading), self._awb_E.data_ptr(), _native.stream_ptr(self.device)))
 
         @property
         def lens_shading(self) -> Optional[torch.Tensor]:
@@ -419,7 +522,7 @@ def camera_isp(name: str, dtype=types.f32):
                                  "load_16f / load_32f take normalised values")
             src = image.to(self.device).contiguous()
             cfa = torch.empty(image.shape, dtype=torch_dtype, device=self.device)
-            sh = _native.shading_arg(self._shading)
+            sh = _native.shading_arg(self._applied_shading())
             if sh is not None:
                 _native.check(_native.lib().mi_isp_load_convert_shading(src.data_ptr(), cfa.data_ptr(), image.shape[0],
                                                                         image.shape[1], mode, dtype.code, lv, sh,
@@ -435,6 +538,11 @@ def camera_isp(name: str, dtype=types.f32):
                 _native.check(_native.lib().mi_isp_defects_fix_cfa(cfa.data_ptr(), image.shape[0], image.shape[1],
                                                                    dtype.code, dm._arg(self.device),
                                                                    _native.stream_ptr(self.device)))
+            if self._awb is not None:                    # auto white balance: the statistics of the source
+                _native.check(_native.lib().mi_isp_awb_stats_cfa(
+                    src.data_ptr(), image.shape[0], image.shape[1], mode, lv, _native.shading_arg(self._shading),
+                    float(self._awb.clip), float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(),
+                    _native.stream_ptr(self.device)))
             return self._process_image(cfa, lens)
 
         def load_16u(self, image, defects=None, undistort=None):
@@ -533,15 +641,15 @@ def camera_isp(name: str, dtype=types.f32):
             lens = self._check_lens(undistort, h, w)
             src = image_data.to(self.device).contiguous()
             if lens is not None:                         # lens distortion: a full-resolution load, then the remap
-                rgb = self._load_full([src], h, w, bits, ids_format, lv, _native.shading_arg(self._shading), [dm])
+                rgb = self._load_full([src], h, w, bits, ids_format, lv, _native.shading_arg(self._applied_shading()), [dm])
                 return self._undistort(rgb, [lens], h, w)[0]
             L = _native.lib()
             # with levels: the same calls through their *_levels twins (the same kernels' level-taking instantiations)
             load = L.mi_isp_load_packed if lv is None else (lambda *a: L.mi_isp_load_packed_levels(*a[:-1], lv, a[-1]))
             load_metered = (L.mi_isp_load_packed_metered if lv is None
                             else (lambda *a: L.mi_isp_load_packed_metered_levels(*a[:-1], lv, a[-1])))
-            sh = _native.shading_arg(self._shading)
-            if sh is not None:                           # lens shading: the *_shading twins (levels or NULL)
+            sh = _native.shading_arg(self._applied_shading())
+            if sh is not None:                           # lens shading (or AWB): the *_shading twins (levels or NULL)
                 load = lambda *a: L.mi_isp_load_packed_shading(*a[:-1], lv, sh, a[-1])   # noqa: E731
                 load_metered = lambda *a: L.mi_isp_load_packed_metered_shading(*a[:-1], lv, sh, a[-1])   # noqa: E731
             # camera_isp.py:302-312: output size and scale of resize_image
@@ -590,7 +698,9 @@ def camera_isp(name: str, dtype=types.f32):
             defects (an extension): None or the DefectMap of this sensor ("Defective pixels").
             undistort (an extension): None or the lens.LensDistortion of this camera ("Lens distortion"): the
             frame is loaded at full resolution, then remapped at the resize geometry (the fused resize is not used)."""
-            return self._load_packed(image_data, 12, ids_format, defects, undistort)
+            rgb = self._load_packed(image_data, 12, ids_format, defects, undistort)
+            self._awb_stats_packed([image_data], 12, ids_format)
+            return rgb
 
         def load_packed12_batch(self, images_data: List[torch.Tensor], ids_format=False,
                                 defects=None, undistort=None) -> List[torch.Tensor]:
@@ -599,12 +709,16 @@ def camera_isp(name: str, dtype=types.f32):
             for bit, without the other launches' dispatch, table build and drain (config 3: 43.0 -> 39.5 us per frame).
             defects: None, or one entry per frame (a DefectMap or None); the fix-ups of all frames take one launch.
             undistort: None, or one entry per frame (a LensDistortion or None); the analytic remaps take one launch."""
-            return self._load_packed_batch(images_data, 12, ids_format, defects, undistort)
+            rgbs = self._load_packed_batch(images_data, 12, ids_format, defects, undistort)
+            self._awb_stats_packed(images_data, 12, ids_format)
+            return rgbs
 
         def load_packed16_batch(self, images_data: List[torch.Tensor], defects=None,
                                 undistort=None) -> List[torch.Tensor]:
             """The same for `load_packed16` (camera_isp.py:342-347)."""
-            return self._load_packed_batch(images_data, 16, False, defects, undistort)
+            rgbs = self._load_packed_batch(images_data, 16, False, defects, undistort)
+            self._awb_stats_packed(images_data, 16, False)
+            return rgbs
 
         def _batch_lenses(self, undistort, n, h, w):
             """The per-frame lenses of a batch call, None for each frame without one; ValueError as _batch_defects."""
@@ -652,7 +766,7 @@ def camera_isp(name: str, dtype=types.f32):
                                                               [maps[i] for i in plain]) if plain else []))
                 rest = [i for i, m in enumerate(lenses) if m is not None]
                 srcs = [images_data[i].to(self.device).contiguous() for i in rest]
-                rgbs = self._load_full(srcs, h, w, bits, ids_format, lv, _native.shading_arg(self._shading),
+                rgbs = self._load_full(srcs, h, w, bits, ids_format, lv, _native.shading_arg(self._applied_shading()),
                                        [maps[i] for i in rest])
                 out.update(zip(rest, self._undistort(rgbs, [lenses[i] for i in rest], h, w)))
                 return [out[i] for i in range(len(images_data))]
@@ -678,7 +792,7 @@ def camera_isp(name: str, dtype=types.f32):
             args = (_native.ptr_array(srcs), _native.ptr_array(rgbs), None if subs is None else _native.ptr_array(subs),
                     len(srcs), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
                     _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, float(scale) if fused else 0.0, st)
-            sh = _native.shading_arg(self._shading)
+            sh = _native.shading_arg(self._applied_shading())
             if sh is not None:
                 _native.check(L.mi_isp_load_packed_batch_shading(*args, lv, sh, _native.stream_ptr(self.device)))
             elif lv is None:
@@ -695,14 +809,18 @@ def camera_isp(name: str, dtype=types.f32):
 
         def load_packed16(self, image_data, defects=None, undistort=None):
             """camera_isp.py:342-347."""
-            return self._load_packed(image_data, 16, False, defects, undistort)
+            rgb = self._load_packed(image_data, 16, False, defects, undistort)
+            self._awb_stats_packed([image_data], 16, False)
+            return rgb
 
         @property
         def color_correct_matrix(self) -> Optional[np.ndarray]:
-            """camera_isp.py:360-369: cc with column j scaled by white_balance[j]."""
+            """camera_isp.py:360-369: cc with column j scaled by white_balance[j].  With auto white balance on, cc as it
+            is: the AWB gains are applied in the raw domain instead."""
             if self.correct_colors:
                 cc = self.color_correction.copy()
-                cc[:, :3] *= self.white_balance
+                if self._awb is None:
+                    cc[:, :3] *= self.white_balance
                 return cc
             return None
 
@@ -767,6 +885,7 @@ def camera_isp(name: str, dtype=types.f32):
                 self.metrics = self._metering_images(images, 0.0, initial)
             else:
                 self.metrics = self._metering_images(images, (1.0 - self.moving_alpha), self.metrics)
+            self.update_white_balance()                  # (auto white balance: a no-op when off)
 
         def tonemap_only(self, image, metrics, gamma, intensity, light_adapt, color_adapt):
             """camera_isp.py:387-390."""
@@ -840,7 +959,7 @@ def camera_isp(name: str, dtype=types.f32):
 
             with the same u8 outputs and the same metering state afterwards, bit for bit.  For a full-resolution
             Camera16 group that fits the chip (`mi_isp_camera_group_fits`: 4096 x 3072 on MI355X, metering stride 8, no
-            resize, no orientation transform, no lens shading grid, single process, every packed frame 4-byte aligned) the
+            resize, no orientation transform, no lens shading grid, no auto white balance, single process, every packed frame 4-byte aligned) the
             loaded images never exist in memory: the metering reads a subsample demosaiced straight from the packed frames, and ONE persistent
             launch takes every camera from packed bytes to its u8 image (csrc/isp_mega_cam.h).  Everything else takes the
             two calls above.
@@ -868,7 +987,7 @@ def camera_isp(name: str, dtype=types.f32):
                 lenses = self._batch_lenses(undistort, len(frames), f0.shape[0], f0.shape[1] * 2 // 3)
                 undistort = lenses if any(m is not None for m in lenses) else None
             fused = (dtype is types.f16 and not ids_format and self.resize_width == 0 and self.scale is None
-                     and self._shading is None                # (lens shading: the two calls below)
+                     and self._applied_shading() is None      # (lens shading or AWB: the two calls below)
                      and defects is None                      # (defective pixels: the two calls below)
                      and undistort is None                    # (lens distortion: the two calls below)
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8

@@ -13,6 +13,7 @@
 #include "isp_stream_resize.h"
 #include "isp_defects.h"
 #include "isp_lens.h"
+#include "isp_awb.h"
 #include <mutex>
 #include <atomic>
 
@@ -25,7 +26,7 @@ void mi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int mi_isp_version(void) { return 1500; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
+extern "C" int mi_isp_version(void) { return 1600; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
 extern "C" const char* mi_isp_last_error(void) { return g_err; }
 
 extern "C" int mi_isp_bayer_weights(int32_t out[4 * 13 * 3]) {
@@ -550,6 +551,106 @@ extern "C" int mi_isp_remap(const void* src, void* dst, const float* map, int H,
   a.n_cams = 1;
   a.cam[0].src = src; a.cam[0].dst = dst; a.cam[0].table = map;
   return lens::launch(a, in_dtype, out_dtype, true, border, (hipStream_t)stream);
+}
+
+// ---- automatic white balance (isp_awb.h; DESIGN.md 3, "Auto white balance") ---------------------------------------
+static int awb_filter(awb::Stats& s, int H, int W, float clip, float floor_, int stride, void* pending, const char* who) {
+  MI_REQUIRE(pending, "%s: null awb pending buffer", who);
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad shape %dx%d", who, H, W);
+  MI_REQUIRE(stride >= 1, "%s: awb stride %d < 1", who, stride);
+  MI_REQUIRE(std::isfinite(clip) && std::isfinite(floor_) && 0.f < floor_ && floor_ < clip,
+             "%s: awb needs 0 < floor < clip, both finite (floor %g, clip %g)", who, (double)floor_, (double)clip);
+  s.H = H; s.W = W; s.stride = stride; s.clip = clip; s.floor = floor_;
+  s.pending = static_cast<unsigned long long*>(pending);
+  return 0;
+}
+
+extern "C" int mi_isp_awb_stats_packed(const uint8_t* const* packed, int n, int H, int W, int bits, int ids_format,
+                                       const mi_isp_levels* lv, const mi_isp_shading* sh, float clip, float floor_,
+                                       int stride, void* pending, void* stream) {
+  const char* who = "awb_stats_packed";
+  MI_REQUIRE(packed || n == 0, "%s: null frame list", who);
+  MI_REQUIRE(n >= 0, "%s: negative frame count", who);
+  for (int i = 0; i < n; ++i) MI_REQUIRE(packed[i], "%s: frame %d is null", who, i);
+  MI_REQUIRE(bits == 12 || bits == 16, "%s: bits must be 12 or 16, got %d", who, bits);
+  MI_REQUIRE(H % 2 == 0 && W % 2 == 0, "%s: image must be even size, got %dx%d", who, H, W);
+  awb::PackedArgs a = {};
+  if (int rc = awb_filter(a.s, H, W, clip, floor_, stride, pending, who)) return rc;
+  tile::Params p = {};
+  p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
+  if (int rc = apply_levels(p, lv, bits, who)) return rc;
+  for (int s = 0; s < 4; ++s) {                       // the per-site decode of the shading path (apply_levels_shading)
+    a.s.black[s] = p.levels ? p.lv_black[s] : 0;
+    a.s.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
+  }
+  if (int rc = apply_shading(a.s, sh, H, W, who)) return rc;
+  a.bits = bits; a.ids = bits == 12 && ids_format;
+  for (int i0 = 0; i0 < n; i0 += awb::MAX_FRAMES) {
+    a.n_frames = n - i0 < awb::MAX_FRAMES ? n - i0 : awb::MAX_FRAMES;
+    for (int i = 0; i < a.n_frames; ++i) a.src[i] = packed[i0 + i];
+    if (int rc = awb::launch_packed(a, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_awb_stats_cfa(const void* cfa, int H, int W, int mode, const mi_isp_levels* lv,
+                                    const mi_isp_shading* sh, float clip, float floor_, int stride, void* pending,
+                                    void* stream) {
+  const char* who = "awb_stats_cfa";
+  MI_REQUIRE(cfa, "%s: null CFA", who);
+  MI_REQUIRE(mode >= MI_LOAD_16U && mode <= MI_LOAD_16F, "%s: bad mode %d", who, mode);
+  awb::Stats s = {};
+  if (int rc = awb_filter(s, H, W, clip, floor_, stride, pending, who)) return rc;
+  if (lv) {                                           // mi_isp_load_convert_shading's levels: k[] holds the denominators
+    MI_REQUIRE(mode == MI_LOAD_16U, "%s: levels apply to u16 codes only (mode %d)", who, mode);
+    MI_REQUIRE(lv->white > 0 && lv->white <= 65535, "%s: white level %d outside (0, 65535]", who, (int)lv->white);
+    for (int k = 0; k < 4; ++k) {
+      MI_REQUIRE(lv->black[k] >= 0 && lv->black[k] < lv->white, "%s: black level %d of site %d outside [0, white = %d)",
+                 who, (int)lv->black[k], k, (int)lv->white);
+      s.black[k] = lv->black[k];
+      s.k[k] = (float)(lv->white - lv->black[k]);
+    }
+    s.has_levels = 1;
+  }
+  if (int rc = apply_shading(s, sh, H, W, who)) return rc;
+  return awb::launch_cfa(s, cfa, mode, (hipStream_t)stream);
+}
+
+// the colour (0 R, 1 G, 2 B) of each CFA site under a demosaic pattern, and the user grid of E
+static int awb_grid(awb::Update& u, int pattern, const mi_isp_shading* user, float* effective, const char* who) {
+  static const int colours[4][4] = {{0, 1, 1, 2}, {1, 0, 2, 1}, {1, 2, 0, 1}, {2, 1, 1, 0}};   // RGGB GRBG GBRG BGGR
+  MI_REQUIRE(pattern >= MI_RGGB && pattern <= MI_BGGR, "%s: bad pattern %d", who, pattern);
+  MI_REQUIRE(effective, "%s: null awb effective grid", who);
+  for (int s = 0; s < 4; ++s) u.site_colour[s] = colours[pattern][s];
+  u.effective = effective;
+  if (!user) { u.user = nullptr; u.user_sites = 1; u.gh = 2; u.gw = 2; return 0; }
+  tile::Params p = {};
+  if (int rc = apply_shading(p, user, 2, 2, who)) return rc;
+  u.user = user->gains_dev; u.user_sites = user->sites; u.gh = user->grid_h; u.gw = user->grid_w;
+  return 0;
+}
+
+extern "C" int mi_isp_awb_update(const int64_t* gathered, int world, void* pending, int pattern, double t, double* state,
+                                 float* gains, const mi_isp_shading* user, float* effective, void* stream) {
+  const char* who = "awb_update";
+  MI_REQUIRE(gathered && pending && state && gains, "%s: null awb buffer", who);
+  MI_REQUIRE(world >= 1, "%s: awb world %d < 1", who, world);
+  MI_REQUIRE(std::isfinite(t), "%s: awb t must be finite", who);
+  awb::Update u = {};
+  if (int rc = awb_grid(u, pattern, user, effective, who)) return rc;
+  u.gathered = reinterpret_cast<const long long*>(gathered); u.world = world;
+  u.pending = static_cast<unsigned long long*>(pending);
+  u.t = t; u.state = state; u.gains = gains;
+  return awb::launch_update(u, (hipStream_t)stream);
+}
+
+extern "C" int mi_isp_awb_rebuild(int pattern, float* gains, const mi_isp_shading* user, float* effective, void* stream) {
+  const char* who = "awb_rebuild";
+  MI_REQUIRE(gains, "%s: null awb gains", who);
+  awb::Update u = {};
+  if (int rc = awb_grid(u, pattern, user, effective, who)) return rc;
+  u.gains = gains;
+  return awb::launch_update(u, (hipStream_t)stream);
 }
 
 // ---- measurement aid: HIP events around each data pass, on the stream it runs on ---------------------

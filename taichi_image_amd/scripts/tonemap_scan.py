@@ -192,6 +192,8 @@ def build_parser() -> argparse.ArgumentParser:
     # lens distortion (an extension): a directory of <camera folder name>.npz files holding K, dist (OpenCV order) and
     # optionally new_K
     tone.add_argument("--lens-distortion", dest="lens_distortion", type=Path, default=None)
+    # auto white balance (an extension): a gray-world loop over every camera's frames, seeded with the fixed white balance
+    tone.add_argument("--auto-white-balance", dest="auto_white_balance", action="store_true")
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -225,7 +227,8 @@ def main(argv=None) -> int:
     device = torch.device(args.device)
     isp = camera_isp.Camera32(bayer.BayerPattern.RGGB, transform=args.transform, moving_alpha=args.moving_alpha,
                               resize_width=args.resize_width, correct_colors=args.correct_colors, device=device,
-                              black_level=black, white_level=args.white_level, lens_shading=shading)
+                              black_level=black, white_level=args.white_level, lens_shading=shading,
+                              auto_white_balance=args.auto_white_balance)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
