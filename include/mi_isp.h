@@ -359,6 +359,35 @@ int mi_isp_awb_update(const int64_t* gathered_dev, int world, void* pending_dev,
                       float* gains_dev, const mi_isp_shading* user_host, float* effective_dev, void* stream);
 int mi_isp_awb_rebuild(int pattern, float* gains_dev, const mi_isp_shading* user_host, float* effective_dev,
                        void* stream);
+/* ---- raw noise reduction ("Raw noise reduction") -----------------------------------------------------
+ * An edge-preserving bilateral filter over same-site neighbours, adapted to the sensor's noise model.  x(p) of raw pixel p
+ * is the f32 value the loader computes before shading and the cast (the decode with or without levels, load_16u's true
+ * division, the value load_16f / load_32f convert).  For p = (r, c), T(p) = the pixels q = (r + 2i, c + 2j), |i|, |j| <=
+ * radius, (i, j) != (0, 0), inside the frame and not set in the defect mask:
+ *   var = gain * max(x(p), 0) + read_noise^2;  k = 1 / (2 strength^2 var)
+ *   w(q) = exp(-(x(q) - x(p))^2 k - (i^2 + j^2) / (2 spatial_sigma^2));  y = (x(p) + sum w(q) x(q)) / (1 + sum w(q))
+ *   cfa = cast_work(y * g(p))      (g the lens shading gain of shading_host, 1 for NULL)
+ * in f32 with the hardware exp and rcp: within one unit of the work dtype of an f64 evaluation (f32: or 1e-5 relative).
+ * The noise model is in the units of x.  Source kinds: MI_RAW_PACKED12 (ids_format selects the IDS layout) and
+ * MI_RAW_PACKED16 with levels as mi_isp_load_packed_levels (H and W even); MI_RAW_16U / 32F / 16F the modes of
+ * mi_isp_load_convert_shading (levels with MI_RAW_16U only).  Only the mask of a defect map is read.  The output is an
+ * H x W work-dtype CFA (MI_F16 / MI_F32) that must not overlap the source.
+ *  - mi_isp_denoise_raw_batch: n frames of one geometry, defects_host NULL or one map (or NULL) per frame; one launch per
+ *    32 frames.
+ *  - mi_isp_denoise_cfa: a normalised H x W CFA of dtype MI_F16 / MI_F32 (no levels, gain or mask), out of the same dtype.
+ * Host-side checks before any launch (error text names "denoise"): radius 1 or 2, gain finite >= 0, read_noise, strength
+ * and spatial_sigma finite > 0, shapes, dtypes, kinds, levels, grids, NULL pointers. */
+typedef struct { float gain, read_noise, strength, spatial_sigma; int32_t radius; } mi_isp_denoise;
+enum { MI_RAW_PACKED12 = 0, MI_RAW_PACKED16 = 1, MI_RAW_16U = 2, MI_RAW_32F = 3, MI_RAW_16F = 4 };
+int mi_isp_denoise_raw(const void* src_dev, void* cfa_dev, int H, int W, int src_kind, int ids_format, int work_dtype,
+                       const mi_isp_levels* levels_host, const mi_isp_shading* shading_host,
+                       const mi_isp_defects* defects_host, const mi_isp_denoise* denoise_host, void* stream);
+int mi_isp_denoise_raw_batch(const void* const* src_host, void* const* cfa_host, int n, int H, int W, int src_kind,
+                             int ids_format, int work_dtype, const mi_isp_levels* levels_host,
+                             const mi_isp_shading* shading_host, const mi_isp_defects* const* defects_host,
+                             const mi_isp_denoise* denoise_host, void* stream);
+int mi_isp_denoise_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, const mi_isp_denoise* denoise_host,
+                       void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==

@@ -18,6 +18,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_ISP_LIB") or os.path.join(_HERE, "lib", "libmi355_isp.so")
 
 MI_U8, MI_U16, MI_F16, MI_F32 = 0, 1, 2, 3
+# source kinds of mi_isp_denoise_raw(_batch)
+MI_RAW_PACKED12, MI_RAW_PACKED16, MI_RAW_16U, MI_RAW_32F, MI_RAW_16F = 0, 1, 2, 3, 4
 
 
 class Levels(ctypes.Structure):
@@ -41,6 +43,13 @@ class Lens(ctypes.Structure):
     _fields_ = [("fx", c_double), ("fy", c_double), ("cx", c_double), ("cy", c_double),
                 ("new_fx", c_double), ("new_fy", c_double), ("new_cx", c_double), ("new_cy", c_double),
                 ("dist", c_double * 8), ("n_dist", c_int32), ("border", c_int32)]
+
+
+class Denoise(ctypes.Structure):
+    """mi_isp_denoise: the raw noise filter's noise model (gain, read_noise, in the loader's x units), strength,
+    spatial_sigma and radius (1 or 2)."""
+    _fields_ = [("gain", c_float), ("read_noise", c_float), ("strength", c_float), ("spatial_sigma", c_float),
+                ("radius", c_int32)]
 
 
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
@@ -116,6 +125,11 @@ SIGNATURES = {
                                      _P, _P]),
     "mi_isp_awb_update": (c_int, [_P, c_int, _P, c_int, c_double, _P, _P, POINTER(Shading), _P, _P]),
     "mi_isp_awb_rebuild": (c_int, [c_int, _P, POINTER(Shading), _P, _P]),
+    "mi_isp_denoise_raw": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading),
+                                   POINTER(Defects), POINTER(Denoise), _P]),
+    "mi_isp_denoise_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
+                                         POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Denoise), _P]),
+    "mi_isp_denoise_cfa": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(Denoise), _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,

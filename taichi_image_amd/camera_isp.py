@@ -21,6 +21,7 @@ import torch
 
 from . import _native, bayer, interpolate, packed, types
 from . import defects as _defects
+from . import denoise as _dn
 from . import lens as _lens
 from . import white_balance as _wb
 from . import distributed as _dist
@@ -276,7 +277,8 @@ def camera_isp(name: str, dtype=types.f32):
                      black_level=None,
                      white_level: Optional[int] = None,
                      lens_shading=None,
-                     auto_white_balance=False):
+                     auto_white_balance=False,
+                     raw_denoise=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -292,6 +294,7 @@ def camera_isp(name: str, dtype=types.f32):
             awb = _wb.check_auto_white_balance(auto_white_balance)
             if awb is not None:
                 _wb.check_seed(white_balance)
+            raw_denoise = _dn.check_raw_denoise(raw_denoise)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -334,6 +337,9 @@ def camera_isp(name: str, dtype=types.f32):
             self._awb_retired = []
             if awb is not None:
                 self._awb_seed(awb)
+            # raw noise reduction (an extension): the RawDenoise of this sensor, or None (the loaders run exactly as
+            # without it).  DESIGN.md 3, "Raw noise reduction".
+            self._raw_denoise = raw_denoise
 
         @property
         def _demosaic_pattern(self):
@@ -345,7 +351,8 @@ def camera_isp(name: str, dtype=types.f32):
                 white_balance: Optional[np.ndarray] = None,
                 color_correction: Optional[np.ndarray] = None,
                 transform: Optional[interpolate.ImageTransform] = None,
-                black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None):
+                black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
+                raw_denoise=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -354,7 +361,8 @@ def camera_isp(name: str, dtype=types.f32):
             auto_white_balance (the extension): None leaves it; False turns it off (the ISP then computes exactly what
             one that never had it does); True or an AutoWhiteBalance turns it on and seeds it: gains f32(white_balance),
             no state, no pending statistics.  white_balance= while it is on seeds it again; lens_shading= while it is on
-            rebuilds the effective grid from the new grid and the current gains on the device."""
+            rebuilds the effective grid from the new grid and the current gains on the device.
+            raw_denoise (the extension): None leaves it, False turns it off, a RawDenoise replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -362,6 +370,7 @@ def camera_isp(name: str, dtype=types.f32):
             awb = self._awb if auto_white_balance is None else _wb.check_auto_white_balance(auto_white_balance)
             if awb is not None and (auto_white_balance is not None or white_balance is not None):
                 _wb.check_seed(self.white_balance if white_balance is None else white_balance)
+            denoise = None if raw_denoise is None or raw_denoise is False else _dn.check_raw_denoise(raw_denoise)
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -402,6 +411,10 @@ def camera_isp(name: str, dtype=types.f32):
                     if self._shading is not None:
                         self._shading_retired.append(self._shading)
                     self._shading = new.to(self.device)
+            if raw_denoise is False:
+                self._raw_denoise = None
+            elif denoise is not None:
+                self._raw_denoise = denoise
             if auto_white_balance is not None:
                 if awb is None:
                     self._awb_off()
@@ -485,6 +498,28 @@ def camera_isp(name: str, dtype=types.f32):
                 _native.shading_arg(self._shading), self._awb_E.data_ptr(), _native.stream_ptr(self.device)))
 
         @property
+        def raw_denoise(self) -> Optional[_dn.RawDenoise]:
+            """The RawDenoise the loaders apply, or None."""
+            return self._raw_denoise
+
+        def _denoised(self, srcs, h, w, kind, ids_format, lv, maps):
+            """The raw noise reduction route: the filtered, gained, cast work-dtype CFAs of the raw frames srcs (one shape,
+            mi_isp_denoise_raw_batch source kind `kind`) in one launch, then the defect fix-up of each frame with a map (maps:
+            one DefectMap or None per frame).  DESIGN.md 3, "Raw noise reduction"."""
+            L = _native.lib()
+            stream = _native.stream_ptr(self.device)
+            cfas = [torch.empty((h, w), dtype=torch_dtype, device=self.device) for _ in srcs]
+            args = [None if m is None else m._arg(self.device) for m in maps]       # (kept alive through the call)
+            p_maps = (ctypes.c_void_p * len(maps))(*[None if a is None else ctypes.addressof(a) for a in args])
+            _native.check(L.mi_isp_denoise_raw_batch(
+                _native.ptr_array(srcs), _native.ptr_array(cfas), len(srcs), h, w, kind, int(bool(ids_format)), dtype.code,
+                lv, _native.shading_arg(self._applied_shading()), p_maps, self._raw_denoise._arg(), stream))
+            for cfa, a in zip(cfas, args):
+                if a is not None:
+                    _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, a, stream))
+            return cfas
+
+        @property
         def lens_shading(self) -> Optional[torch.Tensor]:
             """The lens shading grid the loaders apply, (sites, Gh, Gw) f32 on the device (do not write it; use set), or
             None."""
@@ -523,7 +558,10 @@ def camera_isp(name: str, dtype=types.f32):
             src = image.to(self.device).contiguous()
             cfa = torch.empty(image.shape, dtype=torch_dtype, device=self.device)
             sh = _native.shading_arg(self._applied_shading())
-            if sh is not None:
+            if self._raw_denoise is not None:            # raw noise reduction: the filtered CFA, its defects fixed up
+                cfa = self._denoised([src], image.shape[0], image.shape[1], _native.MI_RAW_16U + mode, False, lv, [dm])[0]
+                dm = None
+            elif sh is not None:
                 _native.check(_native.lib().mi_isp_load_convert_shading(src.data_ptr(), cfa.data_ptr(), image.shape[0],
                                                                         image.shape[1], mode, dtype.code, lv, sh,
                                                                         _native.stream_ptr(self.device)))
@@ -640,6 +678,9 @@ def camera_isp(name: str, dtype=types.f32):
             dm = _defects.check_defects(defects, (h, w))
             lens = self._check_lens(undistort, h, w)
             src = image_data.to(self.device).contiguous()
+            if self._raw_denoise is not None:            # raw noise reduction: the filtered CFA, then the demosaic
+                kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
+                return self._process_image(self._denoised([src], h, w, kind, ids_format, lv, [dm])[0], lens)
             if lens is not None:                         # lens distortion: a full-resolution load, then the remap
                 rgb = self._load_full([src], h, w, bits, ids_format, lv, _native.shading_arg(self._applied_shading()), [dm])
                 return self._undistort(rgb, [lens], h, w)[0]
@@ -758,6 +799,11 @@ def camera_isp(name: str, dtype=types.f32):
             lv = self._levels(bits)
             maps = self._batch_defects(defects, len(images_data), (h, w))
             lenses = self._batch_lenses(undistort, len(images_data), h, w)
+            if self._raw_denoise is not None:            # raw noise reduction: one filter launch, then per frame
+                srcs = [d.to(self.device).contiguous() for d in images_data]
+                kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
+                cfas = self._denoised(srcs, h, w, kind, ids_format, lv, maps)
+                return [self._process_image(c, m) for c, m in zip(cfas, lenses)]
             if any(m is not None for m in lenses):
                 # lens distortion: the frames without a lens as the call without lenses, the others loaded at full
                 # resolution in one launch and remapped
@@ -988,6 +1034,7 @@ def camera_isp(name: str, dtype=types.f32):
                 undistort = lenses if any(m is not None for m in lenses) else None
             fused = (dtype is types.f16 and not ids_format and self.resize_width == 0 and self.scale is None
                      and self._applied_shading() is None      # (lens shading or AWB: the two calls below)
+                     and self._raw_denoise is None            # (raw noise reduction: the two calls below)
                      and defects is None                      # (defective pixels: the two calls below)
                      and undistort is None                    # (lens distortion: the two calls below)
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8

@@ -14,6 +14,7 @@
 #include "isp_defects.h"
 #include "isp_lens.h"
 #include "isp_awb.h"
+#include "isp_denoise.h"
 #include <mutex>
 #include <atomic>
 
@@ -26,7 +27,7 @@ void mi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int mi_isp_version(void) { return 1600; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
+extern "C" int mi_isp_version(void) { return 1700; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
 extern "C" const char* mi_isp_last_error(void) { return g_err; }
 
 extern "C" int mi_isp_bayer_weights(int32_t out[4 * 13 * 3]) {
@@ -651,6 +652,126 @@ extern "C" int mi_isp_awb_rebuild(int pattern, float* gains, const mi_isp_shadin
   if (int rc = awb_grid(u, pattern, user, effective, who)) return rc;
   u.gains = gains;
   return awb::launch_update(u, (hipStream_t)stream);
+}
+
+// ---- raw noise reduction (isp_denoise.h; DESIGN.md 3, "Raw noise reduction") ----------------------------------------
+// the filter's settings, checked on the host; fills the filter members of a
+static int denoise_settings(dn::Args& a, const mi_isp_denoise* d, const char* who) {
+  MI_REQUIRE(d, "%s: null denoise settings", who);
+  MI_REQUIRE(d->radius == 1 || d->radius == 2, "%s: denoise radius %d (1 or 2)", who, (int)d->radius);
+  MI_REQUIRE(std::isfinite(d->gain) && d->gain >= 0.f, "%s: denoise gain %g must be finite and >= 0", who,
+             (double)d->gain);
+  MI_REQUIRE(std::isfinite(d->read_noise) && d->read_noise > 0.f, "%s: denoise read_noise %g must be finite and > 0",
+             who, (double)d->read_noise);
+  MI_REQUIRE(std::isfinite(d->strength) && d->strength > 0.f, "%s: denoise strength %g must be finite and > 0", who,
+             (double)d->strength);
+  MI_REQUIRE(std::isfinite(d->spatial_sigma) && d->spatial_sigma > 0.f,
+             "%s: denoise spatial_sigma %g must be finite and > 0", who, (double)d->spatial_sigma);
+  const double log2e = 1.4426950408889634, rn = d->read_noise, st = d->strength, sg = d->spatial_sigma;
+  a.gain = d->gain;
+  a.rn2 = (float)(rn * rn);
+  a.c2 = (float)(log2e / (2.0 * st * st));
+  for (int k = 0; k < 9; ++k) a.sp[k] = (float)((double)k * log2e / (2.0 * sg * sg));
+  return 0;
+}
+
+static int denoise_geometry(int H, int W, int work_dtype, const char* who) {
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad denoise shape %dx%d", who, H, W);
+  MI_REQUIRE(H < (1 << 22) && W < (1 << 24), "%s: denoise frame %dx%d too large", who, H, W);
+  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: denoise work dtype must be f16 or f32", who);
+  return 0;
+}
+
+// n raw frames of one geometry: every frame's pointers (and defect mask) in the kernel arguments, 32 per launch
+static int denoise_raw_impl(const void* const* src, void* const* cfa, int n, int H, int W, int kind, int ids_format,
+                            int work_dtype, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                            const mi_isp_defects* const* defects, const mi_isp_denoise* d, void* stream, const char* who) {
+  dn::Args a = {};
+  if (int rc = denoise_settings(a, d, who)) return rc;
+  if (int rc = denoise_geometry(H, W, work_dtype, who)) return rc;
+  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad denoise source kind %d", who, kind);
+  MI_REQUIRE(n >= 0 && (src || n == 0) && (cfa || n == 0), "%s: null frame list", who);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && cfa[i], "%s: frame %d has a null pointer", who, i);
+    MI_REQUIRE(src[i] != cfa[i], "%s: frame %d: the CFA must not overwrite its source", who, i);
+  }
+  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
+  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: packed frames must be even size, got %dx%d", who, H, W);
+  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: the IDS layout is a packed-12 layout", who);
+  a.H = H; a.W = W;
+  int src_kind;
+  if (packed) {
+    tile::Params p = {};
+    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
+    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
+    if (int rc = apply_levels(p, levels, bits, who)) return rc;
+    for (int s = 0; s < 4; ++s) {                     // the per-site decode of the shading path (apply_levels_shading)
+      a.black[s] = p.levels ? p.lv_black[s] : 0;
+      a.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
+    }
+    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
+  } else {
+    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
+      MI_REQUIRE(kind == MI_RAW_16U, "%s: levels apply to u16 codes only (source kind %d)", who, kind);
+      MI_REQUIRE(levels->white > 0 && levels->white <= 65535, "%s: white level %d outside (0, 65535]", who,
+                 (int)levels->white);
+      for (int s = 0; s < 4; ++s) {
+        MI_REQUIRE(levels->black[s] >= 0 && levels->black[s] < levels->white,
+                   "%s: black level %d of site %d outside [0, white = %d)", who, (int)levels->black[s], s,
+                   (int)levels->white);
+        a.black[s] = levels->black[s];
+        a.k[s] = (float)(levels->white - levels->black[s]);
+      }
+      a.levels = 1;
+    }
+    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
+  }
+  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
+  a.mask_w = (W + 31) / 32;
+  for (int i = 0; i < n; ++i)
+    if (defects && defects[i]) {
+      MI_REQUIRE(defects[i]->n >= 0, "%s: negative defect count %d", who, (int)defects[i]->n);
+      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: frame %d: defects without a mask", who, i);
+    }
+  for (int i0 = 0; i0 < n; i0 += dn::MAX_FRAMES) {
+    a.n_frames = n - i0 < dn::MAX_FRAMES ? n - i0 : dn::MAX_FRAMES;
+    for (int i = 0; i < a.n_frames; ++i) {
+      const mi_isp_defects* m = defects ? defects[i0 + i] : nullptr;
+      a.f[i] = {src[i0 + i], cfa[i0 + i], (m && m->n > 0) ? m->mask_dev : nullptr};
+    }
+    if (int rc = dn::launch(a, src_kind, work_dtype, d->radius, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_denoise_raw(const void* src, void* cfa, int H, int W, int kind, int ids_format, int work_dtype,
+                                  const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                  const mi_isp_defects* defects, const mi_isp_denoise* denoise, void* stream) {
+  MI_REQUIRE(src && cfa, "denoise_raw: null pointer");
+  return denoise_raw_impl(&src, &cfa, 1, H, W, kind, ids_format, work_dtype, levels, shading, &defects, denoise, stream,
+                          "denoise_raw");
+}
+
+extern "C" int mi_isp_denoise_raw_batch(const void* const* src, void* const* cfa, int n, int H, int W, int kind,
+                                        int ids_format, int work_dtype, const mi_isp_levels* levels,
+                                        const mi_isp_shading* shading, const mi_isp_defects* const* defects,
+                                        const mi_isp_denoise* denoise, void* stream) {
+  return denoise_raw_impl(src, cfa, n, H, W, kind, ids_format, work_dtype, levels, shading, defects, denoise, stream,
+                          "denoise_raw_batch");
+}
+
+extern "C" int mi_isp_denoise_cfa(const void* in, void* out, int H, int W, int dtype, const mi_isp_denoise* denoise,
+                                  void* stream) {
+  const char* who = "denoise_cfa";
+  dn::Args a = {};
+  if (int rc = denoise_settings(a, denoise, who)) return rc;
+  if (int rc = denoise_geometry(H, W, dtype, who)) return rc;
+  MI_REQUIRE(in && out, "%s: null pointer", who);
+  MI_REQUIRE(in != out, "%s: the output must not overwrite the input", who);
+  a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
+  a.n_frames = 1;
+  a.f[0] = {in, out, nullptr};
+  return dn::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype, denoise->radius, (hipStream_t)stream);
 }
 
 // ---- measurement aid: HIP events around each data pass, on the stream it runs on ---------------------

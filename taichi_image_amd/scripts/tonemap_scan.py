@@ -194,6 +194,11 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--lens-distortion", dest="lens_distortion", type=Path, default=None)
     # auto white balance (an extension): a gray-world loop over every camera's frames, seeded with the fixed white balance
     tone.add_argument("--auto-white-balance", dest="auto_white_balance", action="store_true")
+    # raw noise reduction (an extension): the sensor's noise model, GAIN and READ_NOISE in units of the white level
+    # (denoise.noise_model_from_frames fits them from a few frames of a static scene), the filter strength and radius
+    tone.add_argument("--raw-denoise", dest="raw_denoise", type=float, nargs=2, metavar=("GAIN", "READ_NOISE"), default=None)
+    tone.add_argument("--denoise-strength", dest="denoise_strength", type=float, default=1.0)
+    tone.add_argument("--denoise-radius", dest="denoise_radius", type=int, default=1)
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -206,6 +211,7 @@ def main(argv=None) -> int:
     from .. import bayer, camera_isp, ingest
     from ..defects import DefectMap
     from ..lens import LensDistortion
+    from ..denoise import RawDenoise
     args = build_parser().parse_args(argv)
     if args.scan is None and args.images is None:
         raise ValueError("No --scan or --images specified")
@@ -218,6 +224,10 @@ def main(argv=None) -> int:
     if args.lens_shading is not None:
         shading = np.load(args.lens_shading, allow_pickle=False)
         camera_isp._check_shading(shading)                          # (also before any frame is read)
+    denoise = None
+    if args.raw_denoise is not None:                                # (checked before any frame is read)
+        denoise = RawDenoise(args.raw_denoise[0], args.raw_denoise[1], strength=args.denoise_strength,
+                             radius=args.denoise_radius)
     index = ScanIndex.of_scan(args.scan) if args.scan is not None else ScanIndex.of_directory(args.images)
     coords = {} if args.defect_pixels is None else load_defect_pixels(args.defect_pixels, index.cameras, args.width)
     calib = {} if args.lens_distortion is None else load_lens_distortion(args.lens_distortion, index.cameras)
@@ -228,7 +238,7 @@ def main(argv=None) -> int:
     isp = camera_isp.Camera32(bayer.BayerPattern.RGGB, transform=args.transform, moving_alpha=args.moving_alpha,
                               resize_width=args.resize_width, correct_colors=args.correct_colors, device=device,
                               black_level=black, white_level=args.white_level, lens_shading=shading,
-                              auto_white_balance=args.auto_white_balance)
+                              auto_white_balance=args.auto_white_balance, raw_denoise=denoise)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
