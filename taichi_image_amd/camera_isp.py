@@ -462,18 +462,6 @@ def camera_isp(name: str, dtype=types.f32):
             """The grid the loaders apply: E with AWB on, else the user's grid (or None)."""
             return self._awb_E if self._awb is not None else self._shading
 
-        def _awb_stats_packed(self, images_data, bits, ids_format):
-            """Add the AWB statistics of packed frames (one shape) to the pending sums; nothing with AWB off."""
-            if self._awb is None or not images_data:
-                return
-            srcs = [d.to(self.device).contiguous() for d in images_data]
-            h = srcs[0].shape[0]
-            w = srcs[0].shape[1] * 2 // 3 if bits == 12 else srcs[0].shape[1] // 2
-            _native.check(_native.lib().mi_isp_awb_stats_packed(
-                _native.ptr_array(srcs), len(srcs), h, w, bits, int(bool(ids_format)), self._levels(bits),
-                _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor), int(self._awb.stride),
-                self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
-
         @property
         def auto_white_balance(self):
             """The AutoWhiteBalance in effect, or None."""
@@ -531,56 +519,51 @@ def camera_isp(name: str, dtype=types.f32):
             lv = _check_levels(self.black_level, self.white_level, bits)
             return None if lv is None else _native.levels_arg(*lv)
 
-        def resize_image(self, image):
-            """camera_isp.py:302-315."""
-            w, h = image.shape[1], image.shape[0]
+        def _geometry(self, h, w):
+            """(hd, wd, scale) of resize_image's output for an h x w frame (camera_isp.py:302-312), scale 0.0 without a
+            resize."""
             if self.resize_width > 0:
                 scale = self.resize_width / w
-                output_size = (self.resize_width, round(h * scale))
-                return interpolate.resize_bilinear(image, output_size, scale)
-            elif self.scale is not None:
-                output_size = (round(w * self.scale), round(h * self.scale))
-                return interpolate.resize_bilinear(image, output_size, self.scale)
-            else:
+                return round(h * scale), self.resize_width, scale
+            if self.scale is not None:
+                return round(h * self.scale), round(w * self.scale), self.scale
+            return h, w, 0.0
+
+        def resize_image(self, image):
+            """camera_isp.py:302-315."""
+            if self.resize_width <= 0 and self.scale is None:
                 return image
+            hd, wd, scale = self._geometry(*image.shape[:2])
+            return interpolate.resize_bilinear(image, (wd, hd), scale)
 
         def _convert(self, image, mode, src_dtype, defects=None, undistort=None):
             if not isinstance(image, torch.Tensor):
                 raise TypeError("image must be a torch.Tensor")
             assert image.ndim == 2, "image must be a 2-D CFA"
             assert image.dtype == src_dtype, f"image must be {src_dtype}, got {image.dtype}"
-            dm = _defects.check_defects(defects, tuple(image.shape))
-            lens = self._check_lens(undistort, *image.shape)
+            h, w = image.shape
+            dm = _defects.check_defects(defects, (h, w))
+            lens = self._check_lens(undistort, (h, w))
             lv = self._levels(16)
             if lv is not None and mode != 0:
                 raise ValueError("black_level / white_level apply to raw codes (load_16u, load_packed12/16); "
                                  "load_16f / load_32f take normalised values")
+            L = _native.lib()
+            stream = _native.stream_ptr(self.device)
             src = image.to(self.device).contiguous()
-            cfa = torch.empty(image.shape, dtype=torch_dtype, device=self.device)
-            sh = _native.shading_arg(self._applied_shading())
             if self._raw_denoise is not None:            # raw noise reduction: the filtered CFA, its defects fixed up
-                cfa = self._denoised([src], image.shape[0], image.shape[1], _native.MI_RAW_16U + mode, False, lv, [dm])[0]
-                dm = None
-            elif sh is not None:
-                _native.check(_native.lib().mi_isp_load_convert_shading(src.data_ptr(), cfa.data_ptr(), image.shape[0],
-                                                                        image.shape[1], mode, dtype.code, lv, sh,
-                                                                        _native.stream_ptr(self.device)))
-            elif lv is None:
-                _native.check(_native.lib().mi_isp_load_convert(src.data_ptr(), cfa.data_ptr(), cfa.numel(), mode,
-                                                                dtype.code, _native.stream_ptr(self.device)))
+                cfa = self._denoised([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
             else:
-                _native.check(_native.lib().mi_isp_load_convert_levels(src.data_ptr(), cfa.data_ptr(), image.shape[0],
-                                                                       image.shape[1], mode, dtype.code, lv,
-                                                                       _native.stream_ptr(self.device)))
-            if dm is not None:                           # defective pixels: the CFA's listed sites, in place
-                _native.check(_native.lib().mi_isp_defects_fix_cfa(cfa.data_ptr(), image.shape[0], image.shape[1],
-                                                                   dtype.code, dm._arg(self.device),
-                                                                   _native.stream_ptr(self.device)))
+                cfa = torch.empty((h, w), dtype=torch_dtype, device=self.device)
+                # (NULL levels and a NULL grid are exactly the plain mi_isp_load_convert, include/mi_isp.h)
+                _native.check(L.mi_isp_load_convert_shading(src.data_ptr(), cfa.data_ptr(), h, w, mode, dtype.code, lv,
+                                                            _native.shading_arg(self._applied_shading()), stream))
+                if dm is not None:                       # defective pixels: the CFA's listed sites, in place
+                    _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, dm._arg(self.device), stream))
             if self._awb is not None:                    # auto white balance: the statistics of the source
-                _native.check(_native.lib().mi_isp_awb_stats_cfa(
-                    src.data_ptr(), image.shape[0], image.shape[1], mode, lv, _native.shading_arg(self._shading),
-                    float(self._awb.clip), float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(),
-                    _native.stream_ptr(self.device)))
+                _native.check(L.mi_isp_awb_stats_cfa(
+                    src.data_ptr(), h, w, mode, lv, _native.shading_arg(self._shading), float(self._awb.clip),
+                    float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(), stream))
             return self._process_image(cfa, lens)
 
         def load_16u(self, image, defects=None, undistort=None):
@@ -596,48 +579,22 @@ def camera_isp(name: str, dtype=types.f32):
             """camera_isp.py:328-331 (kernel :89-93)."""
             return self._convert(image, 1, torch.float32, defects, undistort)
 
-        def _lens_geometry(self, h, w):
-            """(Hd, Wd, scale) of the output of an h x w frame: resize_image's size and scale, or the frame at scale 1."""
-            if self.resize_width > 0:
-                scale = self.resize_width / w
-                return round(h * scale), self.resize_width, scale
-            if self.scale is not None:
-                return round(h * self.scale), round(w * self.scale), self.scale
-            return h, w, 1.0
-
-        def _check_lens(self, undistort, h, w):
-            """The lens of an h x w frame (None: none); ValueError for another frame shape or a table of another output
-            shape than the loader's."""
+        def _check_lens(self, undistort, shape):
+            """The lens of a frame of `shape` (None: none); ValueError for another frame shape or a table of another
+            output shape than the loader's."""
             if undistort is None:
                 return None
-            return _lens.check_lens(undistort, (h, w), self._lens_geometry(h, w)[:2])
+            return _lens.check_lens(undistort, shape, self._geometry(*shape)[:2])
 
         def _undistort(self, rgbs, lenses, h, w):
             """The full-resolution work-dtype images rgbs remapped through lenses (one each, none None) into new images
-            at the ISP's resize geometry (one launch for the analytic lenses)."""
-            hd, wd, scale = self._lens_geometry(h, w)
+            at the ISP's resize geometry, at scale 1 without a resize (one launch for the analytic lenses)."""
+            hd, wd, scale = self._geometry(h, w)
+            scale = scale or 1.0                         # (no resize: the remap at scale 1)
             outs = [torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device) for _ in rgbs]
             if hd * wd:
                 _lens.apply(lenses, rgbs, outs, h, w, hd, wd, scale, scale, dtype.code, dtype.code, self.device)
             return outs
-
-        def _load_full(self, srcs, h, w, bits, ids_format, lv, sh, maps):
-            """The frames loaded at full resolution (levels, shading and defect fix-ups at scale 0) in one batch launch,
-            without a metering subsample: the source of a lens remap."""
-            L = _native.lib()
-            rgbs = [torch.empty((h, w, 3), dtype=torch_dtype, device=self.device) for _ in srcs]
-            args = (_native.ptr_array(srcs), _native.ptr_array(rgbs), None, len(srcs), h, w, bits, int(bool(ids_format)),
-                    self._demosaic_pattern.value, _native.ccm_arg(self.color_correct_matrix), dtype.code, h, w, 0.0,
-                    self.metering_stride)
-            if sh is not None:
-                _native.check(L.mi_isp_load_packed_batch_shading(*args, lv, sh, _native.stream_ptr(self.device)))
-            elif lv is None:
-                _native.check(L.mi_isp_load_packed_batch(*args, _native.stream_ptr(self.device)))
-            else:
-                _native.check(L.mi_isp_load_packed_batch_levels(*args, lv, _native.stream_ptr(self.device)))
-            if any(m is not None for m in maps):
-                self._fix_defects(srcs, rgbs, None, maps, h, w, bits, ids_format, h, w, 0.0, lv, sh)
-            return rgbs
 
         def _fix_defects(self, srcs, rgbs, subs, maps, h, w, bits, ids_format, hd, wd, scale, lv, sh):
             """The sparse fix-up after a packed load on the same stream: every output pixel of rgbs[i] (and its metering
@@ -664,84 +621,125 @@ def camera_isp(name: str, dtype=types.f32):
                 len(srcs), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value, ccm, dtype.code, hd, wd,
                 float(scale), st, lv, sh, p_maps, p_lists, counts, stream))
 
-        def _load_packed(self, image_data, bits, ids_format, defects=None, undistort=None):
-            if not isinstance(image_data, torch.Tensor):
-                raise TypeError("image_data must be a torch.Tensor")
-            assert image_data.ndim == 2 and image_data.dtype == torch.uint8, "image_data must be (H, bytes) uint8"
+        @staticmethod
+        def _packed_shape(frames, bits):
+            """(h, w) of the packed frames of one call (camera_isp.py:336,343), checked: (H, bytes) uint8 tensors of one
+            shape that hold whole pixels of an even-size image."""
+            f0 = frames[0]
+            for d in frames:
+                if not isinstance(d, torch.Tensor):
+                    raise TypeError("image_data must be a torch.Tensor")
+                assert d.ndim == 2 and d.dtype == torch.uint8, "image_data must be (H, bytes) uint8"
+                assert d is f0 or d.shape == f0.shape, "the frames of a batch must share a shape"
+            h, row = f0.shape
             if bits == 12:
-                assert image_data.shape[1] % 3 == 0, "packed-12 rows must hold whole pixel pairs (bytes % 3 == 0)"
-                w, h = (image_data.shape[1] * 2 // 3, image_data.shape[0])        # camera_isp.py:336
-            else:
-                w, h = (image_data.shape[1] // 2, image_data.shape[0])             # camera_isp.py:343
+                assert row % 3 == 0, "packed-12 rows must hold whole pixel pairs (bytes % 3 == 0)"
+            w = row * 2 // 3 if bits == 12 else row // 2
             assert w % 2 == 0 and h % 2 == 0, "image must be even size"
+            return h, w
+
+        @staticmethod
+        def _per_frame(what, values, n, shape, check):
+            """The per-frame entries of a defects= / undistort= argument, each through check(entry, shape): None for a
+            frame without one, all None for None; ValueError for anything but a list of n entries."""
+            if values is None:
+                return [None] * n
+            if not isinstance(values, (list, tuple)):
+                raise ValueError(f"{what} must be None or a list with one entry per frame, got {type(values).__name__}")
+            if len(values) != n:
+                raise ValueError(f"{what} has {len(values)} entries for {n} frames")
+            return [check(v, shape) for v in values]
+
+        def _load_packed(self, frames, bits, ids_format, defects, undistort, batch):
+            """Every packed loader: the frames checked (levels, defect maps and lenses too, before anything is uploaded or
+            launched), loaded by their route - raw noise reduction, lens remap, or the plain load - and, with auto white
+            balance on, their statistics added to the pending sums in one launch behind the loads.  defects, undistort:
+            None or one entry per frame.  batch: the caller is the batch surface (see _load_frames)."""
+            h, w = self._packed_shape(frames, bits)
             lv = self._levels(bits)
-            dm = _defects.check_defects(defects, (h, w))
-            lens = self._check_lens(undistort, h, w)
-            src = image_data.to(self.device).contiguous()
-            if self._raw_denoise is not None:            # raw noise reduction: the filtered CFA, then the demosaic
+            maps = self._per_frame("defects", defects, len(frames), (h, w), _defects.check_defects)
+            lenses = self._per_frame("undistort", undistort, len(frames), (h, w), self._check_lens)
+            srcs = [d.to(self.device).contiguous() for d in frames]
+            if self._raw_denoise is not None:            # raw noise reduction: one filter launch, then per frame
                 kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
-                return self._process_image(self._denoised([src], h, w, kind, ids_format, lv, [dm])[0], lens)
-            if lens is not None:                         # lens distortion: a full-resolution load, then the remap
-                rgb = self._load_full([src], h, w, bits, ids_format, lv, _native.shading_arg(self._applied_shading()), [dm])
-                return self._undistort(rgb, [lens], h, w)[0]
-            L = _native.lib()
-            # with levels: the same calls through their *_levels twins (the same kernels' level-taking instantiations)
-            load = L.mi_isp_load_packed if lv is None else (lambda *a: L.mi_isp_load_packed_levels(*a[:-1], lv, a[-1]))
-            load_metered = (L.mi_isp_load_packed_metered if lv is None
-                            else (lambda *a: L.mi_isp_load_packed_metered_levels(*a[:-1], lv, a[-1])))
-            sh = _native.shading_arg(self._applied_shading())
-            if sh is not None:                           # lens shading (or AWB): the *_shading twins (levels or NULL)
-                load = lambda *a: L.mi_isp_load_packed_shading(*a[:-1], lv, sh, a[-1])   # noqa: E731
-                load_metered = lambda *a: L.mi_isp_load_packed_metered_shading(*a[:-1], lv, sh, a[-1])   # noqa: E731
-            # camera_isp.py:302-312: output size and scale of resize_image
-            if self.resize_width > 0:
-                scale = self.resize_width / w
-                out_size = (self.resize_width, round(h * scale))
-            elif self.scale is not None:
-                scale = self.scale
-                out_size = (round(w * scale), round(h * scale))
+                cfas = self._denoised(srcs, h, w, kind, ids_format, lv, maps)
+                rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
+            elif lenses.count(None) < len(lenses):       # (some frame has a lens)
+                # lens distortion: the frames without a lens as the call without lenses, the others loaded at full
+                # resolution in one launch and remapped
+                plain = [i for i, m in enumerate(lenses) if m is None]
+                rest = [i for i, m in enumerate(lenses) if m is not None]
+                out = dict(zip(plain, self._load_frames([srcs[i] for i in plain], h, w, bits, ids_format, lv,
+                                                        [maps[i] for i in plain], batch) if plain else []))
+                full = self._load_frames([srcs[i] for i in rest], h, w, bits, ids_format, lv, [maps[i] for i in rest],
+                                         True, full=True)
+                out.update(zip(rest, self._undistort(full, [lenses[i] for i in rest], h, w)))
+                rgbs = [out[i] for i in range(len(srcs))]
             else:
-                scale, out_size = 0.0, (w, h)
-            fused = scale > 0 and min(out_size) > 0 and L.mi_isp_load_packed_scale_supported(float(scale))
-            wd, hd = out_size if fused else (w, h)
-            rgb = torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device)
-            if not fused and scale > 0:                  # a scale the fused kernel does not take: resize separately
-                _native.check(load(
-                    src.data_ptr(), rgb.data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
-                    _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, 0.0, _native.stream_ptr(self.device)))
-                if dm is not None:
-                    self._fix_defects([src], [rgb], None, [dm], h, w, bits, ids_format, hd, wd, 0.0, lv, sh)
-                return self.resize_image(rgb)
-            st = self.metering_stride
-            if fused or not L.mi_isp_load_packed_metered_is_fused(h, w, bits, int(bool(ids_format)), dtype.code, st):
-                _native.check(load(
-                    src.data_ptr(), rgb.data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
-                    _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, float(scale) if fused else 0.0,
-                    _native.stream_ptr(self.device)))
-                if dm is not None:
-                    self._fix_defects([src], [rgb], None, [dm], h, w, bits, ids_format, hd, wd,
-                                      float(scale) if fused else 0.0, lv, sh)
-                return rgb
+                rgbs = self._load_frames(srcs, h, w, bits, ids_format, lv, maps, batch)
+            if self._awb is not None:                    # auto white balance: the statistics of the sources
+                _native.check(_native.lib().mi_isp_awb_stats_packed(
+                    _native.ptr_array(srcs), len(srcs), h, w, bits, int(bool(ids_format)), lv,
+                    _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor),
+                    int(self._awb.stride), self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
+            return rgbs
+
+        def _load_frames(self, srcs, h, w, bits, ids_format, lv, maps, batch, full=False):
+            """The load itself: the checked h x w packed frames srcs (on the device; maps: a DefectMap or None each) to
+            new work-dtype images at the resize geometry, then the defect fix-up on the same stream.  batch selects only
+            the entry point that launches: the batch surface loads all frames in one launch of the batch entry point, the
+            single-frame surface its one frame through the single-frame ones.  full: at full resolution whatever the
+            resize settings and without a metering subsample (the source of a lens remap).
+            The library's *_shading entry points take levels and a grid that may each be NULL; NULL / NULL is exactly the
+            plain call (include/mi_isp.h)."""
+            L = _native.lib()
+            ids, st = int(bool(ids_format)), self.metering_stride
+            hd, wd, scale = (h, w, 0.0) if full else self._geometry(h, w)
+            fused = scale > 0 and min(hd, wd) > 0 and L.mi_isp_load_packed_scale_supported(float(scale))
+            separate = scale > 0 and not fused           # a scale the fused kernel does not take: resize separately
+            if separate and batch:                       # (frame by frame through the single-frame route)
+                return [self._load_frames([s], h, w, bits, ids_format, lv, [m], False)[0] for s, m in zip(srcs, maps)]
+            if not fused:
+                hd, wd, scale = h, w, 0.0
             # the image and, on the way, the stride-subsampled copy update_metering will ask for (camera_isp.py:168-170):
             # the load kernel holds those pixels anyway, the strided gather over six 4K images costs 25 us per call
-            sub = torch.empty(((hd + st - 1) // st, (wd + st - 1) // st, 3), dtype=torch_dtype, device=self.device)
-            _native.check(load_metered(
-                src.data_ptr(), rgb.data_ptr(), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
-                _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, 0.0,
-                sub.data_ptr(), st, _native.stream_ptr(self.device)))
-            if dm is not None:
-                self._fix_defects([src], [rgb], [sub], [dm], h, w, bits, ids_format, hd, wd, 0.0, lv, sh)
-            _tag_subsample(rgb, sub, st)
-            return rgb
+            metered = not (full or fused or separate) and bool(
+                L.mi_isp_load_packed_metered_is_fused(h, w, bits, ids, dtype.code, st))
+            rgbs = [torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device) for _ in srcs]
+            subs = [torch.empty(((hd + st - 1) // st, (wd + st - 1) // st, 3), dtype=torch_dtype, device=self.device)
+                    for _ in srcs] if metered else None
+            sh = _native.shading_arg(self._applied_shading())
+            frame = (h, w, bits, ids, self._demosaic_pattern.value, _native.ccm_arg(self.color_correct_matrix), dtype.code,
+                     hd, wd, float(scale))
+            stream = _native.stream_ptr(self.device)
+            if batch:
+                _native.check(L.mi_isp_load_packed_batch_shading(
+                    _native.ptr_array(srcs), _native.ptr_array(rgbs), None if subs is None else _native.ptr_array(subs),
+                    len(srcs), *frame, st, lv, sh, stream))
+            elif metered:
+                _native.check(L.mi_isp_load_packed_metered_shading(srcs[0].data_ptr(), rgbs[0].data_ptr(), *frame,
+                                                                   subs[0].data_ptr(), st, lv, sh, stream))
+            else:
+                _native.check(L.mi_isp_load_packed_shading(srcs[0].data_ptr(), rgbs[0].data_ptr(), *frame, lv, sh, stream))
+            if maps.count(None) < len(maps):             # (some frame has a map)
+                self._fix_defects(srcs, rgbs, subs, maps, h, w, bits, ids_format, hd, wd, float(scale), lv, sh)
+            if metered:
+                for rgb, sub in zip(rgbs, subs):
+                    _tag_subsample(rgb, sub, st)
+            return [self.resize_image(rgb) for rgb in rgbs] if separate else rgbs
 
         def load_packed12(self, image_data, ids_format=False, defects=None, undistort=None):
             """camera_isp.py:333-340: unpack + demosaic (+ccm) fused in one pass over the packed frame.
             defects (an extension): None or the DefectMap of this sensor ("Defective pixels").
             undistort (an extension): None or the lens.LensDistortion of this camera ("Lens distortion"): the
             frame is loaded at full resolution, then remapped at the resize geometry (the fused resize is not used)."""
-            rgb = self._load_packed(image_data, 12, ids_format, defects, undistort)
-            self._awb_stats_packed([image_data], 12, ids_format)
-            return rgb
+            return self._load_packed([image_data], 12, ids_format, None if defects is None else [defects],
+                                     None if undistort is None else [undistort], False)[0]
+
+        def load_packed16(self, image_data, defects=None, undistort=None):
+            """camera_isp.py:342-347."""
+            return self._load_packed([image_data], 16, False, None if defects is None else [defects],
+                                     None if undistort is None else [undistort], False)[0]
 
         def load_packed12_batch(self, images_data: List[torch.Tensor], ids_format=False,
                                 defects=None, undistort=None) -> List[torch.Tensor]:
@@ -750,114 +748,14 @@ def camera_isp(name: str, dtype=types.f32):
             for bit, without the other launches' dispatch, table build and drain (config 3: 43.0 -> 39.5 us per frame).
             defects: None, or one entry per frame (a DefectMap or None); the fix-ups of all frames take one launch.
             undistort: None, or one entry per frame (a LensDistortion or None); the analytic remaps take one launch."""
-            rgbs = self._load_packed_batch(images_data, 12, ids_format, defects, undistort)
-            self._awb_stats_packed(images_data, 12, ids_format)
-            return rgbs
+            _typecheck("images_data", images_data, list)
+            return self._load_packed(images_data, 12, ids_format, defects, undistort, True) if images_data else []
 
         def load_packed16_batch(self, images_data: List[torch.Tensor], defects=None,
                                 undistort=None) -> List[torch.Tensor]:
             """The same for `load_packed16` (camera_isp.py:342-347)."""
-            rgbs = self._load_packed_batch(images_data, 16, False, defects, undistort)
-            self._awb_stats_packed(images_data, 16, False)
-            return rgbs
-
-        def _batch_lenses(self, undistort, n, h, w):
-            """The per-frame lenses of a batch call, None for each frame without one; ValueError as _batch_defects."""
-            if undistort is None:
-                return [None] * n
-            if not isinstance(undistort, (list, tuple)):
-                raise ValueError(f"undistort must be None or a list with one entry per frame, got {type(undistort).__name__}")
-            if len(undistort) != n:
-                raise ValueError(f"undistort has {len(undistort)} entries for {n} frames")
-            return [self._check_lens(m, h, w) for m in undistort]
-
-        def _batch_defects(self, defects, n, shape):
-            """The per-frame maps of a batch call, None for each frame without one, all None for defects=None; ValueError
-            for a list of another length or a map of another frame shape."""
-            if defects is None:
-                return [None] * n
-            if not isinstance(defects, (list, tuple)):
-                raise ValueError(f"defects must be None or a list with one entry per frame, got {type(defects).__name__}")
-            if len(defects) != n:
-                raise ValueError(f"defects has {len(defects)} entries for {n} frames")
-            return [_defects.check_defects(d, shape) for d in defects]
-
-        def _load_packed_batch(self, images_data, bits, ids_format, defects=None, undistort=None):
             _typecheck("images_data", images_data, list)
-            if len(images_data) == 0:
-                return []
-            for d in images_data:
-                if not isinstance(d, torch.Tensor):
-                    raise TypeError("image_data must be a torch.Tensor")
-                assert d.ndim == 2 and d.dtype == torch.uint8, "image_data must be (H, bytes) uint8"
-                assert d.shape == images_data[0].shape, "the frames of a batch must share a shape"
-            h = images_data[0].shape[0]
-            w = images_data[0].shape[1] * 2 // 3 if bits == 12 else images_data[0].shape[1] // 2
-            if bits == 12:
-                assert images_data[0].shape[1] % 3 == 0, "packed-12 rows must hold whole pixel pairs (bytes % 3 == 0)"
-            assert w % 2 == 0 and h % 2 == 0, "image must be even size"
-            lv = self._levels(bits)
-            maps = self._batch_defects(defects, len(images_data), (h, w))
-            lenses = self._batch_lenses(undistort, len(images_data), h, w)
-            if self._raw_denoise is not None:            # raw noise reduction: one filter launch, then per frame
-                srcs = [d.to(self.device).contiguous() for d in images_data]
-                kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
-                cfas = self._denoised(srcs, h, w, kind, ids_format, lv, maps)
-                return [self._process_image(c, m) for c, m in zip(cfas, lenses)]
-            if any(m is not None for m in lenses):
-                # lens distortion: the frames without a lens as the call without lenses, the others loaded at full
-                # resolution in one launch and remapped
-                plain = [i for i, m in enumerate(lenses) if m is None]
-                out = dict(zip(plain, self._load_packed_batch([images_data[i] for i in plain], bits, ids_format,
-                                                              [maps[i] for i in plain]) if plain else []))
-                rest = [i for i, m in enumerate(lenses) if m is not None]
-                srcs = [images_data[i].to(self.device).contiguous() for i in rest]
-                rgbs = self._load_full(srcs, h, w, bits, ids_format, lv, _native.shading_arg(self._applied_shading()),
-                                       [maps[i] for i in rest])
-                out.update(zip(rest, self._undistort(rgbs, [lenses[i] for i in rest], h, w)))
-                return [out[i] for i in range(len(images_data))]
-            L = _native.lib()
-            if self.resize_width > 0:
-                scale = self.resize_width / w
-                out_size = (self.resize_width, round(h * scale))
-            elif self.scale is not None:
-                scale = self.scale
-                out_size = (round(w * scale), round(h * scale))
-            else:
-                scale, out_size = 0.0, (w, h)
-            fused = scale > 0 and min(out_size) > 0 and L.mi_isp_load_packed_scale_supported(float(scale))
-            if scale > 0 and not fused:                      # a scale the fused kernel does not take
-                return [self._load_packed(d, bits, ids_format, m) for d, m in zip(images_data, maps)]
-            wd, hd = out_size if fused else (w, h)
-            srcs = [d.to(self.device).contiguous() for d in images_data]
-            rgbs = [torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device) for _ in srcs]
-            st = self.metering_stride
-            metered = not fused and bool(L.mi_isp_load_packed_metered_is_fused(h, w, bits, int(bool(ids_format)), dtype.code, st))
-            subs = [torch.empty(((hd + st - 1) // st, (wd + st - 1) // st, 3), dtype=torch_dtype, device=self.device)
-                    for _ in srcs] if metered else None
-            args = (_native.ptr_array(srcs), _native.ptr_array(rgbs), None if subs is None else _native.ptr_array(subs),
-                    len(srcs), h, w, bits, int(bool(ids_format)), self._demosaic_pattern.value,
-                    _native.ccm_arg(self.color_correct_matrix), dtype.code, hd, wd, float(scale) if fused else 0.0, st)
-            sh = _native.shading_arg(self._applied_shading())
-            if sh is not None:
-                _native.check(L.mi_isp_load_packed_batch_shading(*args, lv, sh, _native.stream_ptr(self.device)))
-            elif lv is None:
-                _native.check(L.mi_isp_load_packed_batch(*args, _native.stream_ptr(self.device)))
-            else:
-                _native.check(L.mi_isp_load_packed_batch_levels(*args, lv, _native.stream_ptr(self.device)))
-            if any(m is not None for m in maps):
-                self._fix_defects(srcs, rgbs, subs, maps, h, w, bits, ids_format, hd, wd, float(scale) if fused else 0.0,
-                                  lv, sh)
-            if subs is not None:
-                for rgb, sub in zip(rgbs, subs):
-                    _tag_subsample(rgb, sub, st)
-            return rgbs
-
-        def load_packed16(self, image_data, defects=None, undistort=None):
-            """camera_isp.py:342-347."""
-            rgb = self._load_packed(image_data, 16, False, defects, undistort)
-            self._awb_stats_packed([image_data], 16, False)
-            return rgb
+            return self._load_packed(images_data, 16, False, defects, undistort, True) if images_data else []
 
         @property
         def color_correct_matrix(self) -> Optional[np.ndarray]:
@@ -1022,16 +920,19 @@ def camera_isp(name: str, dtype=types.f32):
             L = _native.lib()
             f0 = frames[0]
             lv = self._levels(12)                            # (sensor levels: checked before anything runs)
-            if defects is not None:                          # (defect maps too)
-                if not (isinstance(f0, torch.Tensor) and f0.ndim == 2):
-                    raise TypeError("frames must be (H, bytes) uint8 tensors")
-                maps = self._batch_defects(defects, len(frames), (f0.shape[0], f0.shape[1] * 2 // 3))
+            if defects is not None or undistort is not None:     # (defect maps and lenses too)
+                shape = self._packed_shape(frames, 12)
+                maps = self._per_frame("defects", defects, len(frames), shape, _defects.check_defects)
+                lenses = self._per_frame("undistort", undistort, len(frames), shape, self._check_lens)
                 defects = maps if any(m is not None for m in maps) else None
-            if undistort is not None:                        # (lenses too)
-                if not (isinstance(f0, torch.Tensor) and f0.ndim == 2):
-                    raise TypeError("frames must be (H, bytes) uint8 tensors")
-                lenses = self._batch_lenses(undistort, len(frames), f0.shape[0], f0.shape[1] * 2 // 3)
                 undistort = lenses if any(m is not None for m in lenses) else None
+
+            def group(name, *args, tail=()):
+                """The camera-group entry point `name`; with levels its _levels twin, which takes them ahead of `tail`."""
+                if lv is None:
+                    return getattr(L, name)(*args, *tail)
+                return getattr(L, name + "_levels")(*args, lv, *tail)
+
             fused = (dtype is types.f16 and not ids_format and self.resize_width == 0 and self.scale is None
                      and self._applied_shading() is None      # (lens shading or AWB: the two calls below)
                      and self._raw_denoise is None            # (raw noise reduction: the two calls below)
@@ -1051,8 +952,7 @@ def camera_isp(name: str, dtype=types.f32):
             if fused:
                 h, w = f0.shape[0], f0.shape[1] * 2 // 3
                 with torch.cuda.device(self.device):
-                    fused = bool(L.mi_isp_camera_group_fits(h, w, self._demosaic_pattern.value, dtype.code, 8) if lv is None
-                                 else L.mi_isp_camera_group_fits_levels(h, w, self._demosaic_pattern.value, dtype.code, 8, lv))
+                    fused = bool(group("mi_isp_camera_group_fits", h, w, self._demosaic_pattern.value, dtype.code, 8))
             if not fused:
                 images = self.load_packed12_batch(frames, ids_format, defects=defects, undistort=undistort)
                 outputs = self.tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt)
@@ -1075,29 +975,19 @@ def camera_isp(name: str, dtype=types.f32):
                 args = (p_srcs, p_imgs, p_outs, n, h, w, self._demosaic_pattern.value, ccm, prev.data_ptr(), metrics.data_ptr(),
                         float(t), float(gamma), float(intensity), float(light_adapt), float(color_adapt), scratch.data_ptr(),
                         ws.data_ptr())
-                if lv is None:
-                    _native.check(L.mi_isp_camera_group_reinhard(*args, stream))
-                else:
-                    _native.check(L.mi_isp_camera_group_reinhard_levels(*args, lv, stream))
+                _native.check(group("mi_isp_camera_group_reinhard", *args, tail=(stream,)))
                 self.metrics = metrics
                 return (outputs, images) if keep_images else outputs
             # a sharded group (one process per GPU): the same three steps with the metering's two all-gathers in between
-            if lv is None:
-                _native.check(L.mi_isp_camera_group_subsample(p_srcs, n, h, w, self._demosaic_pattern.value, ccm,
-                                                              scratch.data_ptr(), stream))
-            else:
-                _native.check(L.mi_isp_camera_group_subsample_levels(p_srcs, n, h, w, self._demosaic_pattern.value, ccm,
-                                                                     scratch.data_ptr(), lv, stream))
+            _native.check(group("mi_isp_camera_group_subsample", p_srcs, n, h, w, self._demosaic_pattern.value, ccm,
+                                scratch.data_ptr(), tail=(stream,)))
             per = int(L.mi_isp_camera_group_scratch_bytes(1, h, w))
             hs, ws_ = (h + 7) // 8, (w + 7) // 8
             subs = [scratch[i * per:i * per + hs * ws_ * 6].view(torch_dtype).view(hs, ws_, 3) for i in range(n)]
             self.metrics = self._metering_images(subs, t, prev, stride=1)
             args = (p_srcs, p_imgs, p_outs, n, h, w, self._demosaic_pattern.value, ccm, self.metrics.data_ptr(), float(gamma),
                     float(intensity), float(light_adapt), float(color_adapt), ws.data_ptr())
-            if lv is None:
-                _native.check(L.mi_isp_camera_group_tonemap(*args, stream))
-            else:
-                _native.check(L.mi_isp_camera_group_tonemap_levels(*args, lv, stream))
+            _native.check(group("mi_isp_camera_group_tonemap", *args, tail=(stream,)))
             return (outputs, images) if keep_images else outputs
 
         def tonemap_linear(self, images: List[torch.Tensor], gamma: float = 1.0):

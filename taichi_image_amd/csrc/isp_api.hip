@@ -107,13 +107,9 @@ static int packed_params(tile::Params& p, const uint8_t* packed, int H, int W, i
 // sensor levels (mi_isp_levels) of a packed source: NULL leaves Params::levels 0 (the kernels without levels)
 static int apply_levels(tile::Params& p, const mi_isp_levels* lv, int bits, const char* who) {
   if (!lv) { p.levels = 0; return 0; }
-  const int top = bits == 16 ? 65535 : 4095;
-  MI_REQUIRE(lv->white > 0 && lv->white <= top, "%s: white level %d outside (0, %d]", who, (int)lv->white, top);
+  if (int rc = mi_check_levels(lv, bits == 16 ? 65535 : 4095, who, p.lv_black)) return rc;
   bool uniform = true;
   for (int s = 0; s < 4; ++s) {
-    MI_REQUIRE(lv->black[s] >= 0 && lv->black[s] < lv->white, "%s: black level %d of site %d outside [0, white = %d)", who,
-               (int)lv->black[s], s, (int)lv->white);
-    p.lv_black[s] = lv->black[s];
     p.lv_k[s] = (float)(1.0 / (double)(lv->white - lv->black[s]));       // S = 1 for the f16 / f32 work dtypes
     uniform = uniform && lv->black[s] == lv->black[0];
   }
@@ -604,13 +600,8 @@ extern "C" int mi_isp_awb_stats_cfa(const void* cfa, int H, int W, int mode, con
   if (int rc = awb_filter(s, H, W, clip, floor_, stride, pending, who)) return rc;
   if (lv) {                                           // mi_isp_load_convert_shading's levels: k[] holds the denominators
     MI_REQUIRE(mode == MI_LOAD_16U, "%s: levels apply to u16 codes only (mode %d)", who, mode);
-    MI_REQUIRE(lv->white > 0 && lv->white <= 65535, "%s: white level %d outside (0, 65535]", who, (int)lv->white);
-    for (int k = 0; k < 4; ++k) {
-      MI_REQUIRE(lv->black[k] >= 0 && lv->black[k] < lv->white, "%s: black level %d of site %d outside [0, white = %d)",
-                 who, (int)lv->black[k], k, (int)lv->white);
-      s.black[k] = lv->black[k];
-      s.k[k] = (float)(lv->white - lv->black[k]);
-    }
+    if (int rc = mi_check_levels(lv, 65535, who, s.black)) return rc;
+    for (int k = 0; k < 4; ++k) s.k[k] = (float)(lv->white - lv->black[k]);
     s.has_levels = 1;
   }
   if (int rc = apply_shading(s, sh, H, W, who)) return rc;
@@ -713,15 +704,8 @@ static int denoise_raw_impl(const void* const* src, void* const* cfa, int n, int
   } else {
     if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
       MI_REQUIRE(kind == MI_RAW_16U, "%s: levels apply to u16 codes only (source kind %d)", who, kind);
-      MI_REQUIRE(levels->white > 0 && levels->white <= 65535, "%s: white level %d outside (0, 65535]", who,
-                 (int)levels->white);
-      for (int s = 0; s < 4; ++s) {
-        MI_REQUIRE(levels->black[s] >= 0 && levels->black[s] < levels->white,
-                   "%s: black level %d of site %d outside [0, white = %d)", who, (int)levels->black[s], s,
-                   (int)levels->white);
-        a.black[s] = levels->black[s];
-        a.k[s] = (float)(levels->white - levels->black[s]);
-      }
+      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
+      for (int s = 0; s < 4; ++s) a.k[s] = (float)(levels->white - levels->black[s]);
       a.levels = 1;
     }
     src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);

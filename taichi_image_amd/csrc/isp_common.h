@@ -241,6 +241,18 @@ static inline int mi_partial_cap(int H, int W) {
   return (int)cap;
 }
 
+// the sensor levels (mi_isp_levels, not NULL) of a source whose codes reach `top`, checked on the host before anything is
+// launched: fills black[4]; the scale of a site (1 / (white - black) or white - black) is the caller's arithmetic
+static inline int mi_check_levels(const mi_isp_levels* lv, int top, const char* who, int black[4]) {
+  MI_REQUIRE(lv->white > 0 && lv->white <= top, "%s: white level %d outside (0, %d]", who, (int)lv->white, top);
+  for (int s = 0; s < 4; ++s) {
+    MI_REQUIRE(lv->black[s] >= 0 && lv->black[s] < lv->white, "%s: black level %d of site %d outside [0, white = %d)", who,
+               (int)lv->black[s], s, (int)lv->white);
+    black[s] = lv->black[s];
+  }
+  return 0;
+}
+
 // Lens shading (mi_isp_shading): the gain of raw pixel (r, c), clamped into the frame (out-of-image pixels
 // hold code 0 and take an edge gain): the node row i and column j of its cell, then G[i][j..j+1] lerped vertically first,
 // then horizontally; every operation one f32 rounding (the library builds with -ffp-contract=off), as the contract says

@@ -1561,16 +1561,9 @@ extern "C" int mi_isp_load_convert_levels(const void* src, void* dst, int H, int
   MI_REQUIRE(src && dst, "load_convert_levels: null pointer");
   MI_REQUIRE(mode == MI_LOAD_16U, "load_convert_levels: levels apply to u16 codes only (mode %d)", mode);
   MI_REQUIRE(out_dtype == MI_F16 || out_dtype == MI_F32, "load_convert_levels: output must be f16/f32");
-  MI_REQUIRE(levels->white > 0 && levels->white <= 65535, "load_convert_levels: white level %d outside (0, 65535]",
-             (int)levels->white);
   ConvLevels lv;
-  for (int s = 0; s < 4; ++s) {
-    MI_REQUIRE(levels->black[s] >= 0 && levels->black[s] < levels->white,
-               "load_convert_levels: black level %d of site %d outside [0, white = %d)", (int)levels->black[s], s,
-               (int)levels->white);
-    lv.black[s] = levels->black[s];
-    lv.den[s] = (float)(levels->white - levels->black[s]);                 // exact: < 2^24
-  }
+  if (int rc = mi_check_levels(levels, 65535, "load_convert_levels", lv.black)) return rc;
+  for (int s = 0; s < 4; ++s) lv.den[s] = (float)(levels->white - levels->black[s]);   // exact: < 2^24
   const int64_t n = (int64_t)H * W;
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
@@ -1596,15 +1589,8 @@ extern "C" int mi_isp_load_convert_shading(const void* src, void* dst, int H, in
   ConvLevels lv = {};
   if (levels) {
     MI_REQUIRE(mode == MI_LOAD_16U, "load_convert_shading: levels apply to u16 codes only (mode %d)", mode);
-    MI_REQUIRE(levels->white > 0 && levels->white <= 65535, "load_convert_shading: white level %d outside (0, 65535]",
-               (int)levels->white);
-    for (int s = 0; s < 4; ++s) {
-      MI_REQUIRE(levels->black[s] >= 0 && levels->black[s] < levels->white,
-                 "load_convert_shading: black level %d of site %d outside [0, white = %d)", (int)levels->black[s], s,
-                 (int)levels->white);
-      lv.black[s] = levels->black[s];
-      lv.den[s] = (float)(levels->white - levels->black[s]);
-    }
+    if (int rc = mi_check_levels(levels, 65535, "load_convert_shading", lv.black)) return rc;
+    for (int s = 0; s < 4; ++s) lv.den[s] = (float)(levels->white - levels->black[s]);
   }
   const int64_t n = (int64_t)H * W;
   if (n == 0) return 0;

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import isp_oracle as O
-from tests.util import assert_close, assert_exact, natural_packed12
+from tests.util import _count_calls, assert_close, assert_exact, natural_packed12
 
 pytestmark = pytest.mark.gpu
 
@@ -158,19 +158,6 @@ def test_levels_metering_and_tonemap(ti, rng, dev, cam, work):
         assert_close(isp.metrics.cpu().numpy(), m, f"metrics step {step}", rel=2e-5)
         for k, (o, r) in enumerate(zip(outs, refs)):
             assert_close(o.cpu().numpy(), O.reinhard_isp(r, m, gamma=0.6)[0], f"u8 step {step} img {k}")
-
-
-def _count_calls(monkeypatch, name):
-    """Count the calls of one library entry point (the probe that a path was taken)."""
-    from taichi_image_amd import _native
-    L = _native.lib()
-    fn, calls = getattr(L, name), []
-
-    def counted(*args):
-        calls.append(name)
-        return fn(*args)
-    monkeypatch.setattr(L, name, counted)
-    return calls
 
 
 @pytest.mark.parametrize("pattern,black", [(O.RGGB, PER_SITE), (O.GBRG, 128)])

@@ -11,8 +11,8 @@ import pytest
 import torch
 
 from oracle import isp_oracle as O
-from tests.test_gpu_shading import _count_calls, make_grid, pixel_gains, ref_load, site_levels
-from tests.util import assert_close, assert_exact, natural_packed12
+from tests.test_gpu_shading import make_grid, pixel_gains, ref_load, site_levels
+from tests.util import _count_calls, assert_close, assert_exact, natural_packed12
 
 pytestmark = pytest.mark.gpu
 

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import isp_oracle as O
-from tests.util import assert_close, assert_exact, natural_packed12
+from tests.util import _count_calls, assert_close, assert_exact, natural_packed12
 
 pytestmark = pytest.mark.gpu
 
@@ -239,18 +239,6 @@ def test_shading_metering_and_tonemap(ti, rng, dev, cam, work):
         assert_close(isp.metrics.cpu().numpy(), m, f"metrics step {step}", rel=2e-5)
         for k, (o, r) in enumerate(zip(outs, refs)):
             assert_close(o.cpu().numpy(), O.reinhard_isp(r, m, gamma=0.6)[0], f"u8 step {step} img {k}")
-
-
-def _count_calls(monkeypatch, name):
-    from taichi_image_amd import _native
-    L = _native.lib()
-    fn, calls = getattr(L, name), []
-
-    def counted(*args):
-        calls.append(name)
-        return fn(*args)
-    monkeypatch.setattr(L, name, counted)
-    return calls
 
 
 def test_process_packed12_shading_4k(ti, rng, dev, monkeypatch):

@@ -53,6 +53,19 @@ def assert_close(got, ref, what="", rel=1e-4, max_bad_frac=0.0):
     return float(err[~nan_r].max()) if (~nan_r).any() else 0.0
 
 
+def _count_calls(monkeypatch, name):
+    """Count the calls of one library entry point (the probe that a path was taken)."""
+    from taichi_image_amd import _native
+    L = _native.lib()
+    fn, calls = getattr(L, name), []
+
+    def counted(*args):
+        calls.append(name)
+        return fn(*args)
+    monkeypatch.setattr(L, name, counted)
+    return calls
+
+
 def random_cfa(rng, H, W, dtype):
     if dtype == "u8":
         return rng.integers(0, 256, (H, W)).astype(np.uint8)
