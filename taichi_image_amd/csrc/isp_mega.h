@@ -477,6 +477,97 @@ template <int K> MI_DEV float gray_pk(const uint32_t (&pk)[12], float w0, float 
   return fma_mix_h<e + 2>(pk[(e + 2) / 2], w2, b);
 }
 
+// ---- two pixels per VALU instruction (v_pk_mul_f32 / v_pk_fma_f32) ----
+// A packed f32 instruction produces two IEEE results, each the bits of the scalar instruction on the same operands, in one
+// issue slot of the wave and two slots of the pipe.  Measured (DESIGN.md 5.0 "The per-wave issue bound",
+// profiles/packed_f32_bench.txt): a fifth fewer VALU instructions per wave bought 4.3 % of the frame - 44.52 -> 43.90 us with
+// phase A on pairs, -> 42.61 with phase C as well; the wave's issue port is not the binding limit, the pairs buy the FMA's
+// pipe rate (2.08 cycles per result against 2.4 - 2.75) and the slots that SALU, waits and hazards take.  Outputs K and K + 4 of a lane's eight pixels sit on the same CFA
+// site: same taps, same weights, window columns four apart.  The window row therefore lives as the eight aligned pairs
+// {v[j], v[j + 4]} (columns 4..7 are held twice: 16 registers per row instead of 12) and accumulator pair 3 K + ch holds
+// channel ch of pixels K and K + 4.  Per chain the operations and their order are those of strm::accumulate_row<EXACT>:
+// first tap x * w, every further tap fma(x, w, acc).
+typedef float f2 __attribute__((ext_vector_type(2)));
+struct WinRow2 { f2 p[8]; };
+
+// strm::decode_row (LUT decode) into the paired layout
+MI_DEV void decode_row2(const uint32_t (&d)[4], const float (&lut)[4096], int lane, WinRow2& row) {
+  uint32_t v[8];
+  tile::unpack12x8(d[0], d[1], d[2], false, v);
+  const uint32_t w = lane == 0 ? d[3] >> 8 : d[3] & 0xFFFFFFu;
+  float own[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) own[i] = lut[v[i]];
+  const float x0 = lut[w & 0xFFFu], x1 = lut[w >> 12];
+  row.p[0] = f2{from_left(own[6], x0), own[2]};
+  row.p[1] = f2{from_left(own[7], x1), own[3]};
+  row.p[2] = f2{own[0], own[4]};
+  row.p[3] = f2{own[1], own[5]};
+  row.p[4] = f2{own[2], own[6]};
+  row.p[5] = f2{own[3], own[7]};
+  row.p[6] = f2{own[4], from_right(own[0], x0)};
+  row.p[7] = f2{own[5], from_right(own[1], x1)};
+}
+
+// A uniform operand of a packed instruction: half H of a register pair for both results.  The compiler folds the splat
+// into the instruction's op_sel bits - no copy, no second register.  (Plain C on purpose: around inline asm it pads with
+// conservative s_nop, ~175 per wave in phase A.)
+template <int H> MI_DEV f2 bc(f2 u) { return __builtin_shufflevector(u, u, H, H); }
+
+// strm::accumulate_row<PR, PC, I, true> on the paired window: v2[3 K + ch] = channel ch of pixels {K, K + 4}
+template <int PR, int PC, int I>
+MI_DEV void accumulate_row2(const WinRow2 (&win)[6], const f2 (&wq2)[4], f2 (&v2)[12]) {
+  bool first[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) first[j] = true;
+  static_for<0, 13>([&](auto tc) {
+    constexpr int t = decltype(tc)::value;
+    constexpr int row = I + 2 + tile::TAP_DR[t];
+    static_for<0, 4>([&](auto kc) {
+      constexpr int K = decltype(kc)::value;
+      constexpr int KIDX = ((I + PR) & 1) + 2 * ((K + PC) & 1);
+      constexpr int col = K + 2 + tile::TAP_DC[t];
+      static_for<0, 3>([&](auto cc) {
+        constexpr int ch = decltype(cc)::value;
+        constexpr int wi = tile::KW[KIDX][t][ch];
+        if constexpr (wi != 0) {
+          f2& acc = v2[3 * K + ch];
+          constexpr int WI = tile::wq_index(wi);        // weight WI = half WI & 1 of pair WI >> 1
+          const f2 w = bc<WI & 1>(wq2[WI >> 1]), x = win[row].p[col];
+          if (first[3 * K + ch]) acc = x * w;                                // v_pk_mul_f32
+          else acc = __builtin_elementwise_fma(x, w, acc);                   // v_pk_fma_f32
+          first[3 * K + ch] = false;
+        }
+      });
+    });
+  });
+}
+
+// ---- Reinhard with color_adapt == 0 on a pixel pair: isp_math.h's reinhard_adapt_ca0 / reinhard_map / norm01, operation
+// for operation (this header is compiled with contraction off: every product, sum and fma below is the one written there);
+// the transcendentals, min / max and the clamp stay one value per instruction.  The uniform operands share register pairs.
+// The gray weights are compile-time constants: the compiler keeps them in scalar register pairs (a packed instruction
+// takes one scalar pair at no extra cost), so the pairs below are the six registers the scalar form's operands take.
+struct ReinhardK2 {
+  f2 ml, ek, li;                       // {mean, la}, {ei, map_key}, {lo, inv}
+};
+MI_DEV f2 norm01_2(f2 x, const ReinhardK2& k) {
+  const f2 d = (x - bc<0>(k.li)) * bc<1>(k.li);
+  return f2{clamp01(d.x), clamp01(d.y)};
+}
+MI_DEV f2 reinhard_adapt2(const f2 (&t)[3], const ReinhardK2& k) {
+  const f2 w01 = {0.587f, 0.299f}, w2 = {0.114f, 0.114f};
+  const f2 g = __builtin_elementwise_fma(t[2], w2, __builtin_elementwise_fma(t[0], bc<1>(w01), t[1] * bc<0>(w01)));
+  const f2 am = __builtin_elementwise_fma(bc<1>(k.ml), g - bc<0>(k.ml), bc<0>(k.ml));
+  const f2 b = bc<0>(k.ek) * am;
+  const f2 e = bc<1>(k.ek) * f2{hw_log2(b.x), hw_log2(b.y)};
+  return f2{hw_exp2(e.x), hw_exp2(e.y)};
+}
+MI_DEV f2 reinhard_map2(f2 t, f2 ad) {
+  const f2 s = ad + t;
+  return t * f2{hw_rcp(s.x), hw_rcp(s.y)};
+}
+
 // "Defines" registers without an instruction.  The resident rows are written and read under wave-uniform conditions (a
 // band may end before its 12th row).  Inside the frame loop a variable that is assigned under a condition carries, for
 // the compiler, its value of the PREVIOUS frame along the other arm - all 252 registers of resident rows would be live
@@ -540,6 +631,16 @@ MI_DEV float pk_hi(uint32_t v) { half_t h[2]; __builtin_memcpy(h, &v, 4); return
 // which cost 3.3 us per frame (58.2 -> 54.9).  Split, every variant fits 256 VGPRs without scratch - as long as the
 // Reinhard dispatch below stays a run-time branch on `ca0` (made compile-time, the RGB = false kernel spilled 17):
 // tests/test_abi.py::test_whole_frame_kernel_uses_no_scratch compiles the kernels and checks.
+//
+// Which of the eight kernels computes on pixel pairs (PKA: the demosaic of phase A; PKC: the color_adapt == 0 Reinhard of
+// phases C and D) - decided by the registers, the count is what the kernel spilled to scratch with the form it does not have:
+//   (PR, PC)         RGB = false              RGB = true (color_adapt != 0)
+//   (0, 0) RGGB      PKA + PKC                scalar (PKA: 16 VGPRs spilled; its color_adapt == 0 arm never runs)
+//   (0, 1) GRBG      PKC (PKA: 5 spilled)     scalar
+//   (1, 0) GBRG      PKA + PKC                scalar
+//   (1, 1) BGGR      PKA + PKC                scalar
+// In every PKC kernel the one LDS row mapped between post 2 and its poll stays scalar (on pairs: 8 spilled around the fold).
+// The results are the same bits in every form.
 // (A variant without the row conditions for frames whose height is a multiple of 12 was tried: with no branches between
 // them the phases' rows become one scheduling region, and the scheduler's reordering cost 225 - 279 spills.  The
 // conditions stay.)
@@ -661,14 +762,21 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
   // ================================ phase A: demosaic once ================================
   // The uniform operands of a phase are set up at ITS start, every frame (vgpr() is opaque, so they are neither hoisted
   // out of the frame loop nor kept alive through the other phases: this kernel has no registers to park them in).
-  float wq[8];
+  // PKA: the demosaic on pixel pairs (accumulate_row2); the paired window takes 24 registers more (table at the kernel's head)
+  constexpr bool PKA = !RGB && !(PR == 0 && PC == 1);
+  f2 wq2[4];                                          // the eight weights: wq2[i >> 1][i & 1]
 #pragma unroll
-  for (int i = 0; i < 8; ++i) wq[i] = vgpr(wq_value(i));
+  for (int i = 0; i < 4; ++i) wq2[i] = f2{vgpr(wq_value(2 * i)), vgpr(wq_value(2 * i + 1))};
   const float gw0 = vgpr(0.299f), gw1 = vgpr(0.587f), gw2 = vgpr(0.114f);
-  WinRow win[6];
+  typedef std::conditional_t<PKA, WinRow2, WinRow> Win;
+  Win win[6];
+  auto decode = [&](const uint32_t (&d)[4], Win& row) {
+    if constexpr (PKA) decode_row2(d, lut, lane, row);
+    else decode_row(d, lut, lane, row);
+  };
   uint32_t xr[NR][12];                                // resident rows NL..ROWS-1 (packed f16 pairs)
 #pragma unroll
-  for (int q = 0; q < 4; ++q) decode_row(pro[q], lut, lane, win[q]);
+  for (int q = 0; q < 4; ++q) decode(pro[q], win[q]);
   MI_CMARK(10);
 #if defined(MI_STREAM_STAMPS) && !defined(MI_STAMP_HWID)
   if (lane == 0 && wave_ok) st_[15] = MI_STAMP_NOW();      // prologue done: first four rows decoded
@@ -679,8 +787,8 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
   static_for<0, ROWS / 2>([&](auto ibc) {
     constexpr int IB = decltype(ibc)::value, PH = IB % 3;
     const int r = r_begin + 2 * IB;
-    decode_row(raw[IB % 2][0], lut, lane, win[(2 * PH + 4) % 6]);
-    decode_row(raw[IB % 2][1], lut, lane, win[(2 * PH + 5) % 6]);
+    decode(raw[IB % 2][0], win[(2 * PH + 4) % 6]);
+    decode(raw[IB % 2][1], win[(2 * PH + 5) % 6]);
     if constexpr (IB + 2 < ROWS / 2) {
       load_row(G, rsrc, r + 6, raw[IB % 2][0]);
       load_row(G, rsrc, r + 7, raw[IB % 2][1]);
@@ -691,7 +799,7 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
     if constexpr (2 * IB >= NL) fresh(xr[2 * IB - NL]);
     if constexpr (2 * IB + 1 >= NL) fresh(xr[2 * IB + 1 - NL]);
     if (r < r_end) {                          // wave-uniform
-      WinRow w6[6];
+      Win w6[6];
 #pragma unroll
       for (int k = 0; k < 6; ++k) w6[k] = win[(2 * PH + k) % 6];
       static_for<0, 2>([&](auto ic) {
@@ -699,7 +807,17 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
         const int row = r + I;
         prio_turn(RR, younger);
         float v[24];
-        accumulate_row<PR, PC, I, true>(w6, wq, v);
+        if constexpr (PKA) {
+          f2 v2[12];
+          accumulate_row2<PR, PC, I>(w6, wq2, v2);
+#pragma unroll
+          for (int j = 0; j < 12; ++j) { v[j] = v2[j].x; v[12 + j] = v2[j].y; }   // pixel K: the low halves, K + 4: the high ones
+        } else {
+          float wq[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) wq[i] = wq2[i >> 1][i & 1];
+          accumulate_row<PR, PC, I, true>(w6, wq, v);
+        }
         if (MI_CENSUS(row < 2 || row >= p.H - 2, false)) border_fix_rows<PR, PC, I>(v, tile::inside_mask(row, p.H), is_left, is_right);
         else if (MI_CENSUS(any_left || any_right, false)) border_fix_cols<PR, PC, I>(v, is_left, is_right, any_left, any_right);
         if (MI_CENSUS(p.has_ccm, false)) {            // bayer.py:152-153, sequential fp32 dot
@@ -767,7 +885,12 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
       __builtin_memcpy(pk, mine, sizeof(mine));
     } else {
 #pragma unroll
-      for (int j = 0; j < 12; ++j) pk[j] = xr[RR - NL][j];
+      for (int j = 0; j < 12; ++j) {
+        pk[j] = xr[RR - NL][j];
+        // (opaque: with the paired Reinhard below the compiler otherwise splits the last register row into its f16 halves
+        // back in phase A - twelve shifts whose results it then spills across the barrier)
+        if constexpr (!RGB) asm volatile("" : "+v"(pk[j]));
+      }
     }
   };
   auto resident = [&](auto rrc, float (&t)[24]) {
@@ -787,7 +910,8 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
   const float lo_s = sh_fp[FP_LO], inv_s = sh_fp[FP_INV];
   const bool unit = MI_CENSUS(lo_s == 0.f && inv_s == 1.f, true);
   // per-pixel operands live in VGPRs: a VALU instruction with an SGPR operand issues at half rate
-  const float lo = vgpr(lo_s), inv = vgpr(inv_s);
+  const f2 lo_inv = {vgpr(lo_s), vgpr(inv_s)};          // (a pair: the packed Reinhard below takes both from it)
+  const float lo = lo_inv.x, inv = lo_inv.y;
   // the normalisation of tonemap.py:13 in phases C and D; only frames whose bounds are not (0, 1) come here.  (As ONE fma,
   // x * inv - lo * inv, measured on one box, unit / non-unit frames: 44.05 / 50.13 us with it, 43.81 / 50.90 without - the
   // frames it is not executed for pay 0.24 us for the other arm's different register allocation.  Not taken: the headline
@@ -826,9 +950,20 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
   MI_MSTAMP(4);
   ReinhardK rk;
   const bool ca0 = MI_CENSUS(p.ca == 0.f, true);        // runtime on purpose: see the note on register allocation at the kernel's head
-  rk.la = vgpr(p.la);
-  rk.map_key = vgpr(sh_fp[FP_MAPKEY]); rk.ei = vgpr(sh_fp[FP_EI]);
-  rk.mean3[0] = vgpr(sh_fp[FP_MEAN3]);
+  // PKC: Reinhard on pixel pairs {k, k + 4} in phases C and D - the color_adapt == 0 arm of the RGB = false kernels (the
+  // other kernels hold that arm too, but have no register to spare).  The scalar operands are then halves of the pairs.
+  constexpr bool PKC = !RGB;
+  ReinhardK2 k2;
+  if constexpr (PKC) {
+    k2.ml = f2{vgpr(sh_fp[FP_MEAN3]), vgpr(p.la)};
+    k2.ek = f2{vgpr(sh_fp[FP_EI]), vgpr(sh_fp[FP_MAPKEY])};
+    k2.li = lo_inv;
+    rk.la = k2.ml.y; rk.map_key = k2.ek.y; rk.ei = k2.ek.x; rk.mean3[0] = k2.ml.x;
+  } else {
+    rk.la = vgpr(p.la);
+    rk.map_key = vgpr(sh_fp[FP_MAPKEY]); rk.ei = vgpr(sh_fp[FP_EI]);
+    rk.mean3[0] = vgpr(sh_fp[FP_MEAN3]);
+  }
   if constexpr (RGB) {
     rk.ca = vgpr(p.ca); rk.mean3[1] = vgpr(sh_fp[FP_MEAN3 + 1]); rk.mean3[2] = vgpr(sh_fp[FP_MEAN3 + 2]);
   } else {
@@ -844,19 +979,39 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
   // (Measured and taken out, round 4 - profiles/r04_barrier_and_phaseC_experiments.txt: the Reinhard chains of 2 or 4
   // pixels in LOCKSTEP, stage by stage between scheduling barriers.  The 146 hazard s_nop of phase C went, the time did
   // not: 44.19 - 44.44 against 44.30 us per frame - with two waves per SIMD the other wave already fills the slots a
-  // dependent chain leaves open; phase C's ~10 us are its instruction count (440 transcendentals at 7.4 cycles, ~610
-  // single-rate and ~1260 double-rate instructions per wave), not its order.  Likewise the gray of the resident pixels
+  // dependent chain leaves open; phase C's ~10 us were its instruction mix (then: 440 transcendentals at 7.4 cycles, ~610
+  // single-rate and ~1260 double-rate instructions per wave), not its order.  On pixel pairs (PKC,
+  // profiles/packed_f32_census.txt) the phase is 2379 instructions per wave: the same 440 transcendentals, 584 v_pk_mul /
+  // add / fma_f32 in place of 1088 scalar ones, 288 conversions, 308 min / max, 333 s_nop.  Likewise the gray of the resident pixels
   // computed ahead, in barrier 0's wait: two rows' worth fit the registers, nothing measurable.)
-  auto tone_row = [&](auto unit_c, auto ca0_c, const float (&t)[24], float (&q)[24]) {
+  auto tone_row = [&](auto unit_c, auto ca0_c, const float (&t)[24], float (&q)[24], auto pairs_c) {
     constexpr bool UNIT = decltype(unit_c)::value, CA0 = decltype(ca0_c)::value;
+    if constexpr (PKC && CA0 && decltype(pairs_c)::value) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float x[3], o[3];
+      for (int k = 0; k < 4; ++k) {
+        f2 x[3];
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) x[ch] = UNIT ? t[3 * k + ch] : norm_fma(t[3 * k + ch]);
-      reinhard_px<CA0>(x, rk, o);
+        for (int ch = 0; ch < 3; ++ch) {
+          x[ch] = f2{t[3 * k + ch], t[3 * k + 12 + ch]};
+          if constexpr (!UNIT) x[ch] = norm01_2(x[ch], k2);
+        }
+        const f2 ad = reinhard_adapt2(x, k2);
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) q[3 * k + ch] = o[ch];
+        for (int ch = 0; ch < 3; ++ch) {
+          const f2 o = reinhard_map2(x[ch], ad);
+          q[3 * k + ch] = o.x; q[3 * k + 12 + ch] = o.y;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        float x[3], o[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) x[ch] = UNIT ? t[3 * k + ch] : norm_fma(t[3 * k + ch]);
+        reinhard_px<CA0>(x, rk, o);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) q[3 * k + ch] = o[ch];
+      }
     }
   };
   auto dispatch = [&](auto&& phase) {
@@ -881,15 +1036,33 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
   // bit the bound can differ from the three-channel one by an ulp - the scalars' contract is 1e-4).
   auto tone_bounds_row = [&](auto unit_c, const float (&t)[24]) {
     constexpr bool UNIT = decltype(unit_c)::value;
+    if constexpr (PKC) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float x[3];
+      for (int k = 0; k < 4; ++k) {
+        f2 x[3];
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) x[ch] = UNIT ? t[3 * k + ch] : norm_fma(t[3 * k + ch]);
-      const float ad = reinhard_adapt_ca0(x, rk);         // (the very function phase D evaluates again)
-      const float xmin = fminf(x[0], fminf(x[1], x[2])), xmax = fmaxf(x[0], fmaxf(x[1], x[2]));
-      vmin = fminf(vmin, reinhard_map(xmin, ad));
-      vmax = fmaxf(vmax, reinhard_map(xmax, ad));
+        for (int ch = 0; ch < 3; ++ch) {
+          x[ch] = f2{t[3 * k + ch], t[3 * k + 12 + ch]};
+          if constexpr (!UNIT) x[ch] = norm01_2(x[ch], k2);
+        }
+        const f2 ad = reinhard_adapt2(x, k2);             // (the very function phase D evaluates again)
+        const f2 xmin = {fminf(x[0].x, fminf(x[1].x, x[2].x)), fminf(x[0].y, fminf(x[1].y, x[2].y))};
+        const f2 xmax = {fmaxf(x[0].x, fmaxf(x[1].x, x[2].x)), fmaxf(x[0].y, fmaxf(x[1].y, x[2].y))};
+        const f2 qmin = reinhard_map2(xmin, ad), qmax = reinhard_map2(xmax, ad);
+        vmin = fminf(vmin, fminf(qmin.x, qmin.y));
+        vmax = fmaxf(vmax, fmaxf(qmax.x, qmax.y));
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        float x[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) x[ch] = UNIT ? t[3 * k + ch] : norm_fma(t[3 * k + ch]);
+        const float ad = reinhard_adapt_ca0(x, rk);         // (the very function phase D evaluates again)
+        const float xmin = fminf(x[0], fminf(x[1], x[2])), xmax = fmaxf(x[0], fmaxf(x[1], x[2]));
+        vmin = fminf(vmin, reinhard_map(xmin, ad));
+        vmax = fmaxf(vmax, reinhard_map(xmax, ad));
+      }
     }
   };
   static_for<0, ROWS>([&](auto rrc) {
@@ -904,7 +1077,7 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
         else tone_bounds_row(std::false_type{}, t);
       } else {
         float q[24];
-        dispatch([&](auto unit_c, auto ca0_c) { tone_row(unit_c, ca0_c, t, q); });
+        dispatch([&](auto unit_c, auto ca0_c) { tone_row(unit_c, ca0_c, t, q, std::true_type{}); });
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           vmin = fminf(vmin, fminf(q[3 * k], fminf(q[3 * k + 1], q[3 * k + 2])));
@@ -939,7 +1112,8 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
       if (r_begin + RR < r_end) {
         float t[24];
         resident(rrc, t);
-        tone_row(unit_c, ca0_c, t, qpre[RR]);
+        // (one value per instruction: on pairs, this row's registers around the barrier's fold cost 8 VGPRs spilled to scratch)
+        tone_row(unit_c, ca0_c, t, qpre[RR], std::false_type{});
       }
     });
   });
@@ -997,7 +1171,7 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
         if (r_begin + RR < r_end) {
           float t[24], q[24];
           resident(rrc, t);
-          tone_row(unit_c, ca0_c, t, q);
+          tone_row(unit_c, ca0_c, t, q, std::true_type{});
           finish_row(rrc, q);
         }
         // the next frame's first rows are asked for while the last rows of this one are mapped and stored (unconditional -
