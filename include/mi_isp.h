@@ -388,6 +388,25 @@ int mi_isp_denoise_raw_batch(const void* const* src_host, void* const* cfa_host,
                              const mi_isp_denoise* denoise_host, void* stream);
 int mi_isp_denoise_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, const mi_isp_denoise* denoise_host,
                        void* stream);
+/* ---- output sharpening ("Output sharpening") ----------------------------------------------------------
+ * An unsharp mask on the luma of a u8 image, in integer arithmetic: the output is the contract's bit for bit.  All values
+ * signed 32-bit, >> arithmetic, coordinates outside the image clamped to the edge; b = (1, 2, 1) for radius 1 and
+ * (1, 4, 6, 4, 1) for radius 2, S = (sum b)^2 (16 or 256), k = 6 + log2 S, A = amount_q6 (the amount times 64, 0 .. 512):
+ *   L = (77 R + 150 G + 29 B + 128) >> 8;  Bl = sum_ij b[i] b[j] L(y + i - r, x + j - r);  d = S L - Bl
+ *   d' = sign(d) max(|d| - threshold S, 0);  delta = (A d' + (1 << (k - 1))) >> k
+ *   overshoot >= 0:  delta = clamp(L + delta, min3x3(L) - overshoot, max3x3(L) + overshoot) - L
+ *   out_c = clamp(I_c + delta, 0, 255) for c = R, G, B
+ *  - mi_isp_sharpen_rgb_batch: n interleaved H x W x 3 images of one geometry, one launch per 32 images.
+ *  - mi_isp_sharpen_yuv420_batch: n planar YUV 4:2:0 images (H * 3 / 2 rows of W bytes; H, W of the Y plane, H even): the
+ *    filter with L = Y, out = clamp(Y + delta, 0, 255); the chroma rows are copied.
+ * src_host / dst_host: n device pointers each, read on the host.  The stencil cannot run in place: src[i] != dst[i], and
+ * the images must not overlap.  Host-side checks before any launch (error text names "sharpen"): the settings' ranges,
+ * n >= 1, H, W >= 0, NULL pointers, src == dst.  H * W == 0 is a successful no-op. */
+typedef struct { int32_t amount_q6, radius, threshold, overshoot /* -1: none */; } mi_isp_sharpen;
+int mi_isp_sharpen_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                             const mi_isp_sharpen* sharpen_host, void* stream);
+int mi_isp_sharpen_yuv420_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                                const mi_isp_sharpen* sharpen_host, void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==

@@ -52,6 +52,12 @@ class Denoise(ctypes.Structure):
                 ("radius", c_int32)]
 
 
+class Sharpen(ctypes.Structure):
+    """mi_isp_sharpen: the output sharpening filter's amount times 64 (0 .. 512), radius (1 or 2), coring threshold
+    (0 .. 255) and halo clamp overshoot (0 .. 255, -1: none)."""
+    _fields_ = [("amount_q6", c_int32), ("radius", c_int32), ("threshold", c_int32), ("overshoot", c_int32)]
+
+
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SIGNATURES = {
@@ -130,6 +136,8 @@ SIGNATURES = {
     "mi_isp_denoise_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
                                          POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Denoise), _P]),
     "mi_isp_denoise_cfa": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(Denoise), _P]),
+    "mi_isp_sharpen_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(Sharpen), _P]),
+    "mi_isp_sharpen_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(Sharpen), _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,

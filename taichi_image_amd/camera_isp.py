@@ -23,6 +23,7 @@ from . import _native, bayer, interpolate, packed, types
 from . import defects as _defects
 from . import denoise as _dn
 from . import lens as _lens
+from . import sharpen as _shp
 from . import white_balance as _wb
 from . import distributed as _dist
 
@@ -278,7 +279,8 @@ def camera_isp(name: str, dtype=types.f32):
                      white_level: Optional[int] = None,
                      lens_shading=None,
                      auto_white_balance=False,
-                     raw_denoise=None):
+                     raw_denoise=None,
+                     sharpen=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -295,6 +297,7 @@ def camera_isp(name: str, dtype=types.f32):
             if awb is not None:
                 _wb.check_seed(white_balance)
             raw_denoise = _dn.check_raw_denoise(raw_denoise)
+            sharpen = _shp.check_sharpen(sharpen)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -340,6 +343,9 @@ def camera_isp(name: str, dtype=types.f32):
             # raw noise reduction (an extension): the RawDenoise of this sensor, or None (the loaders run exactly as
             # without it).  DESIGN.md 3, "Raw noise reduction".
             self._raw_denoise = raw_denoise
+            # output sharpening (an extension): the Sharpen applied to every u8 output of the tonemaps, or None (the
+            # tonemaps run exactly as without it).  DESIGN.md 3, "Output sharpening".
+            self._sharpen = sharpen
 
         @property
         def _demosaic_pattern(self):
@@ -352,7 +358,7 @@ def camera_isp(name: str, dtype=types.f32):
                 color_correction: Optional[np.ndarray] = None,
                 transform: Optional[interpolate.ImageTransform] = None,
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
-                raw_denoise=None):
+                raw_denoise=None, sharpen=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -362,7 +368,8 @@ def camera_isp(name: str, dtype=types.f32):
             one that never had it does); True or an AutoWhiteBalance turns it on and seeds it: gains f32(white_balance),
             no state, no pending statistics.  white_balance= while it is on seeds it again; lens_shading= while it is on
             rebuilds the effective grid from the new grid and the current gains on the device.
-            raw_denoise (the extension): None leaves it, False turns it off, a RawDenoise replaces it."""
+            raw_denoise (the extension): None leaves it, False turns it off, a RawDenoise replaces it.
+            sharpen (the extension): None leaves it, False turns it off, a Sharpen replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -371,6 +378,7 @@ def camera_isp(name: str, dtype=types.f32):
             if awb is not None and (auto_white_balance is not None or white_balance is not None):
                 _wb.check_seed(self.white_balance if white_balance is None else white_balance)
             denoise = None if raw_denoise is None or raw_denoise is False else _dn.check_raw_denoise(raw_denoise)
+            new_sharpen = None if sharpen is None or sharpen is False else _shp.check_sharpen(sharpen)
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -415,6 +423,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._raw_denoise = None
             elif denoise is not None:
                 self._raw_denoise = denoise
+            if sharpen is False:
+                self._sharpen = None
+            elif new_sharpen is not None:
+                self._sharpen = new_sharpen
             if auto_white_balance is not None:
                 if awb is None:
                     self._awb_off()
@@ -506,6 +518,19 @@ def camera_isp(name: str, dtype=types.f32):
                 if a is not None:
                     _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, a, stream))
             return cfas
+
+        @property
+        def sharpen(self) -> Optional[_shp.Sharpen]:
+            """The Sharpen the tonemaps apply to their u8 outputs, or None."""
+            return self._sharpen
+
+        def _sharpened(self, outputs, yuv420=False):
+            """The u8 outputs of a tonemap as the caller gets them: with sharpening on, new tensors holding the filter of
+            `outputs` (which were then the tonemap's temporaries; one launch behind it on the same stream), else
+            `outputs` themselves.  DESIGN.md 3, "Output sharpening"."""
+            if self._sharpen is None or not outputs:
+                return outputs
+            return _shp.apply(outputs, self._sharpen, yuv420)
 
         @property
         def lens_shading(self) -> Optional[torch.Tensor]:
@@ -835,7 +860,7 @@ def camera_isp(name: str, dtype=types.f32):
             """camera_isp.py:387-390."""
             output = torch.empty(_out_shape(image, self.transform), dtype=torch.uint8, device=self.device)
             reinhard_kernel(image, output, metrics, gamma, intensity, light_adapt, color_adapt, self.transform)
-            return output
+            return self._sharpened([output])[0]
 
         def tonemap_reinhard(self, images: List[torch.Tensor],
                              gamma: float = 1.0, intensity: float = 1.0, light_adapt: float = 1.0,
@@ -844,6 +869,10 @@ def camera_isp(name: str, dtype=types.f32):
             with the Reinhard-mapped values (camera_isp.py:211).
             write_back=False (an extension, not the reference's semantics): the same u8 outputs, bit for bit, with the
             images left as they are - a third of the tonemap's memory traffic is that write and its re-read."""
+            return self._sharpened(self._tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt, write_back))
+
+        def _tonemap_reinhard(self, images, gamma, intensity, light_adapt, color_adapt, write_back=True):
+            """tonemap_reinhard before output sharpening."""
             _typecheck("write_back", write_back, bool)
             _typecheck("images", images, list)
             for n, v in (("gamma", gamma), ("intensity", intensity), ("light_adapt", light_adapt),
@@ -872,13 +901,15 @@ def camera_isp(name: str, dtype=types.f32):
             """Extension (not in the reference): `[color.rgb_yuv420_image(o) for o in tonemap_reinhard(images, ...)]`
             - planar YUV 4:2:0 u8 `(H * 3 / 2, W)` per image for video encoders - with the conversion
             (color/yuv_420.py:39-66) fused into the second Reinhard pass when no orientation transform is set
-            and W % 16 == 0: the u8 RGB images are never written.  Same side effects as tonemap_reinhard."""
+            and W % 16 == 0: the u8 RGB images are never written.  Same side effects as tonemap_reinhard.
+            With sharpen= set, the Y plane of each YUV image is sharpened (sharpen.unsharp_mask_yuv420), which is not the
+            YUV image of a sharpened RGB output."""
             from . import color
             _typecheck("images", images, list)
             H, W = images[0].shape[:2]
             if self.transform != interpolate.ImageTransform.none or H % 2 or W % 16:
-                return [color.rgb_yuv420_image(o) for o in self.tonemap_reinhard(images, gamma, intensity,
-                                                                                  light_adapt, color_adapt)]
+                return self._sharpened([color.rgb_yuv420_image(o) for o in self._tonemap_reinhard(
+                    images, gamma, intensity, light_adapt, color_adapt)], yuv420=True)
             for n, v in (("gamma", gamma), ("intensity", intensity), ("light_adapt", light_adapt),
                          ("color_adapt", color_adapt)):
                 _typecheck(n, v, float)
@@ -890,7 +921,7 @@ def camera_isp(name: str, dtype=types.f32):
                 self.metrics.data_ptr(), float(gamma), float(intensity), float(light_adapt), float(color_adapt),
                 ws.data_ptr(), _native.stream_ptr(self.device)))
             _written_in_place(images)
-            return outputs
+            return self._sharpened(outputs, yuv420=True)
 
         def process_packed12(self, frames: List[torch.Tensor], gamma: float = 1.0, intensity: float = 1.0,
                              light_adapt: float = 1.0, color_adapt: float = 0.0, keep_images: bool = False,
@@ -977,6 +1008,7 @@ def camera_isp(name: str, dtype=types.f32):
                         ws.data_ptr())
                 _native.check(group("mi_isp_camera_group_reinhard", *args, tail=(stream,)))
                 self.metrics = metrics
+                outputs = self._sharpened(outputs)
                 return (outputs, images) if keep_images else outputs
             # a sharded group (one process per GPU): the same three steps with the metering's two all-gathers in between
             _native.check(group("mi_isp_camera_group_subsample", p_srcs, n, h, w, self._demosaic_pattern.value, ccm,
@@ -988,6 +1020,7 @@ def camera_isp(name: str, dtype=types.f32):
             args = (p_srcs, p_imgs, p_outs, n, h, w, self._demosaic_pattern.value, ccm, self.metrics.data_ptr(), float(gamma),
                     float(intensity), float(light_adapt), float(color_adapt), ws.data_ptr())
             _native.check(group("mi_isp_camera_group_tonemap", *args, tail=(stream,)))
+            outputs = self._sharpened(outputs)
             return (outputs, images) if keep_images else outputs
 
         def tonemap_linear(self, images: List[torch.Tensor], gamma: float = 1.0):
@@ -1004,7 +1037,7 @@ def camera_isp(name: str, dtype=types.f32):
                 _native.ptr_array(images), _native.ptr_array(outputs), len(images), H, W, dtype.code,
                 self.metrics.data_ptr(), float(gamma), interpolate.transform_code(self.transform), ws.data_ptr(),
                 _native.stream_ptr(self.device)))
-            return outputs
+            return self._sharpened(outputs)
 
     ISP.reinhard_kernel = staticmethod(reinhard_kernel)
     ISP.linear_kernel = staticmethod(linear_kernel)

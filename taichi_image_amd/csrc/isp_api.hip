@@ -15,6 +15,7 @@
 #include "isp_lens.h"
 #include "isp_awb.h"
 #include "isp_denoise.h"
+#include "isp_sharpen.h"
 #include <mutex>
 #include <atomic>
 
@@ -27,7 +28,7 @@ void mi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int mi_isp_version(void) { return 1700; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
+extern "C" int mi_isp_version(void) { return 1800; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
 extern "C" const char* mi_isp_last_error(void) { return g_err; }
 
 extern "C" int mi_isp_bayer_weights(int32_t out[4 * 13 * 3]) {
@@ -756,6 +757,55 @@ extern "C" int mi_isp_denoise_cfa(const void* in, void* out, int H, int W, int d
   a.n_frames = 1;
   a.f[0] = {in, out, nullptr};
   return dn::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype, denoise->radius, (hipStream_t)stream);
+}
+
+// ---- output sharpening (isp_sharpen.h; DESIGN.md 3, "Output sharpening") ---------------------------------------------
+// n u8 images of one geometry (rgb: H x W x 3; else planar YUV 4:2:0 with an H x W Y plane, whose chroma rows are copied):
+// every image's pointers in the kernel arguments, 32 per launch
+static int sharpen_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W, const mi_isp_sharpen* s,
+                        bool rgb, void* stream, const char* who) {
+  MI_REQUIRE(s, "%s: null sharpen settings", who);
+  MI_REQUIRE(s->radius == 1 || s->radius == 2, "%s: sharpen radius %d (1 or 2)", who, (int)s->radius);
+  MI_REQUIRE(s->amount_q6 >= 0 && s->amount_q6 <= 512, "%s: sharpen amount_q6 %d outside 0 .. 512", who,
+             (int)s->amount_q6);
+  MI_REQUIRE(s->threshold >= 0 && s->threshold <= 255, "%s: sharpen threshold %d outside 0 .. 255", who,
+             (int)s->threshold);
+  MI_REQUIRE(s->overshoot >= -1 && s->overshoot <= 255, "%s: sharpen overshoot %d outside 0 .. 255 (-1: none)", who,
+             (int)s->overshoot);
+  MI_REQUIRE(n >= 1, "%s: sharpen needs at least one image, got %d", who, n);
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad sharpen shape %dx%d", who, H, W);
+  // (one 256-thread block per tile: the launch's work-items per image must stay below 2^32)
+  MI_REQUIRE(H < (1 << 22) && W < (1 << 24) &&
+                 (uint64_t)((W + shp::TILE_W - 1) / shp::TILE_W) * (uint64_t)((H + shp::TILE_H - 1) / shp::TILE_H) < (1u << 24),
+             "%s: sharpen image %dx%d too large", who, H, W);
+  MI_REQUIRE(rgb || H % 2 == 0, "%s: the Y plane of a sharpen YUV 4:2:0 image must have an even height, got %d", who, H);
+  MI_REQUIRE(src && dst, "%s: null sharpen image list", who);
+  if ((size_t)H * (size_t)W == 0) return 0;
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && dst[i], "%s: sharpen image %d has a null pointer", who, i);
+    MI_REQUIRE(src[i] != dst[i], "%s: sharpen image %d: the filter cannot run in place", who, i);
+  }
+  shp::Args a = {};
+  a.H = H; a.W = W;
+  a.amount_q6 = s->amount_q6; a.threshold = s->threshold; a.overshoot = s->overshoot;
+  for (int i0 = 0; i0 < n; i0 += shp::MAX_IMAGES) {
+    a.n_images = n - i0 < shp::MAX_IMAGES ? n - i0 : shp::MAX_IMAGES;
+    for (int i = 0; i < a.n_images; ++i) a.im[i] = {src[i0 + i], dst[i0 + i]};
+    if (int rc = shp::launch(a, rgb, s->radius, (hipStream_t)stream)) return rc;
+    if (!rgb)
+      if (int rc = shp::launch_copy(a, (size_t)H * W, (size_t)H * W / 2, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_sharpen_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                        const mi_isp_sharpen* sharpen, void* stream) {
+  return sharpen_impl(src, dst, n, H, W, sharpen, true, stream, "sharpen_rgb_batch");
+}
+
+extern "C" int mi_isp_sharpen_yuv420_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                           const mi_isp_sharpen* sharpen, void* stream) {
+  return sharpen_impl(src, dst, n, H, W, sharpen, false, stream, "sharpen_yuv420_batch");
 }
 
 // ---- measurement aid: HIP events around each data pass, on the stream it runs on ---------------------

@@ -199,6 +199,12 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--raw-denoise", dest="raw_denoise", type=float, nargs=2, metavar=("GAIN", "READ_NOISE"), default=None)
     tone.add_argument("--denoise-strength", dest="denoise_strength", type=float, default=1.0)
     tone.add_argument("--denoise-radius", dest="denoise_radius", type=int, default=1)
+    # output sharpening (an extension): an unsharp mask on the luma of the u8 outputs; AMOUNT 0 .. 8, the blur radius (1 or
+    # 2), the coring threshold in luma codes and the halo clamp (luma codes; default: none)
+    tone.add_argument("--sharpen", dest="sharpen", type=float, metavar="AMOUNT", default=None)
+    tone.add_argument("--sharpen-radius", dest="sharpen_radius", type=int, default=1)
+    tone.add_argument("--sharpen-threshold", dest="sharpen_threshold", type=int, default=0)
+    tone.add_argument("--sharpen-overshoot", dest="sharpen_overshoot", type=int, default=None)
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -212,6 +218,7 @@ def main(argv=None) -> int:
     from ..defects import DefectMap
     from ..lens import LensDistortion
     from ..denoise import RawDenoise
+    from ..sharpen import Sharpen
     args = build_parser().parse_args(argv)
     if args.scan is None and args.images is None:
         raise ValueError("No --scan or --images specified")
@@ -228,6 +235,12 @@ def main(argv=None) -> int:
     if args.raw_denoise is not None:                                # (checked before any frame is read)
         denoise = RawDenoise(args.raw_denoise[0], args.raw_denoise[1], strength=args.denoise_strength,
                              radius=args.denoise_radius)
+    sharpen = None
+    if args.sharpen is not None:                                    # (also before any frame is read)
+        sharpen = Sharpen(args.sharpen, radius=args.sharpen_radius, threshold=args.sharpen_threshold,
+                          overshoot=args.sharpen_overshoot)
+    elif (args.sharpen_radius, args.sharpen_threshold, args.sharpen_overshoot) != (1, 0, None):
+        raise ValueError("--sharpen-radius / --sharpen-threshold / --sharpen-overshoot need --sharpen AMOUNT")
     index = ScanIndex.of_scan(args.scan) if args.scan is not None else ScanIndex.of_directory(args.images)
     coords = {} if args.defect_pixels is None else load_defect_pixels(args.defect_pixels, index.cameras, args.width)
     calib = {} if args.lens_distortion is None else load_lens_distortion(args.lens_distortion, index.cameras)
@@ -238,7 +251,7 @@ def main(argv=None) -> int:
     isp = camera_isp.Camera32(bayer.BayerPattern.RGGB, transform=args.transform, moving_alpha=args.moving_alpha,
                               resize_width=args.resize_width, correct_colors=args.correct_colors, device=device,
                               black_level=black, white_level=args.white_level, lens_shading=shading,
-                              auto_white_balance=args.auto_white_balance, raw_denoise=denoise)
+                              auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)

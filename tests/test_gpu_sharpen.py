@@ -1,0 +1,338 @@
+"""Output sharpening (Camera16/32 sharpen=, unsharp_mask, unsharp_mask_yuv420) on the GPU against tests/sharpen_ref.py, bit
+for bit.  Through the ISP, the sharpened ISP's output must be the restatement applied to the output of an identical ISP
+without sharpening, with the same metering state and the same mutated images."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import isp_oracle as O
+from tests import sharpen_ref as S
+from tests.util import _count_calls, assert_exact, natural_packed12
+
+pytestmark = pytest.mark.gpu
+
+CAMS = ["Camera16", "Camera32"]
+SHAPES = [(1, 1), (1, 9), (9, 1), (2, 3), (5, 5), (31, 33), (64, 64), (70, 131), (96, 256), (130, 260)]
+SETTINGS = [(1.5, 0, None), (1.5, 4, None), (1.5, 0, 0), (1.5, 0, 8), (8.0, 0, None), (0.0, 0, None)]
+ENTRY_POINTS = ("mi_isp_sharpen_rgb_batch", "mi_isp_sharpen_yuv420_batch")
+
+
+@pytest.fixture(scope="module")
+def ti():
+    import taichi_image_amd as t
+    return t
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return torch.device("cuda", 0)
+
+
+def settings(ti, radius):
+    return [(ti.Sharpen(a, radius, t, o), (a, radius, t, o)) for a, t, o in SETTINGS]
+
+
+def check_not_vacuous(img, refs, what):
+    """The references of the SETTINGS in order: each differs from its input (amount 0 excepted, the identity) and from
+    the setting before it."""
+    for k, ref in enumerate(refs):
+        if SETTINGS[k][0] > 0:
+            assert not np.array_equal(ref, img), f"{what}: setting {k} leaves the input as it is"
+        if k > 0:
+            assert not np.array_equal(ref, refs[k - 1]), f"{what}: settings {k - 1} and {k} give the same output"
+
+
+# ---- the filter on its own -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("radius", [1, 2])
+@pytest.mark.parametrize("H,W", SHAPES)
+def test_unsharp_mask_against_the_restatement(ti, rng, dev, radius, H, W):
+    inputs = {"random": rng.integers(0, 256, (H, W, 3)).astype(np.uint8), "scene": S.scene_u8(rng, H, W)}
+    for name, img in inputs.items():
+        t = torch.from_numpy(img).to(dev)
+        refs = []
+        for s, args in settings(ti, radius):
+            ref = S.sharpen_rgb(img, *args)
+            got = ti.sharpen.unsharp_mask(t, s)
+            assert isinstance(got, torch.Tensor) and got.device == dev and got.data_ptr() != t.data_ptr()
+            assert_exact(got.cpu().numpy(), ref, f"{name} {H}x{W} {args}")
+            refs.append(ref)
+        assert_exact(t.cpu().numpy(), img, "the input is left alone")
+        if H >= 31:
+            check_not_vacuous(img, refs, f"{name} {H}x{W} R={radius}")
+
+
+def test_unsharp_mask_containers(ti, rng, dev):
+    img = S.scene_u8(rng, 31, 33)
+    s = ti.Sharpen(1.5, 2, 1, 6)
+    ref = S.sharpen_rgb(img, 1.5, 2, 1, 6)
+    assert not np.array_equal(ref, img)
+    host = ti.sharpen.unsharp_mask(img, s)                            # numpy in, numpy out
+    assert isinstance(host, np.ndarray)
+    assert_exact(host, ref, "numpy")
+    cpu = ti.sharpen.unsharp_mask(torch.from_numpy(img), s)           # torch on the CPU comes back on the CPU
+    assert isinstance(cpu, torch.Tensor) and cpu.device.type == "cpu"
+    assert_exact(cpu.numpy(), ref, "torch cpu")
+    yuv = rng.integers(0, 256, (9, 10)).astype(np.uint8)
+    host = ti.sharpen.unsharp_mask_yuv420(yuv, s)
+    assert isinstance(host, np.ndarray)
+    assert_exact(host, S.sharpen_yuv420(yuv, 1.5, 2, 1, 6), "numpy yuv")
+    with pytest.raises(ValueError):
+        ti.sharpen.unsharp_mask(img.astype(np.float32), s)
+    with pytest.raises(ValueError):
+        ti.sharpen.unsharp_mask(img, (1.5, 2))
+    empty = ti.sharpen.unsharp_mask(np.zeros((0, 8, 3), np.uint8), s)
+    assert empty.shape == (0, 8, 3)
+
+
+@pytest.mark.parametrize("radius", [1, 2])
+@pytest.mark.parametrize("H,W", [(64, 64), (31, 33)])
+def test_views_at_odd_byte_offsets_take_the_byte_path(ti, rng, dev, radius, H, W):
+    """An image that starts 1, 2 or 3 bytes past a 4-byte boundary (W % 4 == 0 at 64 x 64: only the base is odd)."""
+    img = S.scene_u8(rng, H, W)
+    ref = S.sharpen_rgb(img, 1.5, radius, 0, 8)
+    assert not np.array_equal(ref, img)
+    n = H * W * 3
+    buf = torch.zeros(n + 8, dtype=torch.uint8, device=dev)
+    for off in (1, 2, 3):
+        view = buf[off:off + n].view(H, W, 3)
+        view.copy_(torch.from_numpy(img))
+        assert view.data_ptr() % 4 == (buf.data_ptr() + off) % 4 != 0
+        got = ti.sharpen.unsharp_mask(view, ti.Sharpen(1.5, radius, 0, 8))
+        assert_exact(got.cpu().numpy(), ref, f"offset {off}")
+
+
+@pytest.mark.parametrize("n", [1, 3, 33])
+def test_batches(ti, rng, dev, n):
+    """33 images cross the 32-per-launch split."""
+    H, W = 16, 20
+    imgs = [S.scene_u8(rng, H, W, sigma=0.03 + 0.002 * k) for k in range(n)]
+    s = ti.Sharpen(1.5, 2, 0, 8)
+    outs = ti.sharpen.apply([torch.from_numpy(i).to(dev) for i in imgs], s)
+    assert len(outs) == n
+    for k in range(n):
+        ref = S.sharpen_rgb(imgs[k], 1.5, 2, 0, 8)
+        assert not np.array_equal(ref, imgs[k])
+        assert_exact(outs[k].cpu().numpy(), ref, f"image {k} of {n}")
+    yuvs = [rng.integers(0, 256, (H * 3 // 2, W)).astype(np.uint8) for _ in range(n)]
+    outs = ti.sharpen.apply([torch.from_numpy(y).to(dev) for y in yuvs], s, yuv420=True)
+    for k in range(n):
+        assert_exact(outs[k].cpu().numpy(), S.sharpen_yuv420(yuvs[k], 1.5, 2, 0, 8), f"yuv image {k} of {n}")
+
+
+# ---- the Y-plane form --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("radius", [1, 2])
+@pytest.mark.parametrize("H,W", [(2, 2), (6, 10), (64, 64), (70, 132)])
+def test_unsharp_mask_yuv420_against_the_restatement(ti, rng, dev, radius, H, W):
+    chroma = rng.integers(0, 256, (H // 2, W)).astype(np.uint8)
+    inputs = {"random": rng.integers(0, 256, (H, W)).astype(np.uint8), "scene": S.scene_u8(rng, H, W)[..., 1]}
+    for name, y in inputs.items():
+        yuv = np.concatenate([y, chroma])
+        t = torch.from_numpy(yuv).to(dev)
+        refs = []
+        for s, args in settings(ti, radius):
+            ref = S.sharpen_yuv420(yuv, *args)
+            got = ti.sharpen.unsharp_mask_yuv420(t, s).cpu().numpy()
+            assert_exact(got, ref, f"{name} {H}x{W} {args}")
+            assert_exact(got[H:], chroma, "chroma rows")
+            refs.append(ref)
+        if H >= 64:
+            check_not_vacuous(yuv, refs, f"yuv {name} {H}x{W} R={radius}")
+
+
+# ---- one full-size case -------------------------------------------------------------------------------------------------
+def test_full_size_radius_2(ti, rng, dev):
+    H, W = 3072, 4096
+    img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    img[:, :, 1] = (img[:, :, 1] >> 2) + (np.arange(W, dtype=np.uint32)[None, :] * 3 // 64).astype(np.uint8)
+    ref = S.sharpen_rgb(img, 1.5, 2, 1, 12)
+    got = ti.sharpen.unsharp_mask(torch.from_numpy(img).to(dev), ti.Sharpen(1.5, 2, 1, 12)).cpu().numpy()
+    assert not np.array_equal(ref, img)
+    assert_exact(got, ref, "3072 x 4096 R=2")
+
+
+# ---- through the ISP ------------------------------------------------------------------------------------------------------
+SHARP = dict(amount=1.5, radius=2, threshold=1, overshoot=10)
+SHARP_ARGS = (1.5, 2, 1, 10)
+ISP_CASES = ["reinhard", "reinhard_keep", "linear", "only", "process", "process_keep", "rotate_90", "flip_horiz", "resize"]
+
+
+def isp_pair(ti, dev, cam, sharpen=True, **kw):
+    kw = dict(moving_alpha=0.3, device=dev, **kw)
+    plain = getattr(ti, cam)(ti.BayerPattern.RGGB, **kw)
+    sharp = getattr(ti, cam)(ti.BayerPattern.RGGB, sharpen=ti.Sharpen(**SHARP) if sharpen else None, **kw)
+    return plain, sharp
+
+
+def run_case(ti, isp, case, frames):
+    """(u8 outputs, images left behind or None) of one step of `case` on the packed frames."""
+    if case in ("process", "process_keep"):
+        if case == "process_keep":
+            return isp.process_packed12(frames, gamma=0.7, keep_images=True)
+        return isp.process_packed12(frames, gamma=0.7), None
+    imgs = isp.load_packed12_batch(frames)
+    if case == "linear":
+        return isp.tonemap_linear(imgs, gamma=0.8), imgs
+    if case == "only":
+        isp.update_metering(imgs)
+        return [isp.tonemap_only(im, isp.metrics, 0.7, 1.0, 1.0, 0.0) for im in imgs], imgs
+    if case == "yuv420":
+        return isp.tonemap_reinhard_yuv420(imgs, gamma=0.7), imgs
+    return isp.tonemap_reinhard(imgs, gamma=0.7, write_back=case != "reinhard_keep"), imgs
+
+
+def isp_kwargs(ti, case):
+    if case in ("rotate_90", "flip_horiz"):
+        return dict(transform=ti.ImageTransform[case])
+    return dict(resize_width=48) if case == "resize" else {}
+
+
+@pytest.mark.parametrize("cam", CAMS)
+@pytest.mark.parametrize("H,W", [(64, 96), (96, 256)])
+@pytest.mark.parametrize("case", ISP_CASES)
+def test_isp_outputs_are_the_filter_of_the_plain_outputs(ti, rng, dev, monkeypatch, cam, H, W, case):
+    frames = [torch.from_numpy(natural_packed12(rng, H, W, O.RGGB, dark=0.03 * k)).to(dev) for k in range(3)]
+    plain, sharp = isp_pair(ti, dev, cam, **isp_kwargs(ti, case))
+    group = _count_calls(monkeypatch, "mi_isp_camera_group_reinhard")
+    for step in range(2):
+        want, want_imgs = run_case(ti, plain, case, frames)
+        got, got_imgs = run_case(ti, sharp, case, frames)
+        what = f"{cam} {case} {H}x{W} step {step}"
+        for k, (g, w) in enumerate(zip(got, want)):
+            ref = S.sharpen_rgb(w.cpu().numpy(), *SHARP_ARGS)
+            assert not np.array_equal(ref, w.cpu().numpy()), what
+            assert_exact(g.cpu().numpy(), ref, f"{what} output {k}")
+        assert_exact(sharp.metrics.cpu().numpy(), plain.metrics.cpu().numpy(), what + " metering state")
+        if want_imgs is not None:
+            for k, (g, w) in enumerate(zip(got_imgs, want_imgs)):
+                assert_exact(g.cpu().numpy(), w.cpu().numpy(), f"{what} image {k}")
+    if case in ("process", "process_keep"):           # Camera16 takes the one-launch camera group, Camera32 the two calls
+        assert len(group) == (4 if cam == "Camera16" else 0), f"{cam}: {len(group)} camera-group launches"
+
+
+@pytest.mark.parametrize("cam", CAMS)
+@pytest.mark.parametrize("H,W,fused", [(64, 96, True), (66, 100, False)])
+def test_isp_yuv420_sharpens_the_y_plane(ti, rng, dev, monkeypatch, cam, H, W, fused):
+    """W % 16 == 0 takes the fused YUV store, W = 100 the RGB tonemap and the separate conversion: either way the output is
+    the Y-plane filter of the plain call's YUV image (not the YUV image of sharpened RGB)."""
+    frames = [torch.from_numpy(natural_packed12(rng, H, W, O.RGGB, dark=0.03 * k)).to(dev) for k in range(2)]
+    plain, sharp = isp_pair(ti, dev, cam)
+    calls = _count_calls(monkeypatch, "mi_isp_reinhard_batch_yuv420")
+    rgb_calls = _count_calls(monkeypatch, "mi_isp_sharpen_rgb_batch")
+    for step in range(2):
+        want, want_imgs = run_case(ti, plain, "yuv420", frames)
+        got, got_imgs = run_case(ti, sharp, "yuv420", frames)
+        for k, (g, w) in enumerate(zip(got, want)):
+            ref = S.sharpen_yuv420(w.cpu().numpy(), *SHARP_ARGS)
+            assert not np.array_equal(ref, w.cpu().numpy())
+            assert_exact(g.cpu().numpy(), ref, f"{cam} yuv420 {H}x{W} step {step} output {k}")
+        assert_exact(sharp.metrics.cpu().numpy(), plain.metrics.cpu().numpy(), "metering state")
+        for g, w in zip(got_imgs, want_imgs):
+            assert_exact(g.cpu().numpy(), w.cpu().numpy(), "images")
+    assert len(calls) == (4 if fused else 0) and not rgb_calls
+
+
+def test_set_turns_it_on_and_off(ti, rng, dev):
+    H, W = 64, 96
+    frames = [torch.from_numpy(natural_packed12(rng, H, W, O.RGGB)).to(dev)]
+    plain, isp = isp_pair(ti, dev, "Camera32", sharpen=False)
+    assert isp.sharpen is None
+    s = ti.Sharpen(**SHARP)
+
+    def step():
+        want = plain.tonemap_reinhard(plain.load_packed12_batch(frames), gamma=0.7)[0].cpu().numpy()
+        return want, isp.tonemap_reinhard(isp.load_packed12_batch(frames), gamma=0.7)[0].cpu().numpy()
+
+    want, got = step()
+    assert_exact(got, want, "off")
+    isp.set(sharpen=s)
+    assert isp.sharpen == s
+    want, got = step()
+    assert_exact(got, S.sharpen_rgb(want, *SHARP_ARGS), "on with the next call")
+    isp.set(moving_alpha=0.3)                                          # (None leaves it)
+    assert isp.sharpen == s
+    isp.set(sharpen=ti.Sharpen(2.0, 1))
+    want, got = step()
+    assert_exact(got, S.sharpen_rgb(want, 2.0, 1), "replaced")
+    isp.set(sharpen=False)
+    assert isp.sharpen is None
+    want, got = step()
+    assert_exact(got, want, "off again")
+    with pytest.raises(ValueError):
+        isp.set(sharpen=1.5)
+
+
+@pytest.mark.parametrize("cam", CAMS)
+def test_without_sharpen_no_new_entry_point_is_called(ti, rng, dev, monkeypatch, cam):
+    H, W = 64, 96
+    frames = [torch.from_numpy(natural_packed12(rng, H, W, O.RGGB, dark=0.03 * k)).to(dev) for k in range(2)]
+    counts = [_count_calls(monkeypatch, name) for name in ENTRY_POINTS]
+    for case in ISP_CASES + ["yuv420"]:
+        isp = getattr(ti, cam)(ti.BayerPattern.RGGB, device=dev, **isp_kwargs(ti, case))
+        run_case(ti, isp, case, frames)
+        assert not counts[0] and not counts[1], case
+    isp = getattr(ti, cam)(ti.BayerPattern.RGGB, device=dev, sharpen=ti.Sharpen())      # (the probe does count)
+    run_case(ti, isp, "reinhard", frames)
+    run_case(ti, isp, "yuv420", frames)
+    assert len(counts[0]) == 1 and len(counts[1]) == 1
+
+
+def test_graph_capture_of_a_step(ti, rng, dev):
+    """load + tonemap_reinhard with sharpening captured once and replayed on new frame contents."""
+    H, W = 64, 96
+    frames = [[torch.from_numpy(natural_packed12(rng, H, W, O.RGGB, dark=0.02 * ((k + j) % 3))).to(dev)
+               for j in range(2)] for k in range(3)]
+    static = [torch.empty_like(f) for f in frames[0]]
+    cap = ti.Camera16(ti.BayerPattern.RGGB, moving_alpha=0.5, device=dev, sharpen=ti.Sharpen(**SHARP))
+    eager = ti.Camera16(ti.BayerPattern.RGGB, moving_alpha=0.5, device=dev)
+
+    def step(isp, srcs):
+        return isp.tonemap_reinhard(isp.load_packed12_batch(srcs), gamma=0.7, write_back=False)
+
+    for s, f in zip(static, frames[0]):
+        s.copy_(f)
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        step(cap, static)                                    # (warm-up: the first step, eagerly, on the capture stream)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    step(eager, frames[0])
+    torch.cuda.synchronize(dev)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        outs = step(cap, static)
+    seen = []
+    for k in (1, 2):                                         # (a captured update_metering reads the state it was captured with)
+        for s, f in zip(static, frames[k]):
+            s.copy_(f)
+        g.replay()
+        probe = ti.Camera16(ti.BayerPattern.RGGB, moving_alpha=0.5, device=dev)
+        probe.metrics = eager.metrics.clone()
+        want = step(probe, frames[k])
+        torch.cuda.synchronize(dev)
+        for a, b in zip(outs, want):
+            assert_exact(a.cpu().numpy(), S.sharpen_rgb(b.cpu().numpy(), *SHARP_ARGS), f"replay {k}")
+        seen.append(outs[0].cpu().numpy())
+    assert not np.array_equal(seen[0], seen[1]), "the replays saw the same frame"
+
+
+# ---- C ABI error returns ---------------------------------------------------------------------------------------------
+def test_entry_points_refuse_without_a_launch(ti, dev):
+    """Bad radius, src == dst and n = 0 are refused by the host checks: the destination stays as it was."""
+    from taichi_image_amd import _native
+    L = _native.lib()
+    H, W = 8, 12
+    src = torch.full((H, W, 3), 7, dtype=torch.uint8, device=dev)
+    src[:, ::2] = 200
+    dst = torch.full((H, W, 3), 99, dtype=torch.uint8, device=dev)
+    good = _native.Sharpen(96, 1, 0, -1)
+    stream = _native.stream_ptr(dev)
+    for fn, h in ((L.mi_isp_sharpen_rgb_batch, H), (L.mi_isp_sharpen_yuv420_batch, 16)):
+        for args in ((_native.ptr_array([src]), _native.ptr_array([dst]), 1, h, W, _native.Sharpen(96, 3, 0, -1), stream),
+                     (_native.ptr_array([src]), _native.ptr_array([src]), 1, h, W, good, stream),
+                     (_native.ptr_array([src]), _native.ptr_array([dst]), 0, h, W, good, stream)):
+            assert fn(*args) == 1
+            assert b"sharpen" in L.mi_isp_last_error()
+    torch.cuda.synchronize(dev)
+    assert bool((dst == 99).all()) and int(src[0, 0, 0]) == 200
+    assert L.mi_isp_sharpen_rgb_batch(_native.ptr_array([src]), _native.ptr_array([dst]), 1, H, W, good, stream) == 0
+    assert_exact(dst.cpu().numpy(), S.sharpen_rgb(src.cpu().numpy(), 1.5, 1), "the good call")
