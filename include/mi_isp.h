@@ -209,7 +209,14 @@ int mi_isp_load_packed_batch(const uint8_t* const* packed_host, void* const* rgb
 int mi_isp_load_packed_metered_is_fused(int H, int W, int bits, int ids_format, int work_dtype, int sub_stride);
 /* 1 if mi_isp_load_packed can fuse a resize by `scale` (its LDS tile holds the source region of a
  * 64x16 destination tile for scale >= ~0.39, any upscale); otherwise demosaic at full size and
- * call mi_isp_resize_bilinear. */
+ * call mi_isp_resize_bilinear.
+ * This is the bound of the tile kernel, which takes MI_F32 and the frames the streaming kernel
+ * does not.  MI_F16 frames that the streaming kernel takes - 12 bit in the standard layout, W a
+ * multiple of 8, H >= 4, a packed frame below 1 GiB, an output that is 8-byte aligned and smaller
+ * than 4 GiB - accept ANY positive scale, bit-exact like the others (the streaming resize keeps
+ * whole source rows, so no scale outgrows it; below 1/3 it skips source rows, below 1/4 its bands
+ * end on ragged destination columns).  Every other call with a scale outside the bound returns
+ * non-zero and launches nothing. */
 int mi_isp_load_packed_scale_supported(float scale);
 
 /* ---- sensor black and white levels ------------------------------------------------------------------------------------

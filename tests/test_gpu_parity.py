@@ -451,7 +451,7 @@ def test_isp_load_packed12_bit_exact(ti, rng, dev, cam, work, kw):
 
 
 @pytest.mark.parametrize("p", [0, 1, 2, 3])
-@pytest.mark.parametrize("shape,kw", [((98, 168), dict(scale=1.3)), ((98, 168), dict(scale=0.3)),      # upscale; unfused fallback
+@pytest.mark.parametrize("shape,kw", [((98, 168), dict(scale=1.3)), ((98, 168), dict(scale=0.3)),      # upscale; 0.3: the Python layer resizes separately
                                       ((70, 170), dict(resize_width=90)), ((34, 136), dict(scale=0.46875)),
                                       ((130, 264), dict(resize_width=124, correct_colors=True))])
 def test_isp_load_packed12_fused_resize(ti, rng, dev, p, shape, kw):
