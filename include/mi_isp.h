@@ -414,6 +414,37 @@ int mi_isp_sharpen_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst
                              const mi_isp_sharpen* sharpen_host, void* stream);
 int mi_isp_sharpen_yuv420_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
                                 const mi_isp_sharpen* sharpen_host, void* stream);
+/* ---- local contrast ("Local contrast") -----------------------------------------------------------------
+ * Contrast-limited adaptive histogram equalisation (CLAHE) of the luma of a u8 image, in integer arithmetic: the output
+ * is the contract's bit for bit.  All values signed integers, >> arithmetic, / floor division; C = clip_q8 (the clip limit
+ * times 256, 256 .. 16384, or 0: no clip), S = strength_q6 (the strength times 64, 0 .. 64), the image in tiles_y x
+ * tiles_x tiles (1 .. 16 each):
+ *   L = (77 R + 150 G + 29 B + 128) >> 8
+ *   tile (i, j) = rows [i H / Ty, (i + 1) H / Ty) x columns [j W / Tx, (j + 1) W / Tx), n pixels;  h[v] = #{L == v}
+ *   C != 0:  c = max(1, (C n) >> 16);  e = sum_v max(h[v] - c, 0);  h[v] = min(h[v], c) + (e >> 8)
+ *            r = e & 255 > 0:  s = max(256 / r, 1);  h[k s] += 1 for k = 0 .. r - 1
+ *   lut_ij[v] = (2 * 255 * (h[0] + ... + h[v]) + n) / (2 n)
+ *   per axis (m, M, T = y, H, Ty or x, W, Tx):  N = (2 m + 1) T - M;  i0 = N / (2 M);  w = (256 (N - 2 M i0)) / (2 M)
+ *            a = clamp(i0, 0, T - 1);  b = clamp(i0 + 1, 0, T - 1)
+ *   E = ((256 - wy) ((256 - wx) lut[ay][ax][L] + wx lut[ay][bx][L])
+ *            + wy ((256 - wx) lut[by][ax][L] + wx lut[by][bx][L]) + 32768) >> 16
+ *   delta = ((E - L) S + 32) >> 6;  out_c = clamp(I_c + delta, 0, 255) for c = R, G, B
+ *  - mi_isp_local_contrast_rgb_batch: n interleaved H x W x 3 images of one geometry; four launches (clear, histograms, LUTs,
+ *    apply) per 32 images, ordered by the stream.
+ *  - mi_isp_local_contrast_yuv420_batch: n planar YUV 4:2:0 images (H * 3 / 2 rows of W bytes; H, W of the Y plane, both
+ *    even): the operator with L = Y, out = clamp(Y + delta, 0, 255); the chroma rows are copied when src[i] != dst[i].
+ * src_host / dst_host: n device pointers each, read on the host.  src[i] == dst[i] is allowed (the apply step is
+ * pointwise); images that overlap otherwise are not.  ws_dev: mi_isp_local_contrast_workspace_bytes(n, lc) bytes of
+ * device memory, 16-byte aligned, contents irrelevant before and after the call (0 bytes for bad settings or n <= 0).
+ * Host-side checks before any launch (error text names "local_contrast"): the settings' ranges, n >= 0, H, W >= 0,
+ * H >= tiles_y and W >= tiles_x and both <= 32768 (unless H * W == 0), NULL pointers.  n == 0 and H * W == 0 are
+ * successful no-ops. */
+typedef struct { int32_t tiles_y, tiles_x, clip_q8 /* 0: no clip */, strength_q6; } mi_isp_local_contrast;
+size_t mi_isp_local_contrast_workspace_bytes(int n, const mi_isp_local_contrast* lc_host);
+int mi_isp_local_contrast_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                                    const mi_isp_local_contrast* lc_host, void* ws_dev, void* stream);
+int mi_isp_local_contrast_yuv420_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                                       const mi_isp_local_contrast* lc_host, void* ws_dev, void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==

@@ -58,6 +58,12 @@ class Sharpen(ctypes.Structure):
     _fields_ = [("amount_q6", c_int32), ("radius", c_int32), ("threshold", c_int32), ("overshoot", c_int32)]
 
 
+class LocalContrast(ctypes.Structure):
+    """mi_isp_local_contrast: the tile grid (1 .. 16 each way), the clip limit times 256 (256 .. 16384, 0: no clip) and
+    the strength times 64 (0 .. 64)."""
+    _fields_ = [("tiles_y", c_int32), ("tiles_x", c_int32), ("clip_q8", c_int32), ("strength_q6", c_int32)]
+
+
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SIGNATURES = {
@@ -138,6 +144,11 @@ SIGNATURES = {
     "mi_isp_denoise_cfa": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(Denoise), _P]),
     "mi_isp_sharpen_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(Sharpen), _P]),
     "mi_isp_sharpen_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(Sharpen), _P]),
+    "mi_isp_local_contrast_workspace_bytes": (c_size_t, [c_int, POINTER(LocalContrast)]),
+    "mi_isp_local_contrast_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(LocalContrast), _P,
+                                                _P]),
+    "mi_isp_local_contrast_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(LocalContrast),
+                                                   _P, _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,

@@ -24,6 +24,7 @@ from . import defects as _defects
 from . import denoise as _dn
 from . import lens as _lens
 from . import sharpen as _shp
+from . import local_contrast as _lc
 from . import white_balance as _wb
 from . import distributed as _dist
 
@@ -280,7 +281,8 @@ def camera_isp(name: str, dtype=types.f32):
                      lens_shading=None,
                      auto_white_balance=False,
                      raw_denoise=None,
-                     sharpen=None):
+                     sharpen=None,
+                     local_contrast=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -298,6 +300,7 @@ def camera_isp(name: str, dtype=types.f32):
                 _wb.check_seed(white_balance)
             raw_denoise = _dn.check_raw_denoise(raw_denoise)
             sharpen = _shp.check_sharpen(sharpen)
+            local_contrast = _lc.check_local_contrast(local_contrast)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -346,6 +349,9 @@ def camera_isp(name: str, dtype=types.f32):
             # output sharpening (an extension): the Sharpen applied to every u8 output of the tonemaps, or None (the
             # tonemaps run exactly as without it).  DESIGN.md 3, "Output sharpening".
             self._sharpen = sharpen
+            # local contrast (an extension): the LocalContrast applied in place to every u8 output of the tonemaps, before
+            # sharpening, or None (the tonemaps run exactly as without it).  DESIGN.md 3, "Local contrast".
+            self._local_contrast = local_contrast
 
         @property
         def _demosaic_pattern(self):
@@ -358,7 +364,7 @@ def camera_isp(name: str, dtype=types.f32):
                 color_correction: Optional[np.ndarray] = None,
                 transform: Optional[interpolate.ImageTransform] = None,
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
-                raw_denoise=None, sharpen=None):
+                raw_denoise=None, sharpen=None, local_contrast=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -369,7 +375,8 @@ def camera_isp(name: str, dtype=types.f32):
             no state, no pending statistics.  white_balance= while it is on seeds it again; lens_shading= while it is on
             rebuilds the effective grid from the new grid and the current gains on the device.
             raw_denoise (the extension): None leaves it, False turns it off, a RawDenoise replaces it.
-            sharpen (the extension): None leaves it, False turns it off, a Sharpen replaces it."""
+            sharpen (the extension): None leaves it, False turns it off, a Sharpen replaces it.
+            local_contrast (the extension): None leaves it, False turns it off, a LocalContrast replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -379,6 +386,8 @@ def camera_isp(name: str, dtype=types.f32):
                 _wb.check_seed(self.white_balance if white_balance is None else white_balance)
             denoise = None if raw_denoise is None or raw_denoise is False else _dn.check_raw_denoise(raw_denoise)
             new_sharpen = None if sharpen is None or sharpen is False else _shp.check_sharpen(sharpen)
+            new_lc = (None if local_contrast is None or local_contrast is False
+                      else _lc.check_local_contrast(local_contrast))
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -427,6 +436,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._sharpen = None
             elif new_sharpen is not None:
                 self._sharpen = new_sharpen
+            if local_contrast is False:
+                self._local_contrast = None
+            elif new_lc is not None:
+                self._local_contrast = new_lc
             if auto_white_balance is not None:
                 if awb is None:
                     self._awb_off()
@@ -531,6 +544,27 @@ def camera_isp(name: str, dtype=types.f32):
             if self._sharpen is None or not outputs:
                 return outputs
             return _shp.apply(outputs, self._sharpen, yuv420)
+
+        @property
+        def local_contrast(self) -> Optional[_lc.LocalContrast]:
+            """The LocalContrast the tonemaps apply to their u8 outputs, or None."""
+            return self._local_contrast
+
+        def _check_local_contrast_fits(self, images):
+            """ValueError for an image whose output (after the orientation transform) does not take the tile grid, before a
+            tonemap launches anything or moves the metering state."""
+            if self._local_contrast is not None:
+                for im in images:
+                    if isinstance(im, torch.Tensor) and im.ndim >= 2:
+                        _lc.check_shape(*_out_shape(im, self.transform)[:2], self._local_contrast)
+
+        def _finished(self, outputs, yuv420=False):
+            """The u8 outputs of a tonemap as the caller gets them: local contrast, in place on `outputs` (the tonemap's
+            own freshly allocated tensors), then sharpening; with neither set, `outputs` themselves.  DESIGN.md 3, "Local
+            contrast" and "Output sharpening"."""
+            if self._local_contrast is not None and outputs:
+                _lc.apply(outputs, self._local_contrast, yuv420, inplace=True)
+            return self._sharpened(outputs, yuv420)
 
         @property
         def lens_shading(self) -> Optional[torch.Tensor]:
@@ -858,9 +892,10 @@ def camera_isp(name: str, dtype=types.f32):
 
         def tonemap_only(self, image, metrics, gamma, intensity, light_adapt, color_adapt):
             """camera_isp.py:387-390."""
+            self._check_local_contrast_fits([image])
             output = torch.empty(_out_shape(image, self.transform), dtype=torch.uint8, device=self.device)
             reinhard_kernel(image, output, metrics, gamma, intensity, light_adapt, color_adapt, self.transform)
-            return self._sharpened([output])[0]
+            return self._finished([output])[0]
 
         def tonemap_reinhard(self, images: List[torch.Tensor],
                              gamma: float = 1.0, intensity: float = 1.0, light_adapt: float = 1.0,
@@ -869,10 +904,12 @@ def camera_isp(name: str, dtype=types.f32):
             with the Reinhard-mapped values (camera_isp.py:211).
             write_back=False (an extension, not the reference's semantics): the same u8 outputs, bit for bit, with the
             images left as they are - a third of the tonemap's memory traffic is that write and its re-read."""
-            return self._sharpened(self._tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt, write_back))
+            _typecheck("images", images, list)
+            self._check_local_contrast_fits(images)
+            return self._finished(self._tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt, write_back))
 
         def _tonemap_reinhard(self, images, gamma, intensity, light_adapt, color_adapt, write_back=True):
-            """tonemap_reinhard before output sharpening."""
+            """tonemap_reinhard before local contrast and output sharpening."""
             _typecheck("write_back", write_back, bool)
             _typecheck("images", images, list)
             for n, v in (("gamma", gamma), ("intensity", intensity), ("light_adapt", light_adapt),
@@ -903,12 +940,14 @@ def camera_isp(name: str, dtype=types.f32):
             (color/yuv_420.py:39-66) fused into the second Reinhard pass when no orientation transform is set
             and W % 16 == 0: the u8 RGB images are never written.  Same side effects as tonemap_reinhard.
             With sharpen= set, the Y plane of each YUV image is sharpened (sharpen.unsharp_mask_yuv420), which is not the
-            YUV image of a sharpened RGB output."""
+            YUV image of a sharpened RGB output; local_contrast= likewise equalises the Y plane
+            (local_contrast.clahe_yuv420)."""
             from . import color
             _typecheck("images", images, list)
+            self._check_local_contrast_fits(images)
             H, W = images[0].shape[:2]
             if self.transform != interpolate.ImageTransform.none or H % 2 or W % 16:
-                return self._sharpened([color.rgb_yuv420_image(o) for o in self._tonemap_reinhard(
+                return self._finished([color.rgb_yuv420_image(o) for o in self._tonemap_reinhard(
                     images, gamma, intensity, light_adapt, color_adapt)], yuv420=True)
             for n, v in (("gamma", gamma), ("intensity", intensity), ("light_adapt", light_adapt),
                          ("color_adapt", color_adapt)):
@@ -921,7 +960,7 @@ def camera_isp(name: str, dtype=types.f32):
                 self.metrics.data_ptr(), float(gamma), float(intensity), float(light_adapt), float(color_adapt),
                 ws.data_ptr(), _native.stream_ptr(self.device)))
             _written_in_place(images)
-            return self._sharpened(outputs, yuv420=True)
+            return self._finished(outputs, yuv420=True)
 
         def process_packed12(self, frames: List[torch.Tensor], gamma: float = 1.0, intensity: float = 1.0,
                              light_adapt: float = 1.0, color_adapt: float = 0.0, keep_images: bool = False,
@@ -988,6 +1027,8 @@ def camera_isp(name: str, dtype=types.f32):
                 images = self.load_packed12_batch(frames, ids_format, defects=defects, undistort=undistort)
                 outputs = self.tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt)
                 return (outputs, images) if keep_images else outputs
+            if self._local_contrast is not None:
+                _lc.check_shape(h, w, self._local_contrast)
             _raise_resident_faults(L, self.device)
             n = len(srcs)
             outputs = [torch.empty((h, w, 3), dtype=torch.uint8, device=self.device) for _ in srcs]
@@ -1008,7 +1049,7 @@ def camera_isp(name: str, dtype=types.f32):
                         ws.data_ptr())
                 _native.check(group("mi_isp_camera_group_reinhard", *args, tail=(stream,)))
                 self.metrics = metrics
-                outputs = self._sharpened(outputs)
+                outputs = self._finished(outputs)
                 return (outputs, images) if keep_images else outputs
             # a sharded group (one process per GPU): the same three steps with the metering's two all-gathers in between
             _native.check(group("mi_isp_camera_group_subsample", p_srcs, n, h, w, self._demosaic_pattern.value, ccm,
@@ -1020,7 +1061,7 @@ def camera_isp(name: str, dtype=types.f32):
             args = (p_srcs, p_imgs, p_outs, n, h, w, self._demosaic_pattern.value, ccm, self.metrics.data_ptr(), float(gamma),
                     float(intensity), float(light_adapt), float(color_adapt), ws.data_ptr())
             _native.check(group("mi_isp_camera_group_tonemap", *args, tail=(stream,)))
-            outputs = self._sharpened(outputs)
+            outputs = self._finished(outputs)
             return (outputs, images) if keep_images else outputs
 
         def tonemap_linear(self, images: List[torch.Tensor], gamma: float = 1.0):
@@ -1028,6 +1069,7 @@ def camera_isp(name: str, dtype=types.f32):
             _typecheck("images", images, list)
             _typecheck("gamma", gamma, float)
             _check_transform(images, self.transform)
+            self._check_local_contrast_fits(images)
             self.update_metering(images)
             outputs = [torch.empty(_out_shape(image, self.transform), dtype=torch.uint8, device=self.device)
                        for image in images]
@@ -1037,7 +1079,7 @@ def camera_isp(name: str, dtype=types.f32):
                 _native.ptr_array(images), _native.ptr_array(outputs), len(images), H, W, dtype.code,
                 self.metrics.data_ptr(), float(gamma), interpolate.transform_code(self.transform), ws.data_ptr(),
                 _native.stream_ptr(self.device)))
-            return self._sharpened(outputs)
+            return self._finished(outputs)
 
     ISP.reinhard_kernel = staticmethod(reinhard_kernel)
     ISP.linear_kernel = staticmethod(linear_kernel)

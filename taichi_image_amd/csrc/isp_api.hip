@@ -16,6 +16,7 @@
 #include "isp_awb.h"
 #include "isp_denoise.h"
 #include "isp_sharpen.h"
+#include "isp_local_contrast.h"
 #include <mutex>
 #include <atomic>
 
@@ -28,7 +29,7 @@ void mi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int mi_isp_version(void) { return 1800; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
+extern "C" int mi_isp_version(void) { return 1900; }  // 0.1.0 -> major*1e4 + minor*1e3 ... (monotone)
 extern "C" const char* mi_isp_last_error(void) { return g_err; }
 
 extern "C" int mi_isp_bayer_weights(int32_t out[4 * 13 * 3]) {
@@ -806,6 +807,70 @@ extern "C" int mi_isp_sharpen_rgb_batch(const uint8_t* const* src, uint8_t* cons
 extern "C" int mi_isp_sharpen_yuv420_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
                                            const mi_isp_sharpen* sharpen, void* stream) {
   return sharpen_impl(src, dst, n, H, W, sharpen, false, stream, "sharpen_yuv420_batch");
+}
+
+// ---- local contrast (isp_local_contrast.h; DESIGN.md 3, "Local contrast") ----------------------------------------------
+static int local_contrast_settings(const mi_isp_local_contrast* s, const char* who) {
+  MI_REQUIRE(s, "%s: null local_contrast settings", who);
+  MI_REQUIRE(s->tiles_y >= 1 && s->tiles_y <= lc::MAX_TILES && s->tiles_x >= 1 && s->tiles_x <= lc::MAX_TILES,
+             "%s: local_contrast tiles %d x %d outside 1 .. %d", who, (int)s->tiles_y, (int)s->tiles_x, lc::MAX_TILES);
+  MI_REQUIRE(s->clip_q8 == 0 || (s->clip_q8 >= 256 && s->clip_q8 <= 64 * 256),
+             "%s: local_contrast clip_q8 %d outside 256 .. 16384 (0: no clip)", who, (int)s->clip_q8);
+  MI_REQUIRE(s->strength_q6 >= 0 && s->strength_q6 <= 64, "%s: local_contrast strength_q6 %d outside 0 .. 64", who,
+             (int)s->strength_q6);
+  return 0;
+}
+
+extern "C" size_t mi_isp_local_contrast_workspace_bytes(int n, const mi_isp_local_contrast* s) {
+  if (n <= 0 || local_contrast_settings(s, "local_contrast_workspace_bytes")) return 0;
+  return lc::hist_bytes(n, s->tiles_y, s->tiles_x) + lc::lut_bytes(n, s->tiles_y, s->tiles_x);
+}
+
+// n u8 images of one geometry (rgb: H x W x 3; else planar YUV 4:2:0 with an H x W Y plane, whose chroma rows are copied
+// when the image is not filtered in place): every image's pointers in the kernel arguments, 32 per launch
+static int local_contrast_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                               const mi_isp_local_contrast* s, void* ws, bool rgb, void* stream, const char* who) {
+  if (int rc = local_contrast_settings(s, who)) return rc;
+  MI_REQUIRE(n >= 0, "%s: local_contrast with %d images", who, n);
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad local_contrast shape %dx%d", who, H, W);
+  MI_REQUIRE(rgb || (H % 2 == 0 && W % 2 == 0),
+             "%s: the Y plane of a local_contrast YUV 4:2:0 image must have even sides, got %dx%d", who, H, W);
+  if (n == 0 || (size_t)H * (size_t)W == 0) return 0;
+  MI_REQUIRE(H >= s->tiles_y && W >= s->tiles_x, "%s: local_contrast image %dx%d smaller than its %d x %d tiles", who, H, W,
+             (int)s->tiles_y, (int)s->tiles_x);
+  MI_REQUIRE(H <= lc::MAX_SIDE && W <= lc::MAX_SIDE, "%s: local_contrast image %dx%d larger than %d", who, H, W, lc::MAX_SIDE);
+  MI_REQUIRE(src && dst, "%s: null local_contrast image list", who);
+  MI_REQUIRE(ws && mi_aligned(ws, 16), "%s: local_contrast workspace null or not 16-byte aligned", who);
+  for (int i = 0; i < n; ++i) MI_REQUIRE(src[i] && dst[i], "%s: local_contrast image %d has a null pointer", who, i);
+  const size_t per_image = (size_t)s->tiles_y * s->tiles_x * 256;
+  uint32_t* hist = static_cast<uint32_t*>(ws);
+  uint8_t* lut = static_cast<uint8_t*>(ws) + lc::hist_bytes(n, s->tiles_y, s->tiles_x);
+  lc::Args a = {};
+  a.H = H; a.W = W; a.Ty = s->tiles_y; a.Tx = s->tiles_x;
+  a.clip_q8 = s->clip_q8; a.strength_q6 = s->strength_q6;
+  for (int i0 = 0; i0 < n; i0 += lc::MAX_IMAGES) {
+    a.n_images = n - i0 < lc::MAX_IMAGES ? n - i0 : lc::MAX_IMAGES;
+    a.hist = hist + i0 * per_image;
+    a.lut = lut + i0 * per_image;
+    shp::Args chroma = {};                            // the chroma rows of the images not filtered in place
+    for (int i = 0; i < a.n_images; ++i) {
+      a.im[i] = {src[i0 + i], dst[i0 + i]};
+      if (!rgb && src[i0 + i] != dst[i0 + i]) chroma.im[chroma.n_images++] = {src[i0 + i], dst[i0 + i]};
+    }
+    if (int rc = lc::launch(a, rgb, (hipStream_t)stream)) return rc;
+    if (int rc = shp::launch_copy(chroma, (size_t)H * W, (size_t)H * W / 2, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_local_contrast_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                               const mi_isp_local_contrast* lc_host, void* ws, void* stream) {
+  return local_contrast_impl(src, dst, n, H, W, lc_host, ws, true, stream, "local_contrast_rgb_batch");
+}
+
+extern "C" int mi_isp_local_contrast_yuv420_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                                  const mi_isp_local_contrast* lc_host, void* ws, void* stream) {
+  return local_contrast_impl(src, dst, n, H, W, lc_host, ws, false, stream, "local_contrast_yuv420_batch");
 }
 
 // ---- measurement aid: HIP events around each data pass, on the stream it runs on ---------------------

@@ -205,6 +205,12 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--sharpen-radius", dest="sharpen_radius", type=int, default=1)
     tone.add_argument("--sharpen-threshold", dest="sharpen_threshold", type=int, default=0)
     tone.add_argument("--sharpen-overshoot", dest="sharpen_overshoot", type=int, default=None)
+    # local contrast (an extension): CLAHE on the luma of the u8 outputs, before sharpening; STRENGTH 0 .. 1, the tile grid
+    # (rows, columns of the written image) and the clip limit (1 .. 64; 0: no clip)
+    tone.add_argument("--local-contrast", dest="local_contrast", type=float, metavar="STRENGTH", default=None)
+    tone.add_argument("--local-contrast-tiles", dest="local_contrast_tiles", type=int, nargs=2, metavar=("TY", "TX"),
+                      default=None)
+    tone.add_argument("--local-contrast-clip", dest="local_contrast_clip", type=float, default=None)
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -219,6 +225,7 @@ def main(argv=None) -> int:
     from ..lens import LensDistortion
     from ..denoise import RawDenoise
     from ..sharpen import Sharpen
+    from ..local_contrast import LocalContrast
     args = build_parser().parse_args(argv)
     if args.scan is None and args.images is None:
         raise ValueError("No --scan or --images specified")
@@ -241,6 +248,12 @@ def main(argv=None) -> int:
                           overshoot=args.sharpen_overshoot)
     elif (args.sharpen_radius, args.sharpen_threshold, args.sharpen_overshoot) != (1, 0, None):
         raise ValueError("--sharpen-radius / --sharpen-threshold / --sharpen-overshoot need --sharpen AMOUNT")
+    local_contrast = None
+    if args.local_contrast is not None:                             # (also before any frame is read)
+        clip = 2.0 if args.local_contrast_clip is None else (args.local_contrast_clip or None)
+        local_contrast = LocalContrast(tuple(args.local_contrast_tiles or (8, 8)), clip, args.local_contrast)
+    elif args.local_contrast_tiles is not None or args.local_contrast_clip is not None:
+        raise ValueError("--local-contrast-tiles / --local-contrast-clip need --local-contrast STRENGTH")
     index = ScanIndex.of_scan(args.scan) if args.scan is not None else ScanIndex.of_directory(args.images)
     coords = {} if args.defect_pixels is None else load_defect_pixels(args.defect_pixels, index.cameras, args.width)
     calib = {} if args.lens_distortion is None else load_lens_distortion(args.lens_distortion, index.cameras)
@@ -251,7 +264,8 @@ def main(argv=None) -> int:
     isp = camera_isp.Camera32(bayer.BayerPattern.RGGB, transform=args.transform, moving_alpha=args.moving_alpha,
                               resize_width=args.resize_width, correct_colors=args.correct_colors, device=device,
                               black_level=black, white_level=args.white_level, lens_shading=shading,
-                              auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen)
+                              auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen,
+                              local_contrast=local_contrast)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
