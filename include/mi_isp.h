@@ -445,6 +445,30 @@ int mi_isp_local_contrast_rgb_batch(const uint8_t* const* src_host, uint8_t* con
                                     const mi_isp_local_contrast* lc_host, void* ws_dev, void* stream);
 int mi_isp_local_contrast_yuv420_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
                                        const mi_isp_local_contrast* lc_host, void* ws_dev, void* stream);
+/* ---- chroma noise reduction ("Chroma noise reduction") ---------------------------------------------------
+ * A luma-guided mean of the chroma on the grid of 2 x 2 pixel cells of a u8 image, in integer arithmetic: the output is the
+ * contract's bit for bit.  All values signed integers, >> arithmetic, // floor division; tl = luma_threshold and tc =
+ * chroma_threshold (0 .. 255), S = strength_q6 (the strength times 64, 0 .. 64), r = radius (1, 2 or 3).  Cell (a, b), a <
+ * (H + 1) / 2, b < (W + 1) / 2, holds pixels (min(2a + i, H - 1), min(2b + j, W - 1)), i, j in {0, 1}:
+ *   L = (77 R + 150 G + 29 B + 128) >> 8;  SL = sum of the cell's four L;  SB = sum of its four B - SL;  SR likewise with R
+ *   T(p) = the cells q = p + (i, j), |i|, |j| <= r, inside the grid (a cell outside it is no tap) with
+ *          |SL(q) - SL(p)| <= 4 tl, |SB(q) - SB(p)| <= 4 tc and |SR(q) - SR(p)| <= 4 tc
+ *   n = |T(p)|;  DB = sum over T(p) of SB(q) - SB(p);  DR likewise
+ *   db = (2 DB S + 256 n) // (512 n);  dr = (2 DR S + 256 n) // (512 n);  dg = ((-(77 dr + 29 db)) * 437 + 32768) >> 16
+ *   out_c = clamp(I_c + d_c, 0, 255) for each of the cell's pixels, c = R, G, B
+ *  - mi_isp_chroma_denoise_rgb_batch: n interleaved H x W x 3 images of one geometry, one launch per 32 images.
+ *  - mi_isp_chroma_denoise_yuv420_batch: n planar YUV 4:2:0 images (H * 3 / 2 rows of W bytes: the Y rows, the U plane, the
+ *    V plane; H, W of the Y plane, both even): SL = the sum of the cell's four Y, SB = 4 U(a, b), SR = 4 V(a, b);
+ *    U' = clamp(U + db, 0, 255), V' = clamp(V + dr, 0, 255); the Y rows are copied.
+ * src_host / dst_host: n device pointers each, read on the host.  The stencil cannot run in place: src[i] != dst[i], and
+ * the images must not overlap.  Host-side checks before any launch (error text names "chroma_denoise"): the settings'
+ * ranges, n >= 0, H, W >= 0 (both even for the planar form), NULL pointers, src == dst.  n == 0 and H * W == 0 are
+ * successful no-ops. */
+typedef struct { int32_t radius, luma_threshold, chroma_threshold, strength_q6; } mi_isp_chroma_denoise;
+int mi_isp_chroma_denoise_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                                    const mi_isp_chroma_denoise* settings_host, void* stream);
+int mi_isp_chroma_denoise_yuv420_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                                       const mi_isp_chroma_denoise* settings_host, void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==

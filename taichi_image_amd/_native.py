@@ -64,6 +64,12 @@ class LocalContrast(ctypes.Structure):
     _fields_ = [("tiles_y", c_int32), ("tiles_x", c_int32), ("clip_q8", c_int32), ("strength_q6", c_int32)]
 
 
+class ChromaDenoise(ctypes.Structure):
+    """mi_isp_chroma_denoise: the window radius in cells (1, 2 or 3), the luma and chroma thresholds (0 .. 255) and the
+    strength times 64 (0 .. 64)."""
+    _fields_ = [("radius", c_int32), ("luma_threshold", c_int32), ("chroma_threshold", c_int32), ("strength_q6", c_int32)]
+
+
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SIGNATURES = {
@@ -149,6 +155,9 @@ SIGNATURES = {
                                                 _P]),
     "mi_isp_local_contrast_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(LocalContrast),
                                                    _P, _P]),
+    "mi_isp_chroma_denoise_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise), _P]),
+    "mi_isp_chroma_denoise_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise),
+                                                   _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,

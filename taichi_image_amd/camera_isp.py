@@ -24,6 +24,7 @@ from . import defects as _defects
 from . import denoise as _dn
 from . import lens as _lens
 from . import sharpen as _shp
+from . import chroma_denoise as _cdn
 from . import local_contrast as _lc
 from . import white_balance as _wb
 from . import distributed as _dist
@@ -282,7 +283,8 @@ def camera_isp(name: str, dtype=types.f32):
                      auto_white_balance=False,
                      raw_denoise=None,
                      sharpen=None,
-                     local_contrast=None):
+                     local_contrast=None,
+                     chroma_denoise=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -301,6 +303,7 @@ def camera_isp(name: str, dtype=types.f32):
             raw_denoise = _dn.check_raw_denoise(raw_denoise)
             sharpen = _shp.check_sharpen(sharpen)
             local_contrast = _lc.check_local_contrast(local_contrast)
+            chroma_denoise = _cdn.check_chroma_denoise(chroma_denoise)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -352,6 +355,10 @@ def camera_isp(name: str, dtype=types.f32):
             # local contrast (an extension): the LocalContrast applied in place to every u8 output of the tonemaps, before
             # sharpening, or None (the tonemaps run exactly as without it).  DESIGN.md 3, "Local contrast".
             self._local_contrast = local_contrast
+            # chroma noise reduction (an extension): the ChromaDenoise applied to every u8 output of the tonemaps, before
+            # local contrast and sharpening, or None (the tonemaps run exactly as without it).  DESIGN.md 3, "Chroma noise
+            # reduction".
+            self._chroma_denoise = chroma_denoise
 
         @property
         def _demosaic_pattern(self):
@@ -364,7 +371,7 @@ def camera_isp(name: str, dtype=types.f32):
                 color_correction: Optional[np.ndarray] = None,
                 transform: Optional[interpolate.ImageTransform] = None,
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
-                raw_denoise=None, sharpen=None, local_contrast=None):
+                raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -376,7 +383,8 @@ def camera_isp(name: str, dtype=types.f32):
             rebuilds the effective grid from the new grid and the current gains on the device.
             raw_denoise (the extension): None leaves it, False turns it off, a RawDenoise replaces it.
             sharpen (the extension): None leaves it, False turns it off, a Sharpen replaces it.
-            local_contrast (the extension): None leaves it, False turns it off, a LocalContrast replaces it."""
+            local_contrast (the extension): None leaves it, False turns it off, a LocalContrast replaces it.
+            chroma_denoise (the extension): None leaves it, False turns it off, a ChromaDenoise replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -388,6 +396,8 @@ def camera_isp(name: str, dtype=types.f32):
             new_sharpen = None if sharpen is None or sharpen is False else _shp.check_sharpen(sharpen)
             new_lc = (None if local_contrast is None or local_contrast is False
                       else _lc.check_local_contrast(local_contrast))
+            new_cdn = (None if chroma_denoise is None or chroma_denoise is False
+                       else _cdn.check_chroma_denoise(chroma_denoise))
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -440,6 +450,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._local_contrast = None
             elif new_lc is not None:
                 self._local_contrast = new_lc
+            if chroma_denoise is False:
+                self._chroma_denoise = None
+            elif new_cdn is not None:
+                self._chroma_denoise = new_cdn
             if auto_white_balance is not None:
                 if awb is None:
                     self._awb_off()
@@ -558,10 +572,18 @@ def camera_isp(name: str, dtype=types.f32):
                     if isinstance(im, torch.Tensor) and im.ndim >= 2:
                         _lc.check_shape(*_out_shape(im, self.transform)[:2], self._local_contrast)
 
+        @property
+        def chroma_denoise(self) -> Optional[_cdn.ChromaDenoise]:
+            """The ChromaDenoise the tonemaps apply to their u8 outputs, or None."""
+            return self._chroma_denoise
+
         def _finished(self, outputs, yuv420=False):
-            """The u8 outputs of a tonemap as the caller gets them: local contrast, in place on `outputs` (the tonemap's
-            own freshly allocated tensors), then sharpening; with neither set, `outputs` themselves.  DESIGN.md 3, "Local
+            """The u8 outputs of a tonemap as the caller gets them: chroma noise reduction (a stencil: new tensors, which
+            take the place of `outputs`), then local contrast, in place on those (or on the tonemap's own freshly allocated
+            tensors), then sharpening; with none set, `outputs` themselves.  DESIGN.md 3, "Chroma noise reduction", "Local
             contrast" and "Output sharpening"."""
+            if self._chroma_denoise is not None and outputs:
+                outputs = _cdn.apply(outputs, self._chroma_denoise, yuv420)
             if self._local_contrast is not None and outputs:
                 _lc.apply(outputs, self._local_contrast, yuv420, inplace=True)
             return self._sharpened(outputs, yuv420)
@@ -941,7 +963,8 @@ def camera_isp(name: str, dtype=types.f32):
             and W % 16 == 0: the u8 RGB images are never written.  Same side effects as tonemap_reinhard.
             With sharpen= set, the Y plane of each YUV image is sharpened (sharpen.unsharp_mask_yuv420), which is not the
             YUV image of a sharpened RGB output; local_contrast= likewise equalises the Y plane
-            (local_contrast.clahe_yuv420)."""
+            (local_contrast.clahe_yuv420), and chroma_denoise= filters the U and V planes
+            (chroma_denoise.chroma_denoise_yuv420), before both."""
             from . import color
             _typecheck("images", images, list)
             self._check_local_contrast_fits(images)

@@ -16,6 +16,7 @@
 #include "isp_awb.h"
 #include "isp_denoise.h"
 #include "isp_sharpen.h"
+#include "isp_chroma_denoise.h"
 #include "isp_local_contrast.h"
 #include <mutex>
 #include <atomic>
@@ -871,6 +872,61 @@ extern "C" int mi_isp_local_contrast_rgb_batch(const uint8_t* const* src, uint8_
 extern "C" int mi_isp_local_contrast_yuv420_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
                                                   const mi_isp_local_contrast* lc_host, void* ws, void* stream) {
   return local_contrast_impl(src, dst, n, H, W, lc_host, ws, false, stream, "local_contrast_yuv420_batch");
+}
+
+// ---- chroma noise reduction (isp_chroma_denoise.h; DESIGN.md 3, "Chroma noise reduction") -----------------------------
+// n u8 images of one geometry (rgb: H x W x 3; else planar YUV 4:2:0 with an H x W Y plane, whose Y rows are copied): every
+// image's pointers in the kernel arguments, 32 per launch
+static int chroma_denoise_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                               const mi_isp_chroma_denoise* s, bool rgb, void* stream, const char* who) {
+  MI_REQUIRE(s, "%s: null chroma_denoise settings", who);
+  MI_REQUIRE(s->radius >= 1 && s->radius <= 3, "%s: chroma_denoise radius %d (1, 2 or 3)", who, (int)s->radius);
+  MI_REQUIRE(s->luma_threshold >= 0 && s->luma_threshold <= 255, "%s: chroma_denoise luma_threshold %d outside 0 .. 255", who,
+             (int)s->luma_threshold);
+  MI_REQUIRE(s->chroma_threshold >= 0 && s->chroma_threshold <= 255, "%s: chroma_denoise chroma_threshold %d outside 0 .. 255",
+             who, (int)s->chroma_threshold);
+  MI_REQUIRE(s->strength_q6 >= 0 && s->strength_q6 <= 64, "%s: chroma_denoise strength_q6 %d outside 0 .. 64", who,
+             (int)s->strength_q6);
+  MI_REQUIRE(n >= 0, "%s: chroma_denoise with %d images", who, n);
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad chroma_denoise shape %dx%d", who, H, W);
+  // (one 256-thread block per tile: the launch's work-items per image must stay below 2^32)
+  MI_REQUIRE(H < (1 << 22) && W < (1 << 24) &&
+                 (uint64_t)((W + 2 * cdn::TILE_CW - 1) / (2 * cdn::TILE_CW)) *
+                         (uint64_t)((H + 2 * cdn::TILE_CH - 1) / (2 * cdn::TILE_CH)) < (1u << 24),
+             "%s: chroma_denoise image %dx%d too large", who, H, W);
+  MI_REQUIRE(rgb || (H % 2 == 0 && W % 2 == 0),
+             "%s: the Y plane of a chroma_denoise YUV 4:2:0 image must have even sides, got %dx%d", who, H, W);
+  MI_REQUIRE(src && dst, "%s: null chroma_denoise image list", who);
+  if (n == 0 || (size_t)H * (size_t)W == 0) return 0;
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && dst[i], "%s: chroma_denoise image %d has a null pointer", who, i);
+    MI_REQUIRE(src[i] != dst[i], "%s: chroma_denoise image %d: the filter cannot run in place", who, i);
+  }
+  cdn::Args a = {};
+  a.H = H; a.W = W;
+  a.tl4 = 4 * s->luma_threshold; a.tc4 = 4 * s->chroma_threshold; a.strength_q6 = s->strength_q6;
+  for (int i0 = 0; i0 < n; i0 += cdn::MAX_IMAGES) {
+    a.n_images = n - i0 < cdn::MAX_IMAGES ? n - i0 : cdn::MAX_IMAGES;
+    for (int i = 0; i < a.n_images; ++i) a.im[i] = {src[i0 + i], dst[i0 + i]};
+    if (int rc = cdn::launch(a, rgb, s->radius, (hipStream_t)stream)) return rc;
+    if (!rgb) {
+      shp::Args y = {};                               // the Y rows
+      y.n_images = a.n_images;
+      for (int i = 0; i < a.n_images; ++i) y.im[i] = a.im[i];
+      if (int rc = shp::launch_copy(y, 0, (size_t)H * W, (hipStream_t)stream)) return rc;
+    }
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_chroma_denoise_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                               const mi_isp_chroma_denoise* settings, void* stream) {
+  return chroma_denoise_impl(src, dst, n, H, W, settings, true, stream, "chroma_denoise_rgb_batch");
+}
+
+extern "C" int mi_isp_chroma_denoise_yuv420_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                                  const mi_isp_chroma_denoise* settings, void* stream) {
+  return chroma_denoise_impl(src, dst, n, H, W, settings, false, stream, "chroma_denoise_yuv420_batch");
 }
 
 // ---- measurement aid: HIP events around each data pass, on the stream it runs on ---------------------

@@ -211,6 +211,12 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--local-contrast-tiles", dest="local_contrast_tiles", type=int, nargs=2, metavar=("TY", "TX"),
                       default=None)
     tone.add_argument("--local-contrast-clip", dest="local_contrast_clip", type=float, default=None)
+    # chroma noise reduction (an extension): a luma-guided mean of the chroma of the u8 outputs, before local contrast and
+    # sharpening; STRENGTH 0 .. 1, the window radius in 2 x 2 pixel cells (1, 2 or 3) and the luma and chroma thresholds
+    tone.add_argument("--chroma-denoise", dest="chroma_denoise", type=float, metavar="STRENGTH", default=None)
+    tone.add_argument("--chroma-denoise-radius", dest="chroma_denoise_radius", type=int, default=None)
+    tone.add_argument("--chroma-denoise-thresholds", dest="chroma_denoise_thresholds", type=int, nargs=2,
+                      metavar=("LUMA", "CHROMA"), default=None)
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -226,6 +232,7 @@ def main(argv=None) -> int:
     from ..denoise import RawDenoise
     from ..sharpen import Sharpen
     from ..local_contrast import LocalContrast
+    from ..chroma_denoise import ChromaDenoise
     args = build_parser().parse_args(argv)
     if args.scan is None and args.images is None:
         raise ValueError("No --scan or --images specified")
@@ -254,6 +261,13 @@ def main(argv=None) -> int:
         local_contrast = LocalContrast(tuple(args.local_contrast_tiles or (8, 8)), clip, args.local_contrast)
     elif args.local_contrast_tiles is not None or args.local_contrast_clip is not None:
         raise ValueError("--local-contrast-tiles / --local-contrast-clip need --local-contrast STRENGTH")
+    chroma_denoise = None
+    if args.chroma_denoise is not None:                             # (also before any frame is read)
+        tl, tc = args.chroma_denoise_thresholds or (8, 12)
+        chroma_denoise = ChromaDenoise(2 if args.chroma_denoise_radius is None else args.chroma_denoise_radius, tl, tc,
+                                       args.chroma_denoise)
+    elif args.chroma_denoise_radius is not None or args.chroma_denoise_thresholds is not None:
+        raise ValueError("--chroma-denoise-radius / --chroma-denoise-thresholds need --chroma-denoise STRENGTH")
     index = ScanIndex.of_scan(args.scan) if args.scan is not None else ScanIndex.of_directory(args.images)
     coords = {} if args.defect_pixels is None else load_defect_pixels(args.defect_pixels, index.cameras, args.width)
     calib = {} if args.lens_distortion is None else load_lens_distortion(args.lens_distortion, index.cameras)
@@ -265,7 +279,7 @@ def main(argv=None) -> int:
                               resize_width=args.resize_width, correct_colors=args.correct_colors, device=device,
                               black_level=black, white_level=args.white_level, lens_shading=shading,
                               auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen,
-                              local_contrast=local_contrast)
+                              local_contrast=local_contrast, chroma_denoise=chroma_denoise)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
