@@ -469,6 +469,34 @@ int mi_isp_chroma_denoise_rgb_batch(const uint8_t* const* src_host, uint8_t* con
                                     const mi_isp_chroma_denoise* settings_host, void* stream);
 int mi_isp_chroma_denoise_yuv420_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
                                        const mi_isp_chroma_denoise* settings_host, void* stream);
+/* ---- 3D colour LUT ("Colour LUT") --------------------------------------------------------------------------
+ * Tetrahedral interpolation in an N x N x N table on interleaved u8 RGB images, in integer arithmetic: the output is the
+ * contract's bit for bit.  The table T[r][g][b] holds the output colour (u8 R, G, B) at input (255 r, 255 g, 255 b) / (N - 1);
+ * table_dev: N^3 dwords on the device, entry (r * N + g) * N + b = R | G << 8 | B << 16.  N = n_points (2 .. 65), S =
+ * strength_q6 (the strength times 64, 0 .. 64).  All values signed integers, // floor division, >> arithmetic.  Per pixel,
+ * v_c its input codes, c = R, G, B:
+ *   p_c = v_c (N - 1);  i_c = p_c // 255;  f_c = p_c - 255 i_c  (0 .. 254; v_c = 255 gives i_c = N - 1, f_c = 0)
+ *   j_c = min(i_c + 1, N - 1)
+ *   a, b, d = the three axes ordered so that f_a >= f_b >= f_d (the order of tied fractions does not matter: the corner that
+ *             differs has weight 0)
+ *   C0 = T[i_R][i_G][i_B];  C1 = C0's index with axis a moved to j_a;  C2 = C1's with axis b moved to j_b;  C3 = T[j_R][j_G][j_B]
+ *   y_c = (C0_c (255 - f_a) + C1_c (f_a - f_b) + C2_c (f_b - f_d) + C3_c f_d + 127) // 255
+ *   out_c = v_c + (((y_c - v_c) S + 32) >> 6)        (between v_c and y_c: no clamp; S = 64 gives y_c, S = 0 gives v_c)
+ * Every table index stays inside the table whatever its weight is (the min above).
+ *  - mi_isp_color_lut_rgb_batch: n H x W x 3 images of one geometry, one launch per 32 images.  The table is kept in LDS
+ *    (N <= 33) or read through L2, whichever is faster for the launch's size; the output does not depend
+ *    on it.
+ *  - mi_isp_color_lut_rgb_batch_path: the same with the path given (for measurements and tests): 0 the dispatcher's choice,
+ *    1 the table in LDS (n_points <= 33), 2 the table in global memory.
+ * src_host / dst_host: n device pointers each, read on the host.  The operator is pointwise: src[i] == dst[i] is allowed,
+ * any other overlap is not.  Host-side checks before any launch (error text names "color_lut"): the settings' ranges, the
+ * path, n >= 0, H, W >= 0, NULL pointers.  n == 0 and H * W == 0 are successful no-ops.  No host synchronisation; the
+ * launches run on `stream`. */
+typedef struct { int32_t n_points, strength_q6; } mi_isp_color_lut;
+int mi_isp_color_lut_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                               const uint32_t* table_dev, const mi_isp_color_lut* settings_host, void* stream);
+int mi_isp_color_lut_rgb_batch_path(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                                    const uint32_t* table_dev, const mi_isp_color_lut* settings_host, int path, void* stream);
 /* The stateless chain of test/pipeline.py:26-32 (BASELINE config 2) fused:
  * decode12(scaled, work_dtype) -> bayer_to_rgb -> tonemap_reinhard(dtype=out_dtype) in four data passes.
  * The demosaiced work-dtype image is kept between the passes in out_dev itself when out_dtype ==

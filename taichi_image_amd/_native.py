@@ -70,6 +70,11 @@ class ChromaDenoise(ctypes.Structure):
     _fields_ = [("radius", c_int32), ("luma_threshold", c_int32), ("chroma_threshold", c_int32), ("strength_q6", c_int32)]
 
 
+class ColorLut(ctypes.Structure):
+    """mi_isp_color_lut: the table's points per axis (2 .. 65) and the strength times 64 (0 .. 64)."""
+    _fields_ = [("n_points", c_int32), ("strength_q6", c_int32)]
+
+
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SIGNATURES = {
@@ -158,6 +163,9 @@ SIGNATURES = {
     "mi_isp_chroma_denoise_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise), _P]),
     "mi_isp_chroma_denoise_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise),
                                                    _P]),
+    "mi_isp_color_lut_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, _P, POINTER(ColorLut), _P]),
+    "mi_isp_color_lut_rgb_batch_path": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, _P, POINTER(ColorLut), c_int,
+                                                _P]),
     "mi_isp_load_packed_metered_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,

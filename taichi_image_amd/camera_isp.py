@@ -25,6 +25,7 @@ from . import denoise as _dn
 from . import lens as _lens
 from . import sharpen as _shp
 from . import chroma_denoise as _cdn
+from . import color_lut as _clut
 from . import local_contrast as _lc
 from . import white_balance as _wb
 from . import distributed as _dist
@@ -284,7 +285,8 @@ def camera_isp(name: str, dtype=types.f32):
                      raw_denoise=None,
                      sharpen=None,
                      local_contrast=None,
-                     chroma_denoise=None):
+                     chroma_denoise=None,
+                     color_lut=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -304,6 +306,7 @@ def camera_isp(name: str, dtype=types.f32):
             sharpen = _shp.check_sharpen(sharpen)
             local_contrast = _lc.check_local_contrast(local_contrast)
             chroma_denoise = _cdn.check_chroma_denoise(chroma_denoise)
+            color_lut = _clut.check_color_lut(color_lut)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -359,6 +362,12 @@ def camera_isp(name: str, dtype=types.f32):
             # local contrast and sharpening, or None (the tonemaps run exactly as without it).  DESIGN.md 3, "Chroma noise
             # reduction".
             self._chroma_denoise = chroma_denoise
+            # 3D colour LUT (an extension): the ColorLut every u8 RGB output of the tonemaps is mapped through, in place,
+            # before the other output operators, or None (the tonemaps run exactly as without it).  DESIGN.md 3, "Colour
+            # LUT".
+            self._color_lut = color_lut
+            if color_lut is not None:
+                color_lut._device_table(self.device)         # (uploaded now: a captured step finds it on the device)
 
         @property
         def _demosaic_pattern(self):
@@ -371,7 +380,7 @@ def camera_isp(name: str, dtype=types.f32):
                 color_correction: Optional[np.ndarray] = None,
                 transform: Optional[interpolate.ImageTransform] = None,
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
-                raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None):
+                raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -384,7 +393,8 @@ def camera_isp(name: str, dtype=types.f32):
             raw_denoise (the extension): None leaves it, False turns it off, a RawDenoise replaces it.
             sharpen (the extension): None leaves it, False turns it off, a Sharpen replaces it.
             local_contrast (the extension): None leaves it, False turns it off, a LocalContrast replaces it.
-            chroma_denoise (the extension): None leaves it, False turns it off, a ChromaDenoise replaces it."""
+            chroma_denoise (the extension): None leaves it, False turns it off, a ChromaDenoise replaces it.
+            color_lut (the extension): None leaves it, False turns it off, a ColorLut replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -398,6 +408,7 @@ def camera_isp(name: str, dtype=types.f32):
                       else _lc.check_local_contrast(local_contrast))
             new_cdn = (None if chroma_denoise is None or chroma_denoise is False
                        else _cdn.check_chroma_denoise(chroma_denoise))
+            new_clut = None if color_lut is None or color_lut is False else _clut.check_color_lut(color_lut)
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -454,6 +465,11 @@ def camera_isp(name: str, dtype=types.f32):
                 self._chroma_denoise = None
             elif new_cdn is not None:
                 self._chroma_denoise = new_cdn
+            if color_lut is False:
+                self._color_lut = None
+            elif new_clut is not None:
+                self._color_lut = new_clut
+                new_clut._device_table(self.device)
             if auto_white_balance is not None:
                 if awb is None:
                     self._awb_off()
@@ -577,11 +593,19 @@ def camera_isp(name: str, dtype=types.f32):
             """The ChromaDenoise the tonemaps apply to their u8 outputs, or None."""
             return self._chroma_denoise
 
+        @property
+        def color_lut(self) -> Optional[_clut.ColorLut]:
+            """The ColorLut the tonemaps map their u8 RGB outputs through, or None."""
+            return self._color_lut
+
         def _finished(self, outputs, yuv420=False):
-            """The u8 outputs of a tonemap as the caller gets them: chroma noise reduction (a stencil: new tensors, which
-            take the place of `outputs`), then local contrast, in place on those (or on the tonemap's own freshly allocated
-            tensors), then sharpening; with none set, `outputs` themselves.  DESIGN.md 3, "Chroma noise reduction", "Local
-            contrast" and "Output sharpening"."""
+            """The u8 outputs of a tonemap as the caller gets them: the colour LUT, in place on `outputs` (the tonemap's
+            own freshly allocated RGB tensors; planar YUV outputs have been through it before their conversion:
+            tonemap_reinhard_yuv420), then chroma noise reduction (a stencil: new tensors, which take the place of
+            `outputs`), then local contrast, in place on those, then sharpening; with none set, `outputs` themselves.
+            DESIGN.md 3, "Colour LUT", "Chroma noise reduction", "Local contrast" and "Output sharpening"."""
+            if self._color_lut is not None and outputs and not yuv420:
+                _clut.apply(outputs, self._color_lut, inplace=True)
             if self._chroma_denoise is not None and outputs:
                 outputs = _cdn.apply(outputs, self._chroma_denoise, yuv420)
             if self._local_contrast is not None and outputs:
@@ -964,14 +988,18 @@ def camera_isp(name: str, dtype=types.f32):
             With sharpen= set, the Y plane of each YUV image is sharpened (sharpen.unsharp_mask_yuv420), which is not the
             YUV image of a sharpened RGB output; local_contrast= likewise equalises the Y plane
             (local_contrast.clahe_yuv420), and chroma_denoise= filters the U and V planes
-            (chroma_denoise.chroma_denoise_yuv420), before both."""
+            (chroma_denoise.chroma_denoise_yuv420), before both.  A 3D LUT has no planar form: with color_lut= set the RGB
+            outputs are written, mapped through the table and converted (the unfused branch), then the planar operators
+            run."""
             from . import color
             _typecheck("images", images, list)
             self._check_local_contrast_fits(images)
             H, W = images[0].shape[:2]
-            if self.transform != interpolate.ImageTransform.none or H % 2 or W % 16:
-                return self._finished([color.rgb_yuv420_image(o) for o in self._tonemap_reinhard(
-                    images, gamma, intensity, light_adapt, color_adapt)], yuv420=True)
+            if self.transform != interpolate.ImageTransform.none or H % 2 or W % 16 or self._color_lut is not None:
+                rgb = self._tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt)
+                if self._color_lut is not None and rgb:
+                    _clut.apply(rgb, self._color_lut, inplace=True)
+                return self._finished([color.rgb_yuv420_image(o) for o in rgb], yuv420=True)
             for n, v in (("gamma", gamma), ("intensity", intensity), ("light_adapt", light_adapt),
                          ("color_adapt", color_adapt)):
                 _typecheck(n, v, float)

@@ -17,6 +17,7 @@
 #include "isp_denoise.h"
 #include "isp_sharpen.h"
 #include "isp_chroma_denoise.h"
+#include "isp_color_lut.h"
 #include "isp_local_contrast.h"
 #include <mutex>
 #include <atomic>
@@ -927,6 +928,51 @@ extern "C" int mi_isp_chroma_denoise_rgb_batch(const uint8_t* const* src, uint8_
 extern "C" int mi_isp_chroma_denoise_yuv420_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
                                                   const mi_isp_chroma_denoise* settings, void* stream) {
   return chroma_denoise_impl(src, dst, n, H, W, settings, false, stream, "chroma_denoise_yuv420_batch");
+}
+
+// ---- 3D colour LUT (isp_color_lut.h; DESIGN.md 3, "Colour LUT") ------------------------------------------------------------
+// n interleaved u8 RGB images of one geometry through one table: every image's pointers in the kernel arguments, 32 per
+// launch; path: clut::Path (the dispatcher's choice, or one path forced)
+static int color_lut_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W, const uint32_t* table,
+                          const mi_isp_color_lut* s, int path, void* stream, const char* who) {
+  MI_REQUIRE(s, "%s: null color_lut settings", who);
+  MI_REQUIRE(s->n_points >= clut::MIN_POINTS && s->n_points <= clut::MAX_POINTS, "%s: color_lut n_points %d outside %d .. %d",
+             who, (int)s->n_points, clut::MIN_POINTS, clut::MAX_POINTS);
+  MI_REQUIRE(s->strength_q6 >= 0 && s->strength_q6 <= 64, "%s: color_lut strength_q6 %d outside 0 .. 64", who,
+             (int)s->strength_q6);
+  MI_REQUIRE(path == clut::PATH_AUTO || path == clut::PATH_GLOBAL || (path == clut::PATH_LDS && s->n_points <= clut::LDS_POINTS),
+             "%s: color_lut path %d (0: the dispatcher's, 1: LDS, n_points <= %d, 2: global)", who, path, clut::LDS_POINTS);
+  MI_REQUIRE(n >= 0, "%s: color_lut with %d images", who, n);
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad color_lut shape %dx%d", who, H, W);
+  MI_REQUIRE((uint64_t)H * (uint64_t)W < (1ull << 31), "%s: color_lut image %dx%d too large", who, H, W);
+  MI_REQUIRE(table, "%s: null color_lut table", who);
+  MI_REQUIRE(src && dst, "%s: null color_lut image list", who);
+  if (n == 0 || (size_t)H * (size_t)W == 0) return 0;
+  for (int i = 0; i < n; ++i) MI_REQUIRE(src[i] && dst[i], "%s: color_lut image %d has a null pointer", who, i);
+  int dev = 0;
+  MI_HIP(hipGetDevice(&dev));
+  clut::Args a = {};
+  a.pixels = (uint32_t)((size_t)H * (size_t)W);
+  a.dword_rows = W % 4 == 0;
+  a.n_points = s->n_points; a.strength_q6 = s->strength_q6;
+  a.table = table;
+  for (int i0 = 0; i0 < n; i0 += clut::MAX_IMAGES) {
+    a.n_images = n - i0 < clut::MAX_IMAGES ? n - i0 : clut::MAX_IMAGES;
+    for (int i = 0; i < a.n_images; ++i) a.im[i] = {src[i0 + i], dst[i0 + i]};
+    if (int rc = clut::launch(a, (clut::Path)path, ew::device_cus(dev), (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_color_lut_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                          const uint32_t* table, const mi_isp_color_lut* settings, void* stream) {
+  return color_lut_impl(src, dst, n, H, W, table, settings, clut::PATH_AUTO, stream, "color_lut_rgb_batch");
+}
+
+extern "C" int mi_isp_color_lut_rgb_batch_path(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                               const uint32_t* table, const mi_isp_color_lut* settings, int path,
+                                               void* stream) {
+  return color_lut_impl(src, dst, n, H, W, table, settings, path, stream, "color_lut_rgb_batch_path");
 }
 
 // ---- measurement aid: HIP events around each data pass, on the stream it runs on ---------------------

@@ -217,6 +217,10 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--chroma-denoise-radius", dest="chroma_denoise_radius", type=int, default=None)
     tone.add_argument("--chroma-denoise-thresholds", dest="chroma_denoise_thresholds", type=int, nargs=2,
                       metavar=("LUMA", "CHROMA"), default=None)
+    # 3D colour LUT (an extension): a .cube file every u8 output is mapped through (tetrahedral interpolation), before the
+    # other output operators; STRENGTH 0 .. 1 blends between the input and the table's colour
+    tone.add_argument("--color-lut", dest="color_lut", type=Path, metavar="FILE.cube", default=None)
+    tone.add_argument("--color-lut-strength", dest="color_lut_strength", type=float, metavar="STRENGTH", default=None)
     out = ap.add_argument_group("output")
     out.add_argument("--write", type=Path, default=None)
     out.add_argument("--rows", type=int, default=2)
@@ -233,6 +237,7 @@ def main(argv=None) -> int:
     from ..sharpen import Sharpen
     from ..local_contrast import LocalContrast
     from ..chroma_denoise import ChromaDenoise
+    from ..color_lut import ColorLut
     args = build_parser().parse_args(argv)
     if args.scan is None and args.images is None:
         raise ValueError("No --scan or --images specified")
@@ -268,6 +273,11 @@ def main(argv=None) -> int:
                                        args.chroma_denoise)
     elif args.chroma_denoise_radius is not None or args.chroma_denoise_thresholds is not None:
         raise ValueError("--chroma-denoise-radius / --chroma-denoise-thresholds need --chroma-denoise STRENGTH")
+    color_lut = None
+    if args.color_lut is not None:                                  # (read and checked before any frame is read)
+        color_lut = ColorLut.from_cube(args.color_lut, 1.0 if args.color_lut_strength is None else args.color_lut_strength)
+    elif args.color_lut_strength is not None:
+        raise ValueError("--color-lut-strength needs --color-lut FILE.cube")
     index = ScanIndex.of_scan(args.scan) if args.scan is not None else ScanIndex.of_directory(args.images)
     coords = {} if args.defect_pixels is None else load_defect_pixels(args.defect_pixels, index.cameras, args.width)
     calib = {} if args.lens_distortion is None else load_lens_distortion(args.lens_distortion, index.cameras)
@@ -279,7 +289,7 @@ def main(argv=None) -> int:
                               resize_width=args.resize_width, correct_colors=args.correct_colors, device=device,
                               black_level=black, white_level=args.white_level, lens_shading=shading,
                               auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen,
-                              local_contrast=local_contrast, chroma_denoise=chroma_denoise)
+                              local_contrast=local_contrast, chroma_denoise=chroma_denoise, color_lut=color_lut)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
