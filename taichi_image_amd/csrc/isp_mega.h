@@ -551,18 +551,24 @@ MI_DEV void accumulate_row2(const WinRow2 (&win)[6], const f2 (&wq2)[4], f2 (&v2
 struct ReinhardK2 {
   f2 ml, ek, li;                       // {mean, la}, {ei, map_key}, {lo, inv}
 };
-MI_DEV f2 norm01_2(f2 x, const ReinhardK2& k) {
-  const f2 d = (x - bc<0>(k.li)) * bc<1>(k.li);
+MI_DEV f2 norm01_2(f2 x, f2 li) {                       // li = {lo, inv}
+  const f2 d = (x - bc<0>(li)) * bc<1>(li);
   return f2{clamp01(d.x), clamp01(d.y)};
 }
-MI_DEV f2 reinhard_adapt2(const f2 (&t)[3], const ReinhardK2& k) {
+MI_DEV f2 norm01_2(f2 x, const ReinhardK2& k) { return norm01_2(x, k.li); }
+// The adaptation term in two parts: the gray of the pixels needs none of the frame's scalars (the LDS rows' gray is
+// computed inside barrier 0's wait: frame_kernel's `ahead`), the rest needs mean, ei and map_key.
+MI_DEV f2 reinhard_gray2(const f2 (&t)[3]) {
   const f2 w01 = {0.587f, 0.299f}, w2 = {0.114f, 0.114f};
-  const f2 g = __builtin_elementwise_fma(t[2], w2, __builtin_elementwise_fma(t[0], bc<1>(w01), t[1] * bc<0>(w01)));
+  return __builtin_elementwise_fma(t[2], w2, __builtin_elementwise_fma(t[0], bc<1>(w01), t[1] * bc<0>(w01)));
+}
+MI_DEV f2 reinhard_adapt_g2(f2 g, const ReinhardK2& k) {
   const f2 am = __builtin_elementwise_fma(bc<1>(k.ml), g - bc<0>(k.ml), bc<0>(k.ml));
   const f2 b = bc<0>(k.ek) * am;
   const f2 e = bc<1>(k.ek) * f2{hw_log2(b.x), hw_log2(b.y)};
   return f2{hw_exp2(e.x), hw_exp2(e.y)};
 }
+MI_DEV f2 reinhard_adapt2(const f2 (&t)[3], const ReinhardK2& k) { return reinhard_adapt_g2(reinhard_gray2(t), k); }
 MI_DEV f2 reinhard_map2(f2 t, f2 ad) {
   const f2 s = ad + t;
   return t * f2{hw_rcp(s.x), hw_rcp(s.y)};
@@ -626,6 +632,16 @@ MI_DEV float pk_hi(uint32_t v) { half_t h[2]; __builtin_memcpy(h, &v, 4); return
 #define MI_MEGA_PRE2 1
 #endif
 
+// The scalar-free half of phase C's work on the LDS rows (read, conversions, normalisation, gray, smallest and largest
+// channel) runs between a wave's post at barrier 0 and its first poll - and again, for frames whose bounds are not (0, 1),
+// between post 1 and its poll (frame_kernel: `ahead`).  0 = phase C does it all, as before.
+#ifndef MI_MEGA_AHEAD
+#define MI_MEGA_AHEAD 1
+#endif
+// (Measured and taken out - profiles/lds_rows_ahead_bench.txt, lds_rows_ahead_knobs.patch puts them back: the ahead work at
+// issue priority 0 instead of the priority phase A's last turn left, and the watch stage's first poll issued in front of
+// it.  Neither moved the frame by more than the runs scatter.)
+
 // RGB: color_adapt != 0 (per-channel sums in the statistics).  Two kernels instead of a run-time flag: with both kinds of
 // statistics in one body the register allocator spilled 13 VGPRs to scratch in phase A and reloaded them in B / C / D,
 // which cost 3.3 us per frame (58.2 -> 54.9).  Split, every variant fits 256 VGPRs without scratch - as long as the
@@ -639,6 +655,9 @@ MI_DEV float pk_hi(uint32_t v) { half_t h[2]; __builtin_memcpy(h, &v, 4); return
 //   (0, 1) GRBG      PKC (PKA: 5 spilled)     scalar
 //   (1, 0) GBRG      PKA + PKC                scalar
 //   (1, 1) BGGR      PKA + PKC                scalar
+//   all four         + LDS rows ahead         none (no tone_bounds_row on the arm it executes)
+// LDS rows ahead (`ahead`, MI_MEGA_AHEAD): the scalar-free half of phase C's work on the five LDS rows in the waits of barriers
+// 0 and 1; 120 registers between the post and phase C's fifth row, every kernel still at 256 VGPRs without scratch.
 // In every PKC kernel the one LDS row mapped between post 2 and its poll stays scalar (on pairs: 8 spilled around the fold).
 // The results are the same bits in every form.
 // (A variant without the row conditions for frames whose height is a multiple of 12 was tried: with no branches between
@@ -899,8 +918,44 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
     unpack_row(pk, t);
   };
 
+  // Phase C's LDS rows, ahead of the barrier they wait behind.  Phase C wants only the bounds of their mapped values
+  // (tone_bounds_row), and with color_adapt == 0 half of that work needs no scalar of the frame: the read, the conversions,
+  // the normalisation, rgb_gray and the pixel's smallest and largest channel.  A wave does it between its post and its first
+  // poll - the median wave idles 5.7 us there - under the assumption phase A makes for the statistics: bounds (0, 1).  When
+  // they are not, the values are computed again (now normalised) inside barrier 1's wait.  Per pixel pair {k, k + 4} the
+  // operations and their order are those of tone_bounds_row; 24 registers per row, dead once phase C has taken the row -
+  // before the first register row's mapped values exist.  (The register rows have no such slack: round 4's "gray ahead".)
+  constexpr bool AHEAD = !RGB && MI_MEGA_AHEAD != 0;
+  f2 gpre[AHEAD ? NL : 1][4], mnpre[AHEAD ? NL : 1][4], mxpre[AHEAD ? NL : 1][4];
+  auto ahead = [&](auto unit_c, f2 li) __attribute__((always_inline)) {
+    constexpr bool UNIT = decltype(unit_c)::value;
+    if constexpr (AHEAD) {
+      static_for<0, NL>([&](auto rrc) {
+        constexpr int RR = decltype(rrc)::value;
+        fresh(gpre[RR]); fresh(mnpre[RR]); fresh(mxpre[RR]);
+        if (r_begin + RR < r_end) {                     // wave-uniform
+          float t[24];
+          resident(rrc, t);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            f2 x[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+              x[ch] = f2{t[3 * k + ch], t[3 * k + 12 + ch]};
+              if constexpr (!UNIT) x[ch] = norm01_2(x[ch], li);
+            }
+            gpre[RR][k] = reinhard_gray2(x);
+            mnpre[RR][k] = f2{fminf(x[0].x, fminf(x[1].x, x[2].x)), fminf(x[0].y, fminf(x[1].y, x[2].y))};
+            mxpre[RR][k] = f2{fmaxf(x[0].x, fmaxf(x[1].x, x[2].x)), fmaxf(x[0].y, fmaxf(x[1].y, x[2].y))};
+          }
+        }
+      });
+    }
+  };
+
   // ================================ barrier 0: bounds (tonemap.py:146) ================================
   MI_MSTAMP(2);
+  ahead(std::true_type{}, f2{0.f, 1.f});               // (behind the post: the record's store has been issued)
 #ifdef MI_STREAM_STAMPS
   barrier_fold<9, ew::FIN_BOUNDS>(m, ws, seq, 0, rows_bounds, tag, sh_fp, fl, lane, want_rgb, st_ + 9);
 #else
@@ -945,6 +1000,8 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
     const float v1[1] = {col_ok ? sl0 + sl1 : 0.f};
     const int op[1] = {2};
     block_reduce_post<1>(v1, op, red, &arrived, rows_stats, p.part_stride, blockIdx.x, wave, lane, tag);
+    // the bounds are known now: the LDS rows' ahead values again, normalised (they replace the speculative ones)
+    ahead(std::false_type{}, lo_inv);
     barrier_fold<1, ew::FIN_STATS>(m, ws, seq, 1, rows_stats, tag, sh_fp, fl, lane);
   }
   MI_MSTAMP(4);
@@ -983,7 +1040,8 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
   // single-rate and ~1260 double-rate instructions per wave), not its order.  On pixel pairs (PKC,
   // profiles/packed_f32_census.txt) the phase is 2379 instructions per wave: the same 440 transcendentals, 584 v_pk_mul /
   // add / fma_f32 in place of 1088 scalar ones, 288 conversions, 308 min / max, 333 s_nop.  Likewise the gray of the resident pixels
-  // computed ahead, in barrier 0's wait: two rows' worth fit the registers, nothing measurable.)
+  // computed ahead, in barrier 0's wait: two rows' worth fit the registers, nothing measurable - that was for rows whose values
+  // had to stay live while phase C turns 84 registers of x into 168 of q; the LDS rows' are dead before: `ahead` above.)
   auto tone_row = [&](auto unit_c, auto ca0_c, const float (&t)[24], float (&q)[24], auto pairs_c) {
     constexpr bool UNIT = decltype(unit_c)::value, CA0 = decltype(ca0_c)::value;
     if constexpr (PKC && CA0 && decltype(pairs_c)::value) {
@@ -1070,12 +1128,27 @@ __global__ __launch_bounds__(THREADS, 2) void frame_kernel(const MBatch mb) {
     if constexpr (RR >= NL) fresh(qr_[RR - NL]);
     prio_turn(RR, younger);
     if (r_begin + RR < r_end) {
-      float t[24];
-      resident(rrc, t);
       if (RR < NL && ca0) {                            // (wave-uniform)
-        if (unit) tone_bounds_row(std::true_type{}, t);
-        else tone_bounds_row(std::false_type{}, t);
+        if constexpr (AHEAD) {
+          // the scalar half of tone_bounds_row on what `ahead` left: no LDS read, no conversion, no normalisation here
+          if constexpr (RR < NL) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const f2 ad = reinhard_adapt_g2(gpre[RR][k], k2);
+              const f2 qmin = reinhard_map2(mnpre[RR][k], ad), qmax = reinhard_map2(mxpre[RR][k], ad);
+              vmin = fminf(vmin, fminf(qmin.x, qmin.y));
+              vmax = fmaxf(vmax, fmaxf(qmax.x, qmax.y));
+            }
+          }
+        } else {
+          float t[24];
+          resident(rrc, t);
+          if (unit) tone_bounds_row(std::true_type{}, t);
+          else tone_bounds_row(std::false_type{}, t);
+        }
       } else {
+        float t[24];
+        resident(rrc, t);
         float q[24];
         dispatch([&](auto unit_c, auto ca0_c) { tone_row(unit_c, ca0_c, t, q, std::true_type{}); });
 #pragma unroll
