@@ -395,6 +395,36 @@ int mi_isp_denoise_raw_batch(const void* const* src_host, void* const* cfa_host,
                              const mi_isp_denoise* denoise_host, void* stream);
 int mi_isp_denoise_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, const mi_isp_denoise* denoise_host,
                        void* stream);
+/* ---- highlight reconstruction ("Highlight reconstruction") ----------------------------------------------
+ * Clipped raw pixels rebuilt from their neighbours' white-balanced values, in f32 with one rounding per operation: the
+ * output is the contract's bit for bit.  x(p) is the value raw noise reduction filters (above); s(p) = (row & 1) * 2 +
+ * (col & 1); w[s] the balance gain (wb[0..2] = R, G, B; wb_dev, when not NULL, 3 f32 on the device that override wb and
+ * are read by the kernel) of the site's colour under `pattern`; b(q) = x(q) * w[s(q)]; t = clip.
+ *   MI_HIGHLIGHTS_REBUILD: p with x(p) >= t: for each of its two tap groups (R / B site: (r-1,c) (r,c-1) (r,c+1) (r+1,c),
+ *     then (r-1,c-1) (r-1,c+1) (r+1,c-1) (r+1,c+1); G site: (r,c-1) (r,c+1), then (r-1,c) (r+1,c)) with n >= 1 taps inside
+ *     the frame and not set in the defect mask, m = (the sum of their b in that order) / n; e = the larger m; when
+ *     e > b(p): y = max(x(p), e / w[s(p)]).  Every other pixel: y = x(p).
+ *   MI_HIGHLIGHTS_CLIP: y = min(x(p), (t * min(w)) / w[s(p)]).
+ *   cfa = cast_work(y * g(p))      (g the lens shading gain of shading_host, 1 for NULL)
+ * Source kinds, levels, grids, defect maps and outputs as mi_isp_denoise_raw(_batch).  out_f32_plain != 0: the output is
+ * the H x W f32 y itself, without gain or cast (shading_host must be NULL), for mi_isp_denoise_raw_batch to take as
+ * MI_RAW_32F.
+ *  - mi_isp_highlights_cfa: a normalised H x W CFA of dtype MI_F16 / MI_F32 (no levels, gain or mask), out of the same dtype.
+ * Host-side checks before any launch (error text names "highlights"): the mode, clip finite > 0, host gains finite > 0
+ * (device gains are the caller's), the pattern, shapes, dtypes, kinds, levels, grids, NULL pointers.  n == 0 and
+ * H * W == 0 are successful no-ops. */
+typedef struct { int32_t mode; float clip; float wb[3]; const float* wb_dev; } mi_isp_highlights;
+enum { MI_HIGHLIGHTS_REBUILD = 0, MI_HIGHLIGHTS_CLIP = 1 };
+int mi_isp_highlights_raw(const void* src_dev, void* cfa_dev, int H, int W, int src_kind, int ids_format, int work_dtype,
+                          int pattern, const mi_isp_levels* levels_host, const mi_isp_shading* shading_host,
+                          const mi_isp_defects* defects_host, const mi_isp_highlights* highlights_host, int out_f32_plain,
+                          void* stream);
+int mi_isp_highlights_raw_batch(const void* const* src_host, void* const* cfa_host, int n, int H, int W, int src_kind,
+                                int ids_format, int work_dtype, int pattern, const mi_isp_levels* levels_host,
+                                const mi_isp_shading* shading_host, const mi_isp_defects* const* defects_host,
+                                const mi_isp_highlights* highlights_host, int out_f32_plain, void* stream);
+int mi_isp_highlights_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, int pattern,
+                          const mi_isp_highlights* highlights_host, void* stream);
 /* ---- output sharpening ("Output sharpening") ----------------------------------------------------------
  * An unsharp mask on the luma of a u8 image, in integer arithmetic: the output is the contract's bit for bit.  All values
  * signed 32-bit, >> arithmetic, coordinates outside the image clamped to the edge; b = (1, 2, 1) for radius 1 and

@@ -52,6 +52,12 @@ class Denoise(ctypes.Structure):
                 ("radius", c_int32)]
 
 
+class Highlights(ctypes.Structure):
+    """mi_isp_highlights: the mode (0 rebuild, 1 clip), the clip level, the balance gains of R, G, B and, when not NULL,
+    3 f32 on the device that override them."""
+    _fields_ = [("mode", c_int32), ("clip", c_float), ("wb", c_float * 3), ("wb_dev", c_void_p)]
+
+
 class Sharpen(ctypes.Structure):
     """mi_isp_sharpen: the output sharpening filter's amount times 64 (0 .. 512), radius (1 or 2), coring threshold
     (0 .. 255) and halo clamp overshoot (0 .. 255, -1: none)."""
@@ -153,6 +159,12 @@ SIGNATURES = {
     "mi_isp_denoise_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
                                          POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Denoise), _P]),
     "mi_isp_denoise_cfa": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(Denoise), _P]),
+    "mi_isp_highlights_raw": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading),
+                                      POINTER(Defects), POINTER(Highlights), c_int, _P]),
+    "mi_isp_highlights_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Highlights), c_int,
+                                            _P]),
+    "mi_isp_highlights_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Highlights), _P]),
     "mi_isp_sharpen_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(Sharpen), _P]),
     "mi_isp_sharpen_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(Sharpen), _P]),
     "mi_isp_local_contrast_workspace_bytes": (c_size_t, [c_int, POINTER(LocalContrast)]),

@@ -22,6 +22,7 @@ import torch
 from . import _native, bayer, interpolate, packed, types
 from . import defects as _defects
 from . import denoise as _dn
+from . import highlights as _hl
 from . import lens as _lens
 from . import sharpen as _shp
 from . import chroma_denoise as _cdn
@@ -286,7 +287,8 @@ def camera_isp(name: str, dtype=types.f32):
                      sharpen=None,
                      local_contrast=None,
                      chroma_denoise=None,
-                     color_lut=None):
+                     color_lut=None,
+                     highlights=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -303,6 +305,7 @@ def camera_isp(name: str, dtype=types.f32):
             if awb is not None:
                 _wb.check_seed(white_balance)
             raw_denoise = _dn.check_raw_denoise(raw_denoise)
+            highlights = _hl.check_highlights(highlights)
             sharpen = _shp.check_sharpen(sharpen)
             local_contrast = _lc.check_local_contrast(local_contrast)
             chroma_denoise = _cdn.check_chroma_denoise(chroma_denoise)
@@ -352,6 +355,9 @@ def camera_isp(name: str, dtype=types.f32):
             # raw noise reduction (an extension): the RawDenoise of this sensor, or None (the loaders run exactly as
             # without it).  DESIGN.md 3, "Raw noise reduction".
             self._raw_denoise = raw_denoise
+            # highlight reconstruction (an extension): the Highlights the loaders apply to clipped raw pixels, or None (the
+            # loaders run exactly as without it).  DESIGN.md 3, "Highlight reconstruction".
+            self._highlights = highlights
             # output sharpening (an extension): the Sharpen applied to every u8 output of the tonemaps, or None (the
             # tonemaps run exactly as without it).  DESIGN.md 3, "Output sharpening".
             self._sharpen = sharpen
@@ -380,7 +386,8 @@ def camera_isp(name: str, dtype=types.f32):
                 color_correction: Optional[np.ndarray] = None,
                 transform: Optional[interpolate.ImageTransform] = None,
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
-                raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None):
+                raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
+                highlights=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -394,7 +401,8 @@ def camera_isp(name: str, dtype=types.f32):
             sharpen (the extension): None leaves it, False turns it off, a Sharpen replaces it.
             local_contrast (the extension): None leaves it, False turns it off, a LocalContrast replaces it.
             chroma_denoise (the extension): None leaves it, False turns it off, a ChromaDenoise replaces it.
-            color_lut (the extension): None leaves it, False turns it off, a ColorLut replaces it."""
+            color_lut (the extension): None leaves it, False turns it off, a ColorLut replaces it.
+            highlights (the extension): None leaves it, False turns it off, a Highlights replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -403,6 +411,7 @@ def camera_isp(name: str, dtype=types.f32):
             if awb is not None and (auto_white_balance is not None or white_balance is not None):
                 _wb.check_seed(self.white_balance if white_balance is None else white_balance)
             denoise = None if raw_denoise is None or raw_denoise is False else _dn.check_raw_denoise(raw_denoise)
+            new_hl = None if highlights is None or highlights is False else _hl.check_highlights(highlights)
             new_sharpen = None if sharpen is None or sharpen is False else _shp.check_sharpen(sharpen)
             new_lc = (None if local_contrast is None or local_contrast is False
                       else _lc.check_local_contrast(local_contrast))
@@ -453,6 +462,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._raw_denoise = None
             elif denoise is not None:
                 self._raw_denoise = denoise
+            if highlights is False:
+                self._highlights = None
+            elif new_hl is not None:
+                self._highlights = new_hl
             if sharpen is False:
                 self._sharpen = None
             elif new_sharpen is not None:
@@ -563,6 +576,46 @@ def camera_isp(name: str, dtype=types.f32):
             return cfas
 
         @property
+        def highlights(self) -> Optional[_hl.Highlights]:
+            """The Highlights the loaders apply, or None."""
+            return self._highlights
+
+        def _highlights_arg(self):
+            """The mi_isp_highlights of a load: the balance gains are the AWB gains on the device with AWB on, else
+            f32(white_balance) when the colour matrix carries it (correct_colors), else (1, 1, 1)."""
+            if self._awb is not None:
+                return self._highlights._arg(gains_dev=self._awb_gains)
+            if self.correct_colors:
+                return self._highlights._arg(_hl.check_white_balance(self.white_balance))
+            return self._highlights._arg()
+
+        def _reconstructed(self, srcs, h, w, kind, ids_format, lv, maps):
+            """The highlight reconstruction route: the reconstructed, gained, cast work-dtype CFAs of the raw frames srcs
+            (one shape, mi_isp_highlights_raw_batch source kind `kind`) in one launch, then the defect fix-up of each frame
+            with a map (maps: one DefectMap or None per frame).  With raw noise reduction on as well the launch writes the
+            plain f32 y, which the filter then takes as an f32 source with the same grid and maps.  DESIGN.md 3,
+            "Highlight reconstruction"."""
+            L = _native.lib()
+            stream = _native.stream_ptr(self.device)
+            plain = self._raw_denoise is not None
+            cfas = [torch.empty((h, w), dtype=torch_dtype, device=self.device) for _ in srcs]
+            ys = [torch.empty((h, w), dtype=torch.float32, device=self.device) for _ in srcs] if plain else cfas
+            args = [None if m is None else m._arg(self.device) for m in maps]       # (kept alive through the call)
+            p_maps = (ctypes.c_void_p * len(maps))(*[None if a is None else ctypes.addressof(a) for a in args])
+            sh = _native.shading_arg(self._applied_shading())
+            _native.check(L.mi_isp_highlights_raw_batch(
+                _native.ptr_array(srcs), _native.ptr_array(ys), len(srcs), h, w, kind, int(bool(ids_format)), dtype.code,
+                self._demosaic_pattern.value, lv, None if plain else sh, p_maps, self._highlights_arg(), int(plain), stream))
+            if plain:
+                _native.check(L.mi_isp_denoise_raw_batch(
+                    _native.ptr_array(ys), _native.ptr_array(cfas), len(srcs), h, w, _native.MI_RAW_32F, 0, dtype.code,
+                    None, sh, p_maps, self._raw_denoise._arg(), stream))
+            for cfa, a in zip(cfas, args):
+                if a is not None:
+                    _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, a, stream))
+            return cfas
+
+        @property
         def sharpen(self) -> Optional[_shp.Sharpen]:
             """The Sharpen the tonemaps apply to their u8 outputs, or None."""
             return self._sharpen
@@ -656,7 +709,9 @@ def camera_isp(name: str, dtype=types.f32):
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             src = image.to(self.device).contiguous()
-            if self._raw_denoise is not None:            # raw noise reduction: the filtered CFA, its defects fixed up
+            if self._highlights is not None:             # highlight reconstruction (then raw noise reduction, if on)
+                cfa = self._reconstructed([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
+            elif self._raw_denoise is not None:          # raw noise reduction: the filtered CFA, its defects fixed up
                 cfa = self._denoised([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
             else:
                 cfa = torch.empty((h, w), dtype=torch_dtype, device=self.device)
@@ -765,9 +820,11 @@ def camera_isp(name: str, dtype=types.f32):
             maps = self._per_frame("defects", defects, len(frames), (h, w), _defects.check_defects)
             lenses = self._per_frame("undistort", undistort, len(frames), (h, w), self._check_lens)
             srcs = [d.to(self.device).contiguous() for d in frames]
-            if self._raw_denoise is not None:            # raw noise reduction: one filter launch, then per frame
+            if self._highlights is not None or self._raw_denoise is not None:
+                # highlight reconstruction, raw noise reduction or both: one launch each, then per frame
                 kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
-                cfas = self._denoised(srcs, h, w, kind, ids_format, lv, maps)
+                route = self._reconstructed if self._highlights is not None else self._denoised
+                cfas = route(srcs, h, w, kind, ids_format, lv, maps)
                 rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
             elif lenses.count(None) < len(lenses):       # (some frame has a lens)
                 # lens distortion: the frames without a lens as the call without lenses, the others loaded at full
@@ -1057,6 +1114,7 @@ def camera_isp(name: str, dtype=types.f32):
             fused = (dtype is types.f16 and not ids_format and self.resize_width == 0 and self.scale is None
                      and self._applied_shading() is None      # (lens shading or AWB: the two calls below)
                      and self._raw_denoise is None            # (raw noise reduction: the two calls below)
+                     and self._highlights is None             # (highlight reconstruction: the two calls below)
                      and defects is None                      # (defective pixels: the two calls below)
                      and undistort is None                    # (lens distortion: the two calls below)
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8

@@ -15,6 +15,7 @@
 #include "isp_lens.h"
 #include "isp_awb.h"
 #include "isp_denoise.h"
+#include "isp_highlights.h"
 #include "isp_sharpen.h"
 #include "isp_chroma_denoise.h"
 #include "isp_color_lut.h"
@@ -760,6 +761,127 @@ extern "C" int mi_isp_denoise_cfa(const void* in, void* out, int H, int W, int d
   a.n_frames = 1;
   a.f[0] = {in, out, nullptr};
   return dn::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype, denoise->radius, (hipStream_t)stream);
+}
+
+// ---- highlight reconstruction (isp_highlights.h; DESIGN.md 3, "Highlight reconstruction") ----------------------------
+// the operator's settings and the demosaic pattern, checked on the host; fills the operator members of a
+static int highlights_settings(hl::Args& a, const mi_isp_highlights* h, int pattern, const char* who) {
+  static const int colours[4][4] = {{0, 1, 1, 2}, {1, 0, 2, 1}, {1, 2, 0, 1}, {2, 1, 1, 0}};   // RGGB GRBG GBRG BGGR
+  MI_REQUIRE(h, "%s: null highlights settings", who);
+  MI_REQUIRE(h->mode == MI_HIGHLIGHTS_REBUILD || h->mode == MI_HIGHLIGHTS_CLIP, "%s: highlights mode %d (0 rebuild, 1 clip)",
+             who, (int)h->mode);
+  MI_REQUIRE(std::isfinite(h->clip) && h->clip > 0.f, "%s: highlights clip %g must be finite and > 0", who,
+             (double)h->clip);
+  if (!h->wb_dev)
+    for (int k = 0; k < 3; ++k)
+      MI_REQUIRE(std::isfinite(h->wb[k]) && h->wb[k] > 0.f, "%s: highlights balance gain %d (%g) must be finite and > 0",
+                 who, k, (double)h->wb[k]);
+  MI_REQUIRE(pattern >= MI_RGGB && pattern <= MI_BGGR, "%s: bad highlights pattern %d", who, pattern);
+  a.mode = h->mode == MI_HIGHLIGHTS_CLIP ? hl::MODE_CLIP : hl::MODE_REBUILD;
+  a.t = h->clip;
+  for (int k = 0; k < 3; ++k) a.wb[k] = h->wb_dev ? 1.f : h->wb[k];
+  a.wb_dev = h->wb_dev;
+  for (int s = 0; s < 4; ++s) a.colour[s] = colours[pattern][s];
+  return 0;
+}
+
+static int highlights_geometry(int H, int W, int work_dtype, const char* who) {
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad highlights shape %dx%d", who, H, W);
+  MI_REQUIRE(H < (1 << 22) && W < (1 << 24), "%s: highlights frame %dx%d too large", who, H, W);
+  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: highlights work dtype must be f16 or f32", who);
+  return 0;
+}
+
+// n raw frames of one geometry: every frame's pointers (and defect mask) in the kernel arguments, 32 per launch
+static int highlights_raw_impl(const void* const* src, void* const* cfa, int n, int H, int W, int kind, int ids_format,
+                               int work_dtype, int pattern, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                               const mi_isp_defects* const* defects, const mi_isp_highlights* h, int plain, void* stream,
+                               const char* who) {
+  hl::Args a = {};
+  if (int rc = highlights_settings(a, h, pattern, who)) return rc;
+  if (int rc = highlights_geometry(H, W, work_dtype, who)) return rc;
+  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad highlights source kind %d", who, kind);
+  MI_REQUIRE(n >= 0, "%s: highlights with %d frames", who, n);
+  if (n == 0 || H == 0 || W == 0) return 0;
+  MI_REQUIRE(src && cfa, "%s: highlights: null frame list", who);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && cfa[i], "%s: highlights: frame %d has a null pointer", who, i);
+    MI_REQUIRE(src[i] != cfa[i], "%s: highlights: frame %d: the CFA must not overwrite its source", who, i);
+  }
+  MI_REQUIRE(!plain || !shading, "%s: highlights: the plain f32 output takes no shading grid", who);
+  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
+  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: highlights: packed frames must be even size, got %dx%d", who, H, W);
+  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: highlights: the IDS layout is a packed-12 layout", who);
+  a.H = H; a.W = W;
+  int src_kind;
+  if (packed) {
+    tile::Params p = {};
+    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
+    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
+    if (int rc = apply_levels(p, levels, bits, who)) return rc;
+    for (int s = 0; s < 4; ++s) {                     // the per-site decode of the shading path (apply_levels_shading)
+      a.black[s] = p.levels ? p.lv_black[s] : 0;
+      a.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
+    }
+    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
+  } else {
+    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
+      MI_REQUIRE(kind == MI_RAW_16U, "%s: highlights: levels apply to u16 codes only (source kind %d)", who, kind);
+      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
+      for (int s = 0; s < 4; ++s) a.k[s] = (float)(levels->white - levels->black[s]);
+      a.levels = 1;
+    }
+    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
+  }
+  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
+  a.mask_w = (W + 31) / 32;
+  for (int i = 0; i < n; ++i)
+    if (defects && defects[i]) {
+      MI_REQUIRE(defects[i]->n >= 0, "%s: highlights: negative defect count %d", who, (int)defects[i]->n);
+      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: highlights: frame %d: defects without a mask", who, i);
+    }
+  const int out = plain ? hl::OUT_PLAIN : (work_dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32);
+  for (int i0 = 0; i0 < n; i0 += hl::MAX_FRAMES) {
+    a.n_frames = n - i0 < hl::MAX_FRAMES ? n - i0 : hl::MAX_FRAMES;
+    for (int i = 0; i < a.n_frames; ++i) {
+      const mi_isp_defects* m = defects ? defects[i0 + i] : nullptr;
+      a.f[i] = {src[i0 + i], cfa[i0 + i], (m && m->n > 0) ? m->mask_dev : nullptr};
+    }
+    if (int rc = hl::launch(a, src_kind, out, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_highlights_raw(const void* src, void* cfa, int H, int W, int kind, int ids_format, int work_dtype,
+                                     int pattern, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                     const mi_isp_defects* defects, const mi_isp_highlights* highlights, int out_f32_plain,
+                                     void* stream) {
+  return highlights_raw_impl(&src, &cfa, 1, H, W, kind, ids_format, work_dtype, pattern, levels, shading, &defects,
+                             highlights, out_f32_plain, stream, "highlights_raw");
+}
+
+extern "C" int mi_isp_highlights_raw_batch(const void* const* src, void* const* cfa, int n, int H, int W, int kind,
+                                           int ids_format, int work_dtype, int pattern, const mi_isp_levels* levels,
+                                           const mi_isp_shading* shading, const mi_isp_defects* const* defects,
+                                           const mi_isp_highlights* highlights, int out_f32_plain, void* stream) {
+  return highlights_raw_impl(src, cfa, n, H, W, kind, ids_format, work_dtype, pattern, levels, shading, defects, highlights,
+                             out_f32_plain, stream, "highlights_raw_batch");
+}
+
+extern "C" int mi_isp_highlights_cfa(const void* in, void* out, int H, int W, int dtype, int pattern,
+                                     const mi_isp_highlights* highlights, void* stream) {
+  const char* who = "highlights_cfa";
+  hl::Args a = {};
+  if (int rc = highlights_settings(a, highlights, pattern, who)) return rc;
+  if (int rc = highlights_geometry(H, W, dtype, who)) return rc;
+  if (H == 0 || W == 0) return 0;
+  MI_REQUIRE(in && out, "%s: highlights: null pointer", who);
+  MI_REQUIRE(in != out, "%s: highlights: the output must not overwrite the input", who);
+  a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
+  a.n_frames = 1;
+  a.f[0] = {in, out, nullptr};
+  return hl::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
+                    (hipStream_t)stream);
 }
 
 // ---- output sharpening (isp_sharpen.h; DESIGN.md 3, "Output sharpening") ---------------------------------------------

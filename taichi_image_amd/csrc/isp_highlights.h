@@ -1,0 +1,55 @@
+// Highlight reconstruction (mi_isp_highlights; DESIGN.md 3, "Highlight reconstruction"): raw pixels at the sensor's clip
+// level are raised to the brightest white-balanced mean of their unclipped neighbour colours ("rebuild"), or every pixel is
+// limited to the balanced clip level ("clip"), on the f32 value x each loader computes before shading and the cast.  The
+// kernel writes the gained, cast CFA of the work dtype (or the plain f32 y for raw noise reduction to filter); the demosaic
+// and everything after it then run unchanged on that CFA.  One launch takes up to MAX_FRAMES frames of one geometry.
+#pragma once
+#include "isp_common.h"
+#include "isp_denoise.h"
+
+namespace hl {
+
+constexpr int MAX_FRAMES = 32;              // frames per launch (grid.z)
+constexpr int THREADS = 256;                // 4 waves
+constexpr int TILE_W = 64;                  // output tile: 64 columns (one per lane) ...
+constexpr int TILE_H = 64;                  // ... by 64 rows: wave w owns rows 16 w .. 16 w + 15
+constexpr int PX = TILE_H / 4;              // output pixels per lane
+constexpr int HALO_R = 1;                   // halo rows: the taps are one pixel away ...
+constexpr int HALO_C = 2;                   // ... and the decode takes pairs that start on even columns
+
+enum Mode { MODE_REBUILD = 0, MODE_CLIP = 1 };
+enum Out { OUT_F16 = 0, OUT_F32 = 1, OUT_PLAIN = 2 };   // work-dtype CFA with gain and cast, or the plain f32 y
+
+struct Frame {
+  const void* src;
+  void* dst;                                // H x W CFA: the work dtype, or f32 for OUT_PLAIN
+  const uint32_t* mask;                     // defect mask (H rows x mask_w words, bit c & 31 of word c >> 5), or NULL
+};
+
+struct Args {
+  int H, W;
+  // decode: the members of dn::Args (the sources are dn::Src)
+  int levels;
+  int black[4];
+  float k[4];
+  // lens shading / AWB gain (the members shade_gain reads); shading 0: gain 1
+  int shading;
+  const float* sh_gain;
+  int sh_sites, sh_gh, sh_gw;
+  float sh_sy, sh_sx;
+  int mask_w;
+  // the operator: t = f32(clip); the balance gains of R, G, B (wb_dev, when not NULL, overrides wb: 3 f32 on the device,
+  // read by the kernel); colour[s] of CFA site s = (row & 1) * 2 + (col & 1) under the demosaic pattern
+  int mode;
+  float t;
+  float wb[3];
+  const float* wb_dev;
+  int colour[4];
+  int n_frames;
+  Frame f[MAX_FRAMES];
+};
+
+// one launch (a.n_frames frames): src one of dn::Src, out one of Out
+int launch(const Args& a, int src, int out, hipStream_t stream);
+
+}  // namespace hl

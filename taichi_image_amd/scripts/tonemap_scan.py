@@ -199,6 +199,10 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--raw-denoise", dest="raw_denoise", type=float, nargs=2, metavar=("GAIN", "READ_NOISE"), default=None)
     tone.add_argument("--denoise-strength", dest="denoise_strength", type=float, default=1.0)
     tone.add_argument("--denoise-radius", dest="denoise_radius", type=int, default=1)
+    # highlight reconstruction (an extension): clipped raw pixels rebuilt from their neighbours ("rebuild") or every pixel
+    # limited to the balanced clip level ("clip"); T the clip level in units of the white level (default 0.98)
+    tone.add_argument("--highlights", dest="highlights", choices=("rebuild", "clip"), default=None)
+    tone.add_argument("--highlights-clip", dest="highlights_clip", type=float, metavar="T", default=None)
     # output sharpening (an extension): an unsharp mask on the luma of the u8 outputs; AMOUNT 0 .. 8, the blur radius (1 or
     # 2), the coring threshold in luma codes and the halo clamp (luma codes; default: none)
     tone.add_argument("--sharpen", dest="sharpen", type=float, metavar="AMOUNT", default=None)
@@ -234,6 +238,7 @@ def main(argv=None) -> int:
     from ..defects import DefectMap
     from ..lens import LensDistortion
     from ..denoise import RawDenoise
+    from ..highlights import Highlights
     from ..sharpen import Sharpen
     from ..local_contrast import LocalContrast
     from ..chroma_denoise import ChromaDenoise
@@ -254,6 +259,11 @@ def main(argv=None) -> int:
     if args.raw_denoise is not None:                                # (checked before any frame is read)
         denoise = RawDenoise(args.raw_denoise[0], args.raw_denoise[1], strength=args.denoise_strength,
                              radius=args.denoise_radius)
+    highlights = None
+    if args.highlights is not None:                                 # (also before any frame is read)
+        highlights = Highlights(args.highlights, 0.98 if args.highlights_clip is None else args.highlights_clip)
+    elif args.highlights_clip is not None:
+        raise ValueError("--highlights-clip needs --highlights {rebuild,clip}")
     sharpen = None
     if args.sharpen is not None:                                    # (also before any frame is read)
         sharpen = Sharpen(args.sharpen, radius=args.sharpen_radius, threshold=args.sharpen_threshold,
@@ -289,7 +299,8 @@ def main(argv=None) -> int:
                               resize_width=args.resize_width, correct_colors=args.correct_colors, device=device,
                               black_level=black, white_level=args.white_level, lens_shading=shading,
                               auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen,
-                              local_contrast=local_contrast, chroma_denoise=chroma_denoise, color_lut=color_lut)
+                              local_contrast=local_contrast, chroma_denoise=chroma_denoise, color_lut=color_lut,
+                              highlights=highlights)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
