@@ -425,6 +425,41 @@ int mi_isp_highlights_raw_batch(const void* const* src_host, void* const* cfa_ho
                                 const mi_isp_highlights* highlights_host, int out_f32_plain, void* stream);
 int mi_isp_highlights_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, int pattern,
                           const mi_isp_highlights* highlights_host, void* stream);
+/* ---- chromatic aberration ("Chromatic aberration") ------------------------------------------------------
+ * Lateral chromatic aberration corrected on the CFA: the red and the blue site planes are resampled radially about the
+ * optical centre, green is left alone; in f32 with one rounding per operation, left to right, never contracted: the
+ * output is the contract's bit for bit.  x(p) is the value raw noise reduction filters (above); s(p) = (row & 1) * 2 +
+ * (col & 1); the colour of a site follows `pattern`.  The library rounds once from double to f32: cy, cx, iR2 = 1 /
+ * norm_radius^2, and per channel d0 = k0 - 1, d1 = k1, d2 = k2 (red[] / blue[] = k0, k1, k2).
+ *   green site: y = x(p).
+ *   red / blue site p = (r, c) of parity (r0, c0), site plane P of nr x nc cells, d of its channel:
+ *     dy = f32(r) - cy;  dx = f32(c) - cx;  r2 = dx dx + dy dy;  q = r2 iR2;  e = d0 + q (d1 + q d2)
+ *     vs = f32(r) + dy e;  us = f32(c) + dx e;  a = (vs - f32(r0)) 0.5;  b = (us - f32(c0)) 0.5
+ *     i = floor(a), fr = a - f32(i);  j = floor(b), fc = b - f32(j)
+ *     i0 = clamp(i, 0, nr - 1), i1 = clamp(i + 1, 0, nr - 1), j0, j1 likewise;  mix(u, v, t) = u (1 - t) + v t
+ *     y = mix(mix(P[i0,j0], P[i0,j1], fc), mix(P[i1,j0], P[i1,j1], fc), fr)
+ *     when one of the four taps is set in the defect mask: w00 = (1 - fr)(1 - fc), w01 = (1 - fr) fc, w10 = fr (1 - fc),
+ *     w11 = fr fc; S, N the sums of w and of w x over the unmasked taps in the order 00, 01, 10, 11, each from its first
+ *     kept term; y = N / S when S > 0, else x(p)
+ *   cfa = cast_work(y * g(p))      (g the lens shading gain of shading_host at p, 1 for NULL)
+ * Source kinds, levels, grids, defect maps and outputs as mi_isp_highlights_raw(_batch), out_f32_plain included (the
+ * output is the H x W f32 y itself; shading_host must be NULL).
+ *  - mi_isp_chromatic_cfa: a normalised H x W CFA of dtype MI_F16 / MI_F32 (no levels, gain or mask), out of the same dtype.
+ * Host-side checks before any launch (error text names "chromatic"): every setting finite (in f32 too), norm_radius > 0,
+ * the shift limit - max |(k0 - 1) + q (k1 + q k2)| r <= 8 raw pixels for both channels, in double at 1025 equally spaced
+ * radii r from 0 to the distance of the farthest corner pixel from the centre, q = r^2 / norm_radius^2 - the pattern,
+ * shapes, dtypes, kinds, levels, grids, NULL pointers.  n == 0 and H * W == 0 are successful no-ops. */
+typedef struct { double cy, cx, norm_radius; double red[3], blue[3]; } mi_isp_chromatic;
+int mi_isp_chromatic_raw(const void* src_dev, void* cfa_dev, int H, int W, int src_kind, int ids_format, int work_dtype,
+                         int pattern, const mi_isp_levels* levels_host, const mi_isp_shading* shading_host,
+                         const mi_isp_defects* defects_host, const mi_isp_chromatic* chromatic_host, int out_f32_plain,
+                         void* stream);
+int mi_isp_chromatic_raw_batch(const void* const* src_host, void* const* cfa_host, int n, int H, int W, int src_kind,
+                               int ids_format, int work_dtype, int pattern, const mi_isp_levels* levels_host,
+                               const mi_isp_shading* shading_host, const mi_isp_defects* const* defects_host,
+                               const mi_isp_chromatic* chromatic_host, int out_f32_plain, void* stream);
+int mi_isp_chromatic_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, int pattern,
+                         const mi_isp_chromatic* chromatic_host, void* stream);
 /* ---- output sharpening ("Output sharpening") ----------------------------------------------------------
  * An unsharp mask on the luma of a u8 image, in integer arithmetic: the output is the contract's bit for bit.  All values
  * signed 32-bit, >> arithmetic, coordinates outside the image clamped to the edge; b = (1, 2, 1) for radius 1 and

@@ -58,6 +58,13 @@ class Highlights(ctypes.Structure):
     _fields_ = [("mode", c_int32), ("clip", c_float), ("wb", c_float * 3), ("wb_dev", c_void_p)]
 
 
+class Chromatic(ctypes.Structure):
+    """mi_isp_chromatic: the optical centre (cy, cx) and the normalisation radius in raw pixels, and (k0, k1, k2) of the
+    red and of the blue channel's scale."""
+    _fields_ = [("cy", c_double), ("cx", c_double), ("norm_radius", c_double), ("red", c_double * 3),
+                ("blue", c_double * 3)]
+
+
 class Sharpen(ctypes.Structure):
     """mi_isp_sharpen: the output sharpening filter's amount times 64 (0 .. 512), radius (1 or 2), coring threshold
     (0 .. 255) and halo clamp overshoot (0 .. 255, -1: none)."""
@@ -165,6 +172,12 @@ SIGNATURES = {
                                             POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Highlights), c_int,
                                             _P]),
     "mi_isp_highlights_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Highlights), _P]),
+    "mi_isp_chromatic_raw": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading),
+                                     POINTER(Defects), POINTER(Chromatic), c_int, _P]),
+    "mi_isp_chromatic_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Chromatic), c_int,
+                                           _P]),
+    "mi_isp_chromatic_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Chromatic), _P]),
     "mi_isp_sharpen_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(Sharpen), _P]),
     "mi_isp_sharpen_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(Sharpen), _P]),
     "mi_isp_local_contrast_workspace_bytes": (c_size_t, [c_int, POINTER(LocalContrast)]),

@@ -23,6 +23,7 @@ from . import _native, bayer, interpolate, packed, types
 from . import defects as _defects
 from . import denoise as _dn
 from . import highlights as _hl
+from . import chromatic as _ca
 from . import lens as _lens
 from . import sharpen as _shp
 from . import chroma_denoise as _cdn
@@ -288,7 +289,8 @@ def camera_isp(name: str, dtype=types.f32):
                      local_contrast=None,
                      chroma_denoise=None,
                      color_lut=None,
-                     highlights=None):
+                     highlights=None,
+                     chromatic_aberration=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -306,6 +308,7 @@ def camera_isp(name: str, dtype=types.f32):
                 _wb.check_seed(white_balance)
             raw_denoise = _dn.check_raw_denoise(raw_denoise)
             highlights = _hl.check_highlights(highlights)
+            chromatic_aberration = _ca.check_chromatic_aberration(chromatic_aberration)
             sharpen = _shp.check_sharpen(sharpen)
             local_contrast = _lc.check_local_contrast(local_contrast)
             chroma_denoise = _cdn.check_chroma_denoise(chroma_denoise)
@@ -358,6 +361,9 @@ def camera_isp(name: str, dtype=types.f32):
             # highlight reconstruction (an extension): the Highlights the loaders apply to clipped raw pixels, or None (the
             # loaders run exactly as without it).  DESIGN.md 3, "Highlight reconstruction".
             self._highlights = highlights
+            # chromatic aberration (an extension): the ChromaticAberration the loaders correct on the CFA, or None (the
+            # loaders run exactly as without it).  DESIGN.md 3, "Chromatic aberration".
+            self._chromatic = chromatic_aberration
             # output sharpening (an extension): the Sharpen applied to every u8 output of the tonemaps, or None (the
             # tonemaps run exactly as without it).  DESIGN.md 3, "Output sharpening".
             self._sharpen = sharpen
@@ -387,7 +393,7 @@ def camera_isp(name: str, dtype=types.f32):
                 transform: Optional[interpolate.ImageTransform] = None,
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
-                highlights=None):
+                highlights=None, chromatic_aberration=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -402,7 +408,8 @@ def camera_isp(name: str, dtype=types.f32):
             local_contrast (the extension): None leaves it, False turns it off, a LocalContrast replaces it.
             chroma_denoise (the extension): None leaves it, False turns it off, a ChromaDenoise replaces it.
             color_lut (the extension): None leaves it, False turns it off, a ColorLut replaces it.
-            highlights (the extension): None leaves it, False turns it off, a Highlights replaces it."""
+            highlights (the extension): None leaves it, False turns it off, a Highlights replaces it.
+            chromatic_aberration (the extension): None leaves it, False turns it off, a ChromaticAberration replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -412,6 +419,8 @@ def camera_isp(name: str, dtype=types.f32):
                 _wb.check_seed(self.white_balance if white_balance is None else white_balance)
             denoise = None if raw_denoise is None or raw_denoise is False else _dn.check_raw_denoise(raw_denoise)
             new_hl = None if highlights is None or highlights is False else _hl.check_highlights(highlights)
+            new_ca = (None if chromatic_aberration is None or chromatic_aberration is False
+                      else _ca.check_chromatic_aberration(chromatic_aberration))
             new_sharpen = None if sharpen is None or sharpen is False else _shp.check_sharpen(sharpen)
             new_lc = (None if local_contrast is None or local_contrast is False
                       else _lc.check_local_contrast(local_contrast))
@@ -466,6 +475,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._highlights = None
             elif new_hl is not None:
                 self._highlights = new_hl
+            if chromatic_aberration is False:
+                self._chromatic = None
+            elif new_ca is not None:
+                self._chromatic = new_ca
             if sharpen is False:
                 self._sharpen = None
             elif new_sharpen is not None:
@@ -616,6 +629,50 @@ def camera_isp(name: str, dtype=types.f32):
             return cfas
 
         @property
+        def chromatic_aberration(self) -> Optional[_ca.ChromaticAberration]:
+            """The ChromaticAberration the loaders correct, or None."""
+            return self._chromatic
+
+        def _corrected(self, srcs, h, w, kind, ids_format, lv, maps):
+            """The chromatic aberration route: the raw stages that are on, in the order highlight reconstruction,
+            chromatic aberration, raw noise reduction, one launch each for the raw frames srcs (one shape, source kind
+            `kind`), then the defect fix-up of each frame with a map (maps: one DefectMap or None per frame).  A stage
+            that is not the last writes the plain f32 y, which the next takes as an f32 source without levels; the last
+            applies the grid and the cast; all read the same masks.  DESIGN.md 3, "Chromatic aberration"."""
+            L = _native.lib()
+            stream = _native.stream_ptr(self.device)
+            n = len(srcs)
+            args = [None if m is None else m._arg(self.device) for m in maps]       # (kept alive through the call)
+            p_maps = (ctypes.c_void_p * len(maps))(*[None if a is None else ctypes.addressof(a) for a in args])
+            sh = _native.shading_arg(self._applied_shading())
+            pattern = self._demosaic_pattern.value
+            ids = int(bool(ids_format))
+            stages = []
+            if self._highlights is not None:
+                hl_arg = self._highlights_arg()
+                stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_highlights_raw_batch(
+                    i, o, n, h, w, k, f, dtype.code, pattern, l, s, p_maps, hl_arg, plain, stream))
+            ca_arg = self._chromatic._arg((h, w))
+            stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_chromatic_raw_batch(
+                i, o, n, h, w, k, f, dtype.code, pattern, l, s, p_maps, ca_arg, plain, stream))
+            if self._raw_denoise is not None:
+                dn_arg = self._raw_denoise._arg()
+                stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_denoise_raw_batch(
+                    i, o, n, h, w, k, f, dtype.code, l, s, p_maps, dn_arg, stream))
+            cfas = [torch.empty((h, w), dtype=torch_dtype, device=self.device) for _ in srcs]
+            cur, cur_kind, cur_ids, cur_lv = srcs, kind, ids, lv
+            for k, stage in enumerate(stages):
+                last = k == len(stages) - 1
+                outs = cfas if last else [torch.empty((h, w), dtype=torch.float32, device=self.device) for _ in srcs]
+                _native.check(stage(_native.ptr_array(cur), _native.ptr_array(outs), cur_kind, cur_ids, cur_lv,
+                                    sh if last else None, int(not last)))
+                cur, cur_kind, cur_ids, cur_lv = outs, _native.MI_RAW_32F, 0, None
+            for cfa, a in zip(cfas, args):
+                if a is not None:
+                    _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, a, stream))
+            return cfas
+
+        @property
         def sharpen(self) -> Optional[_shp.Sharpen]:
             """The Sharpen the tonemaps apply to their u8 outputs, or None."""
             return self._sharpen
@@ -706,10 +763,14 @@ def camera_isp(name: str, dtype=types.f32):
             if lv is not None and mode != 0:
                 raise ValueError("black_level / white_level apply to raw codes (load_16u, load_packed12/16); "
                                  "load_16f / load_32f take normalised values")
+            if self._chromatic is not None:
+                self._chromatic.check_shape((h, w))      # (before anything is uploaded or launched)
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             src = image.to(self.device).contiguous()
-            if self._highlights is not None:             # highlight reconstruction (then raw noise reduction, if on)
+            if self._chromatic is not None:              # chromatic aberration, among the raw stages that are on
+                cfa = self._corrected([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
+            elif self._highlights is not None:           # highlight reconstruction (then raw noise reduction, if on)
                 cfa = self._reconstructed([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
             elif self._raw_denoise is not None:          # raw noise reduction: the filtered CFA, its defects fixed up
                 cfa = self._denoised([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
@@ -819,11 +880,15 @@ def camera_isp(name: str, dtype=types.f32):
             lv = self._levels(bits)
             maps = self._per_frame("defects", defects, len(frames), (h, w), _defects.check_defects)
             lenses = self._per_frame("undistort", undistort, len(frames), (h, w), self._check_lens)
+            if self._chromatic is not None:
+                self._chromatic.check_shape((h, w))
             srcs = [d.to(self.device).contiguous() for d in frames]
-            if self._highlights is not None or self._raw_denoise is not None:
-                # highlight reconstruction, raw noise reduction or both: one launch each, then per frame
+            if self._chromatic is not None or self._highlights is not None or self._raw_denoise is not None:
+                # the raw stages - highlight reconstruction, chromatic aberration, raw noise reduction - that are on: one
+                # launch each, then per frame
                 kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
-                route = self._reconstructed if self._highlights is not None else self._denoised
+                route = (self._corrected if self._chromatic is not None
+                         else self._reconstructed if self._highlights is not None else self._denoised)
                 cfas = route(srcs, h, w, kind, ids_format, lv, maps)
                 rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
             elif lenses.count(None) < len(lenses):       # (some frame has a lens)
@@ -1115,6 +1180,7 @@ def camera_isp(name: str, dtype=types.f32):
                      and self._applied_shading() is None      # (lens shading or AWB: the two calls below)
                      and self._raw_denoise is None            # (raw noise reduction: the two calls below)
                      and self._highlights is None             # (highlight reconstruction: the two calls below)
+                     and self._chromatic is None              # (chromatic aberration: the two calls below)
                      and defects is None                      # (defective pixels: the two calls below)
                      and undistort is None                    # (lens distortion: the two calls below)
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8

@@ -16,6 +16,7 @@
 #include "isp_awb.h"
 #include "isp_denoise.h"
 #include "isp_highlights.h"
+#include "isp_chromatic.h"
 #include "isp_sharpen.h"
 #include "isp_chroma_denoise.h"
 #include "isp_color_lut.h"
@@ -881,6 +882,148 @@ extern "C" int mi_isp_highlights_cfa(const void* in, void* out, int H, int W, in
   a.n_frames = 1;
   a.f[0] = {in, out, nullptr};
   return hl::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
+                    (hipStream_t)stream);
+}
+
+// ---- chromatic aberration (isp_chromatic.h; DESIGN.md 3, "Chromatic aberration") --------------------------------------
+// the largest shift |(k0 - 1) + q (k1 + q k2)| r of a channel over an H x W frame, in double: at ca::SHIFT_SAMPLES equally
+// spaced radii from 0 to the distance of the farthest corner pixel from the centre, q = r^2 / norm_radius^2
+static double chromatic_max_shift(const mi_isp_chromatic* s, const double k[3], int H, int W) {
+  const double ry = std::fmax(std::fabs(s->cy), std::fabs((double)(H - 1) - s->cy));
+  const double rx = std::fmax(std::fabs(s->cx), std::fabs((double)(W - 1) - s->cx));
+  const double rmax = std::sqrt(ry * ry + rx * rx), n2 = s->norm_radius * s->norm_radius;
+  double worst = 0.0;
+  for (int i = 0; i < ca::SHIFT_SAMPLES; ++i) {
+    const double r = rmax * (double)i / (double)(ca::SHIFT_SAMPLES - 1);
+    const double q = r * r / n2;
+    const double shift = std::fabs((k[0] - 1.0) + q * (k[1] + q * k[2])) * r;
+    if (!(shift <= worst)) worst = shift;            // (a NaN is kept, and rejected by the caller)
+  }
+  return worst;
+}
+
+// the operator's settings, the demosaic pattern and the frame shape, checked on the host; fills the operator members of a
+static int chromatic_settings(ca::Args& a, const mi_isp_chromatic* s, int pattern, int H, int W, int dtype,
+                              const char* who) {
+  static const int colours[4][4] = {{0, 1, 1, 2}, {1, 0, 2, 1}, {1, 2, 0, 1}, {2, 1, 1, 0}};   // RGGB GRBG GBRG BGGR
+  MI_REQUIRE(s, "%s: null chromatic aberration settings", who);
+  MI_REQUIRE(std::isfinite(s->cy) && std::isfinite(s->cx), "%s: chromatic aberration centre (%g, %g) must be finite", who,
+             s->cy, s->cx);
+  MI_REQUIRE(std::isfinite(s->norm_radius) && s->norm_radius > 0.0, "%s: chromatic aberration norm_radius %g must be finite and > 0",
+             who, s->norm_radius);
+  for (int k = 0; k < 3; ++k)
+    MI_REQUIRE(std::isfinite(s->red[k]) && std::isfinite(s->blue[k]),
+               "%s: chromatic aberration coefficient %d (red %g, blue %g) must be finite", who, k, s->red[k], s->blue[k]);
+  MI_REQUIRE(pattern >= MI_RGGB && pattern <= MI_BGGR, "%s: bad chromatic aberration pattern %d", who, pattern);
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad chromatic aberration shape %dx%d", who, H, W);
+  MI_REQUIRE(H < (1 << 22) && W < (1 << 22), "%s: chromatic aberration frame %dx%d too large", who, H, W);
+  MI_REQUIRE(dtype == MI_F16 || dtype == MI_F32, "%s: chromatic aberration work dtype must be f16 or f32", who);
+  a.cy = (float)s->cy; a.cx = (float)s->cx;
+  a.iR2 = (float)(1.0 / (s->norm_radius * s->norm_radius));
+  a.dr[0] = (float)(s->red[0] - 1.0); a.dr[1] = (float)s->red[1]; a.dr[2] = (float)s->red[2];
+  a.db[0] = (float)(s->blue[0] - 1.0); a.db[1] = (float)s->blue[1]; a.db[2] = (float)s->blue[2];
+  bool finite = std::isfinite(a.cy) && std::isfinite(a.cx) && std::isfinite(a.iR2);
+  for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(a.dr[k]) && std::isfinite(a.db[k]);
+  MI_REQUIRE(finite, "%s: chromatic aberration settings overflow f32", who);
+  if (H > 0 && W > 0) {
+    const double mr = chromatic_max_shift(s, s->red, H, W), mb = chromatic_max_shift(s, s->blue, H, W);
+    MI_REQUIRE(mr <= ca::MAX_SHIFT && mb <= ca::MAX_SHIFT,
+               "%s: chromatic aberration shift (red %g, blue %g raw pixels on a %dx%d frame) exceeds %g", who, mr, mb, H, W,
+               ca::MAX_SHIFT);
+    a.halo = ca::halo_for(mr > mb ? mr : mb);
+  }
+  for (int k = 0; k < 4; ++k) a.colour[k] = colours[pattern][k];
+  return 0;
+}
+
+// n raw frames of one geometry: every frame's pointers (and defect mask) in the kernel arguments, 32 per launch
+static int chromatic_raw_impl(const void* const* src, void* const* cfa, int n, int H, int W, int kind, int ids_format,
+                              int work_dtype, int pattern, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                              const mi_isp_defects* const* defects, const mi_isp_chromatic* s, int plain, void* stream,
+                              const char* who) {
+  ca::Args a = {};
+  if (int rc = chromatic_settings(a, s, pattern, H, W, work_dtype, who)) return rc;
+  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad chromatic aberration source kind %d", who, kind);
+  MI_REQUIRE(n >= 0, "%s: chromatic aberration with %d frames", who, n);
+  if (n == 0 || H == 0 || W == 0) return 0;
+  MI_REQUIRE(src && cfa, "%s: chromatic aberration: null frame list", who);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && cfa[i], "%s: chromatic aberration: frame %d has a null pointer", who, i);
+    MI_REQUIRE(src[i] != cfa[i], "%s: chromatic aberration: frame %d: the CFA must not overwrite its source", who, i);
+  }
+  MI_REQUIRE(!plain || !shading, "%s: chromatic aberration: the plain f32 output takes no shading grid", who);
+  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
+  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: chromatic aberration: packed frames must be even size, got %dx%d",
+             who, H, W);
+  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: chromatic aberration: the IDS layout is a packed-12 layout", who);
+  a.H = H; a.W = W;
+  int src_kind;
+  if (packed) {
+    tile::Params p = {};
+    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
+    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
+    if (int rc = apply_levels(p, levels, bits, who)) return rc;
+    for (int k = 0; k < 4; ++k) {                     // the per-site decode of the shading path (apply_levels_shading)
+      a.black[k] = p.levels ? p.lv_black[k] : 0;
+      a.k[k] = p.levels ? p.lv_k[k] : p.k_decode;
+    }
+    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
+  } else {
+    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
+      MI_REQUIRE(kind == MI_RAW_16U, "%s: chromatic aberration: levels apply to u16 codes only (source kind %d)", who, kind);
+      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
+      for (int k = 0; k < 4; ++k) a.k[k] = (float)(levels->white - levels->black[k]);
+      a.levels = 1;
+    }
+    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
+  }
+  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
+  a.mask_w = (W + 31) / 32;
+  for (int i = 0; i < n; ++i)
+    if (defects && defects[i]) {
+      MI_REQUIRE(defects[i]->n >= 0, "%s: chromatic aberration: negative defect count %d", who, (int)defects[i]->n);
+      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: chromatic aberration: frame %d: defects without a mask", who, i);
+    }
+  const int out = plain ? hl::OUT_PLAIN : (work_dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32);
+  for (int i0 = 0; i0 < n; i0 += ca::MAX_FRAMES) {
+    a.n_frames = n - i0 < ca::MAX_FRAMES ? n - i0 : ca::MAX_FRAMES;
+    for (int i = 0; i < a.n_frames; ++i) {
+      const mi_isp_defects* m = defects ? defects[i0 + i] : nullptr;
+      a.f[i] = {src[i0 + i], cfa[i0 + i], (m && m->n > 0) ? m->mask_dev : nullptr};
+    }
+    if (int rc = ca::launch(a, src_kind, out, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_chromatic_raw(const void* src, void* cfa, int H, int W, int kind, int ids_format, int work_dtype,
+                                    int pattern, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                    const mi_isp_defects* defects, const mi_isp_chromatic* chromatic, int out_f32_plain,
+                                    void* stream) {
+  return chromatic_raw_impl(&src, &cfa, 1, H, W, kind, ids_format, work_dtype, pattern, levels, shading, &defects,
+                            chromatic, out_f32_plain, stream, "chromatic_raw");
+}
+
+extern "C" int mi_isp_chromatic_raw_batch(const void* const* src, void* const* cfa, int n, int H, int W, int kind,
+                                          int ids_format, int work_dtype, int pattern, const mi_isp_levels* levels,
+                                          const mi_isp_shading* shading, const mi_isp_defects* const* defects,
+                                          const mi_isp_chromatic* chromatic, int out_f32_plain, void* stream) {
+  return chromatic_raw_impl(src, cfa, n, H, W, kind, ids_format, work_dtype, pattern, levels, shading, defects, chromatic,
+                            out_f32_plain, stream, "chromatic_raw_batch");
+}
+
+extern "C" int mi_isp_chromatic_cfa(const void* in, void* out, int H, int W, int dtype, int pattern,
+                                    const mi_isp_chromatic* chromatic, void* stream) {
+  const char* who = "chromatic_cfa";
+  ca::Args a = {};
+  if (int rc = chromatic_settings(a, chromatic, pattern, H, W, dtype, who)) return rc;
+  if (H == 0 || W == 0) return 0;
+  MI_REQUIRE(in && out, "%s: chromatic aberration: null pointer", who);
+  MI_REQUIRE(in != out, "%s: chromatic aberration: the output must not overwrite the input", who);
+  a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
+  a.n_frames = 1;
+  a.f[0] = {in, out, nullptr};
+  return ca::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
                     (hipStream_t)stream);
 }
 

@@ -203,6 +203,12 @@ def build_parser() -> argparse.ArgumentParser:
     # limited to the balanced clip level ("clip"); T the clip level in units of the white level (default 0.98)
     tone.add_argument("--highlights", dest="highlights", choices=("rebuild", "clip"), default=None)
     tone.add_argument("--highlights-clip", dest="highlights_clip", type=float, metavar="T", default=None)
+    # chromatic aberration (an extension): (k0, k1, k2) of the red and of the blue channel's radial scale, the optical
+    # centre (default: the middle of the frame) and the normalisation radius (default: the half diagonal), in raw pixels
+    tone.add_argument("--chromatic-aberration", dest="chromatic_aberration", type=float, nargs=6,
+                      metavar=("R0", "R1", "R2", "B0", "B1", "B2"), default=None)
+    tone.add_argument("--chromatic-center", dest="chromatic_center", type=float, nargs=2, metavar=("CY", "CX"), default=None)
+    tone.add_argument("--chromatic-norm-radius", dest="chromatic_norm_radius", type=float, metavar="R", default=None)
     # output sharpening (an extension): an unsharp mask on the luma of the u8 outputs; AMOUNT 0 .. 8, the blur radius (1 or
     # 2), the coring threshold in luma codes and the halo clamp (luma codes; default: none)
     tone.add_argument("--sharpen", dest="sharpen", type=float, metavar="AMOUNT", default=None)
@@ -239,6 +245,7 @@ def main(argv=None) -> int:
     from ..lens import LensDistortion
     from ..denoise import RawDenoise
     from ..highlights import Highlights
+    from ..chromatic import ChromaticAberration
     from ..sharpen import Sharpen
     from ..local_contrast import LocalContrast
     from ..chroma_denoise import ChromaDenoise
@@ -264,6 +271,13 @@ def main(argv=None) -> int:
         highlights = Highlights(args.highlights, 0.98 if args.highlights_clip is None else args.highlights_clip)
     elif args.highlights_clip is not None:
         raise ValueError("--highlights-clip needs --highlights {rebuild,clip}")
+    chromatic = None
+    if args.chromatic_aberration is not None:                       # (also before any frame is read)
+        k = args.chromatic_aberration
+        chromatic = ChromaticAberration(tuple(k[:3]), tuple(k[3:]), center=args.chromatic_center,
+                                        norm_radius=args.chromatic_norm_radius)
+    elif args.chromatic_center is not None or args.chromatic_norm_radius is not None:
+        raise ValueError("--chromatic-center / --chromatic-norm-radius need --chromatic-aberration R0 R1 R2 B0 B1 B2")
     sharpen = None
     if args.sharpen is not None:                                    # (also before any frame is read)
         sharpen = Sharpen(args.sharpen, radius=args.sharpen_radius, threshold=args.sharpen_threshold,
@@ -300,7 +314,7 @@ def main(argv=None) -> int:
                               black_level=black, white_level=args.white_level, lens_shading=shading,
                               auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen,
                               local_contrast=local_contrast, chroma_denoise=chroma_denoise, color_lut=color_lut,
-                              highlights=highlights)
+                              highlights=highlights, chromatic_aberration=chromatic)
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
