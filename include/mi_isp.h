@@ -572,6 +572,25 @@ int mi_isp_pipeline12_reinhard(const uint8_t* packed_dev, void* out_dev, void* w
                                int ids_format, int pattern, const float* ccm9_host,
                                int work_dtype, int out_dtype, float gamma, float intensity,
                                float light_adapt, float color_adapt, void* ws_dev, void* stream);
+/* Which chain of kernels mi_isp_pipeline12_reinhard[_batch] runs for these arguments, without launching anything: the
+ * library's own decision (the function that answers here is the one the launches go through), from the pointers'
+ * VALUES, the shape, the layout and the dtypes alone.  Nothing is dereferenced and no device is touched: made-up
+ * addresses are fine, and no GPU is needed.
+ *   MI_ISP_ROUTE_STREAM          the streaming kernels, four passes over the packed frame: the standard layout, W % 8 == 0,
+ *                                H >= 4, packed rows 4-byte aligned, the output 16-byte (u8: 8-byte) aligned
+ *   MI_ISP_ROUTE_CACHED_STREAM   such a frame whose OUTPUT is not aligned, with an aligned work-dtype image (work_image_dev,
+ *                                or the output when it has the work dtype): the streaming kernel stores the image and
+ *                                reduces its bounds, three elementwise passes follow
+ *   MI_ISP_ROUTE_CACHED_TILE     any other frame with W % 8 == 0 and an aligned work-dtype image: the tile kernel as the
+ *                                first pass (hot = 1: its specialisation for aligned packed rows; 0: the generic kernel)
+ *   MI_ISP_ROUTE_RECOMPUTE       everything else (W % 8 != 0, no aligned work-dtype image): four tile passes over the
+ *                                packed frame and three finalize launches
+ * rows_per_wave, bands_x: the streaming kernels' geometry (0 on the tile routes); n_blocks: the blocks (= partial results)
+ * of the route's first pass.  Non-zero with a message for arguments mi_isp_pipeline12_reinhard refuses. */
+enum { MI_ISP_ROUTE_STREAM = 0, MI_ISP_ROUTE_CACHED_STREAM = 1, MI_ISP_ROUTE_CACHED_TILE = 2, MI_ISP_ROUTE_RECOMPUTE = 3 };
+typedef struct { int32_t route, hot, rows_per_wave, bands_x, n_blocks; } mi_isp_route;
+int mi_isp_pipeline12_route(const uint8_t* packed_dev, void* out_dev, void* work_image_dev, int H, int W, int ids_format,
+                            int work_dtype, int out_dtype, mi_isp_route* route_host);
 /* One camera group from packed bytes to u8 outputs in one call on the caller's stream (ISP.load_packed12/16 per
  * camera, camera_isp.py:333-347; the rolling metering over the group, :376-385 -> :142-175; ISP.tonemap_reinhard or
  * tonemap_linear, :394-413, with the orientation transform folded into the store).

@@ -88,6 +88,16 @@ class ColorLut(ctypes.Structure):
     _fields_ = [("n_points", c_int32), ("strength_q6", c_int32)]
 
 
+class Route(ctypes.Structure):
+    """mi_isp_route: the chain mi_isp_pipeline12_reinhard takes (ROUTES), the tile first pass's HOT specialisation, the
+    streaming kernels' rows per wave and column bands (0 on the tile routes), the first pass's blocks."""
+    _fields_ = [("route", c_int32), ("hot", c_int32), ("rows_per_wave", c_int32), ("bands_x", c_int32), ("n_blocks", c_int32)]
+
+
+# MI_ISP_ROUTE_*
+ROUTES = ("stream", "cached_stream", "cached_tile", "recompute")
+
+
 # every symbol include/mi_isp.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SIGNATURES = {
@@ -195,6 +205,7 @@ SIGNATURES = {
     "mi_isp_load_packed_scale_supported": (c_int, [c_float]),
     "mi_isp_pipeline12_reinhard": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int,
                                            c_float, c_float, c_float, c_float, _P, _P]),
+    "mi_isp_pipeline12_route": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(Route)]),
     "mi_isp_pipeline12_reinhard_batch": (c_int, [POINTER(_P), POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int,
                                                  POINTER(c_float), c_int, c_int, c_float, c_float, c_float, c_float,
                                                  _P, POINTER(_P), c_int]),
@@ -323,6 +334,15 @@ def ccm_arg(correct_colors):
     m = np.asarray(correct_colors, dtype=np.float64).reshape(-1)
     assert m.size == 9, "colour correction must be a 3x3 matrix"
     return (c_float * 9)(*[float(v) for v in m])
+
+
+def pipeline12_route(packed_ptr, out_ptr, work_image_ptr, H, W, ids_format, work_code, out_code):
+    """mi_isp_pipeline12_route: (route name of ROUTES, the Route) of these arguments of mi_isp_pipeline12_reinhard.
+    Addresses as integers (None / 0: no work image); nothing is launched or dereferenced."""
+    r = Route()
+    check(lib().mi_isp_pipeline12_route(packed_ptr, out_ptr, work_image_ptr or None, int(H), int(W), int(bool(ids_format)),
+                                        int(work_code), int(out_code), ctypes.byref(r)))
+    return ROUTES[r.route], r
 
 
 def levels_arg(black, white):

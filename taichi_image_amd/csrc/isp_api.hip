@@ -1340,7 +1340,8 @@ static int pipeline_frame(tile::Params p, int pattern, int work_dtype, float int
 // buffer itself when the output has the work dtype, a caller-provided buffer otherwise; `out` / `out_dtype`:
 // the final destination of pass 3.
 static int pipeline_frame_cached(tile::Params p, int pattern, int work_dtype, float gamma, float intensity,
-                                 float* ws, int which, hipStream_t s, void* image, void* out, int out_dtype) {
+                                 float* ws, int which, hipStream_t s, void* image, void* out, int out_dtype,
+                                 bool stream0) {
   float* fp = ws;
   float* partials = ws + FP_COUNT;
   const int cap = mi_partial_cap(p.H, p.W);
@@ -1350,7 +1351,6 @@ static int pipeline_frame_cached(tile::Params p, int pattern, int work_dtype, fl
   const PassTimer tm = which < 0 ? pass_timer(s) : PassTimer{0, false, s};
   if (int rc = tm.begin(0)) return rc;
   int n_bounds = tile::num_tiles(p.H, p.W);
-  const bool stream0 = use_stream(p, work_dtype, image, work_dtype);
   if (stream0) {
     strm::SArgs a = {};
     a.t = p;
@@ -1549,8 +1549,20 @@ static bool no_cached_pipeline() {
 #endif
 }
 
-static bool use_cached(const tile::Params& p, int work_dtype, int out_dtype) {
-  return !no_cached_pipeline() && work_dtype == out_dtype && p.vec_store;
+// Which chain of kernels a frame of the multi-pass chain takes (mi_isp.h: MI_ISP_ROUTE_*).  The one place that decides:
+// pipeline12_frame and mi_isp_pipeline12_pass launch what it says, mi_isp_pipeline12_route reports it.  Host arithmetic
+// on the arguments' values only.  p: pipeline_params + packed_params, dst = out, vec_store = vec_store_ok(out).
+// *image: where the cached routes keep the work-dtype image (the output itself when it has the work dtype).
+static int pipeline12_route(const tile::Params& p, int work_dtype, void* out, int out_dtype, void* work_image,
+                            void** image) {
+  *image = nullptr;
+  if (use_stream(p, work_dtype, out, out_dtype) && p.vec_store && !force_cached()) return MI_ISP_ROUTE_STREAM;
+  void* im = work_dtype == out_dtype ? out : work_image;
+  if (!no_cached_pipeline() && im && vec_store_ok(im, p.W, work_dtype)) {
+    *image = im;
+    return use_stream(p, work_dtype, im, work_dtype) ? MI_ISP_ROUTE_CACHED_STREAM : MI_ISP_ROUTE_CACHED_TILE;
+  }
+  return MI_ISP_ROUTE_RECOMPUTE;
 }
 
 static int pipeline_params(tile::Params& p, int H, int W, int ids_format, int pattern, const float* ccm9,
@@ -1590,14 +1602,15 @@ static int pipeline12_frame(const uint8_t* packed, void* out, void* work_image, 
     void* dsts[1] = {out};
     return mega_launch_frames(p, ma, pattern, intensity, srcs, dsts, ws, 0, 1, s);
   }
-  if (use_stream(p, work_dtype, out, out_dtype) && p.vec_store && !force_cached())
-    return pipeline_frame_stream(p, pattern, work_dtype, intensity, ws, -1, s);
-  void* image = work_dtype == out_dtype ? out : work_image;
-  if (!no_cached_pipeline() && image && vec_store_ok(image, W, work_dtype))
-    return pipeline_frame_cached(p, pattern, work_dtype, gamma, intensity, ws, -1, s, image, out, out_dtype);
-  p.dst = out;
-  p.vec_store = vec_store_ok(out, W, out_dtype);
-  return pipeline_frame(p, pattern, work_dtype, intensity, ws, s);
+  void* image = nullptr;
+  switch (pipeline12_route(p, work_dtype, out, out_dtype, work_image, &image)) {
+    case MI_ISP_ROUTE_STREAM: return pipeline_frame_stream(p, pattern, work_dtype, intensity, ws, -1, s);
+    case MI_ISP_ROUTE_CACHED_STREAM:
+      return pipeline_frame_cached(p, pattern, work_dtype, gamma, intensity, ws, -1, s, image, out, out_dtype, true);
+    case MI_ISP_ROUTE_CACHED_TILE:
+      return pipeline_frame_cached(p, pattern, work_dtype, gamma, intensity, ws, -1, s, image, out, out_dtype, false);
+    default: return pipeline_frame(p, pattern, work_dtype, intensity, ws, s);
+  }
 }
 
 extern "C" int mi_isp_pipeline12_reinhard(const uint8_t* packed, void* out, void* work_image, int H, int W,
@@ -1608,6 +1621,32 @@ extern "C" int mi_isp_pipeline12_reinhard(const uint8_t* packed, void* out, void
   return pipeline12_frame(packed, out, work_image, H, W, ids_format, pattern, ccm9, work_dtype, out_dtype, gamma,
                           intensity, light_adapt, color_adapt, static_cast<float*>(ws), (hipStream_t)stream,
                           "pipeline12_reinhard");
+}
+
+extern "C" int mi_isp_pipeline12_route(const uint8_t* packed, void* out, void* work_image, int H, int W, int ids_format,
+                                       int work_dtype, int out_dtype, mi_isp_route* route) {
+  MI_REQUIRE(route, "pipeline12_route: null result");
+  MI_REQUIRE(out, "pipeline12_route: null pointer");
+  *route = mi_isp_route{};
+  tile::Params p = {};
+  if (int rc = pipeline_params(p, H, W, ids_format, MI_RGGB, nullptr, work_dtype, out_dtype, 1.f, 1.f, 0.f)) return rc;
+  if (int rc = packed_params(p, packed, H, W, 12, ids_format, work_dtype, "pipeline12_route")) return rc;
+  p.dst = out;
+  p.vec_store = vec_store_ok(out, W, out_dtype);
+  void* image = nullptr;
+  route->route = pipeline12_route(p, work_dtype, out, out_dtype, work_image, &image);
+  if (route->route == MI_ISP_ROUTE_CACHED_TILE) {             // the Params of pipeline_frame_cached's first pass
+    p.dst = image; p.vec_store = vec_store_ok(image, W, work_dtype); p.out_dtype = work_dtype; p.out_scale = 1.f;
+    route->hot = tile::hot_spec(p, work_dtype, tile::EPI_STORE_MINMAX);
+  }
+  if (route->route == MI_ISP_ROUTE_STREAM || route->route == MI_ISP_ROUTE_CACHED_STREAM) {
+    strm::SArgs a = {};
+    strm::geometry(H, W, a);
+    route->rows_per_wave = a.rows_per_wave; route->bands_x = a.bands_x; route->n_blocks = a.n_blocks;
+  } else {
+    route->n_blocks = tile::num_tiles(H, W);
+  }
+  return 0;
 }
 
 extern "C" int mi_isp_pipeline12_reinhard_whole_frame(const uint8_t* packed, void* out, int H, int W, int ids_format,
@@ -2067,10 +2106,15 @@ extern "C" int mi_isp_pipeline12_pass(const uint8_t* packed, void* out, int H, i
   p.dst = out;
   p.vec_store = vec_store_ok(out, W, out_dtype);
   float* fp = static_cast<float*>(ws);
-  if (use_stream(p, work_dtype, out, out_dtype) && p.vec_store && debug_skip == 0 && !force_cached())
+  // (no work image here: an output of another dtype than the work dtype recomputes; debug_skip times the tile kernel)
+  void* image = nullptr;
+  const int route = debug_skip != 0 ? (int)MI_ISP_ROUTE_RECOMPUTE
+                                    : pipeline12_route(p, work_dtype, out, out_dtype, nullptr, &image);
+  if (route == MI_ISP_ROUTE_STREAM)
     return pipeline_frame_stream(p, pattern, work_dtype, 1.0f, fp, pass, (hipStream_t)stream);
-  if (use_cached(p, work_dtype, out_dtype) && debug_skip == 0)
-    return pipeline_frame_cached(p, pattern, work_dtype, gamma, 1.0f, fp, pass, (hipStream_t)stream, out, out, out_dtype);
+  if (route == MI_ISP_ROUTE_CACHED_STREAM || route == MI_ISP_ROUTE_CACHED_TILE)
+    return pipeline_frame_cached(p, pattern, work_dtype, gamma, 1.0f, fp, pass, (hipStream_t)stream, image, out, out_dtype,
+                                 route == MI_ISP_ROUTE_CACHED_STREAM);
   p.fp = fp; p.partials = fp + FP_COUNT; p.part_stride = mi_partial_cap(H, W);
   p.debug_skip = debug_skip & 63;
   static const int epi[4] = {tile::EPI_MINMAX, tile::EPI_STATS, tile::EPI_RH_MINMAX, tile::EPI_RH_STORE};

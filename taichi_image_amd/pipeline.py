@@ -2,10 +2,21 @@
 
     decode12(packed, dtype=work, scaled=True) -> bayer_to_rgb -> tonemap_reinhard(dtype=out)
 
-as four data passes (csrc/isp_api.hip: pipeline_frame_cached when the output has the work dtype - one
-tile pass that writes the demosaiced image into the output buffer, three elementwise passes on it -
-and pipeline_frame, four tile passes over the packed frame, otherwise).  Results are
-identical to calling packed.decode12 / bayer.bayer_to_rgb / tonemap.tonemap_reinhard in turn.
+as ONE launch of the whole-frame kernel (csrc/isp_mega.h) for the frames it takes, and otherwise as the multi-pass
+chain: four data passes, by one of four routes (csrc/isp_api.hip: pipeline12_route decides, _native.pipeline12_route
+reports the decision for given buffers without launching anything):
+
+  stream          the standard 12-bit layout with W % 8 == 0, H >= 4, packed rows 4-byte aligned and an aligned output:
+                  four passes of the streaming kernels (csrc/isp_stream.h) over the packed frame, nothing in between
+  cached_stream   such a frame whose output is not aligned, with an aligned work-dtype image (the output itself when it
+                  has the work dtype, else scratch this module allocates): the streaming kernel stores the demosaiced
+                  image, three elementwise passes follow (pipeline_frame_cached)
+  cached_tile     any other frame with W % 8 == 0 (IDS layout, H == 2, a packed view off its 4-byte boundary) and such
+                  an image: the tile kernel (csrc/isp_tile.h) as the first pass, then the same three passes
+  recompute       everything else - W % 8 != 0, no aligned work-dtype image: four tile passes over the packed frame and
+                  three finalize launches (pipeline_frame)
+
+Results are identical to calling packed.decode12 / bayer.bayer_to_rgb / tonemap.tonemap_reinhard in turn.
 """
 from __future__ import annotations
 

@@ -36,6 +36,18 @@ def test_host_only_entry_points():
     assert np.array_equal(bayer.bayer_weights(), O.BAYER_KERNELS)
     assert L.mi_isp_workspace_bytes(3072, 4096) >= 64 * 4 + 8 * 3072 * 4
     assert L.mi_isp_workspace_bytes(0, 0) == 0
+    # which chain mi_isp_pipeline12_reinhard takes: from the pointers' values alone (made-up addresses, no device)
+    a = 0x7F0000000000
+    name, r = _native.pipeline12_route(a, a + (1 << 30), None, 3072, 4096, 0, _native.MI_F16, _native.MI_F16)
+    assert (name, r.hot, r.rows_per_wave, r.bands_x, r.n_blocks) == ("stream", 0, 12, 8, 512)
+    name, r = _native.pipeline12_route(a, a + (1 << 30) + 4, a + (2 << 30), 3072, 4096, 0, _native.MI_F16, _native.MI_U8)
+    assert (name, r.rows_per_wave) == ("cached_stream", 12)
+    name, r = _native.pipeline12_route(a, a + (1 << 30), a + (2 << 30), 70, 264, 1, _native.MI_F32, _native.MI_U16)
+    assert (name, r.hot, r.rows_per_wave, r.n_blocks) == ("cached_tile", 1, 0, 9)
+    assert _native.pipeline12_route(a + 1, a + (1 << 30), a + (2 << 30), 70, 264, 0, _native.MI_F32, _native.MI_U16)[1].hot == 0
+    assert _native.pipeline12_route(a, a + (1 << 30), None, 70, 264, 1, _native.MI_F32, _native.MI_U16)[0] == "recompute"
+    assert _native.pipeline12_route(a, a + (1 << 30), a + (2 << 30), 70, 266, 0, _native.MI_F16, _native.MI_F16)[0] == "recompute"
+    assert L.mi_isp_pipeline12_route(None, a, None, 4, 16, 0, 2, 2, _native.Route()) != 0 and b"null" in L.mi_isp_last_error()
 
 
 def test_argument_validation_reports_errors():

@@ -288,7 +288,8 @@ def test_degenerate_pipeline(ti, dev, kind, shape):
                 got = _host(pipeline12_reinhard(torch.from_numpy(packed).to(dev), dtype=getattr(ti.types, out),
                                                 whole_frame=wf, check=True if wf else None, **kw))
                 assert_close(got, want, f"{kind} {out} whole_frame={wf} {kw}")
-        # f32 work dtype: the tile passes over the packed frame
+        # f32 work dtype: still the stream route where the f16 call took it (strm::supported takes f32; the tile routes
+        # have tests/test_gpu_multi_pass_matrix.py)
         got = _host(pipeline12_reinhard(torch.from_numpy(packed).to(dev), work_dtype=ti.types.f32, dtype=ti.types.f32,
                                         whole_frame=False, **kw))
         assert_close(got, c_oracle.pipeline12_reinhard(packed, work="f32", out="f32", **kw), f"{kind} f32 {kw}")
@@ -436,7 +437,7 @@ def test_single_pixel_decides(ti, dev, monkeypatch, needle, shape):
             assert_close(got, want, f"{name} {(y, x)} whole_frame={wf}")
         got = _host(pipeline12_reinhard(torch.from_numpy(packed).to(dev), work_dtype=ti.types.f32, dtype=ti.types.f32,
                                         whole_frame=False))
-        assert_close(got, c_oracle.pipeline12_reinhard(packed, work="f32", out="f32"), f"{name} {(y, x)} f32 tile passes")
+        assert_close(got, c_oracle.pipeline12_reinhard(packed, work="f32", out="f32"), f"{name} {(y, x)} f32 multi-pass chain")    # (the stream route: strm::supported takes f32)
         # the ISP: metering on the subsample (a grid needle decides its bounds) and max_out over the whole image
         refs = [O.isp_load_packed12(packed, "f16")]
         m = c_oracle.IspState(0.3).update_metering(refs)

@@ -289,18 +289,40 @@ def test_pipeline12_reinhard(ti, rng, dev, p, ids, work, dout, shape):
 def test_pipeline12_without_work_image_recomputes(ti, rng, dev):
     """The C entry point without scratch for the work-dtype image (work_image_dev == NULL) and an output dtype
     other than the work dtype: every pass re-derives the demosaic from the packed frame (the minimal-traffic
-    variant) - same results as the oracle."""
+    variant) - same results as the oracle.  This frame (standard layout, W % 8 == 0, aligned buffers) takes the
+    stream route (mi_isp_pipeline12_route), whose four passes all recompute; the tile recompute chain has the
+    sibling below and tests/test_gpu_multi_pass_matrix.py."""
     from taichi_image_amd import _native
     H, W = 70, 200
     packed = natural_packed12(rng, H, W)
     pk = torch.from_numpy(packed).to(dev)
     out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
     ws = _native.workspace(H, W, dev)
+    assert _native.pipeline12_route(pk.data_ptr(), out.data_ptr(), None, H, W, 0, ti.types.f16.code,
+                                    ti.types.u8.code)[0] == "stream"
     _native.check(_native.lib().mi_isp_pipeline12_reinhard(
         pk.data_ptr(), out.data_ptr(), None, H, W, 0, 0, None, ti.types.f16.code, ti.types.u8.code, 0.8, 1.0, 1.0, 0.0,
         ws.data_ptr(), _native.stream_ptr(dev)))
     assert_close(out.cpu().numpy(), O.pipeline12_reinhard(packed, 0, False, None, "f16", "u8", gamma=0.8),
                  "pipeline12 recompute variant")
+
+
+def test_pipeline12_without_work_image_recomputes_ids(ti, rng, dev):
+    """The same call on an IDS frame: no stream kernel takes that layout, and without a work image the library runs
+    the tile recompute chain (four tile passes over the packed frame, three finalize launches)."""
+    from taichi_image_amd import _native
+    H, W = 70, 200
+    packed = natural_packed12(rng, H, W, ids_format=True)
+    pk = torch.from_numpy(packed).to(dev)
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    ws = _native.workspace(H, W, dev)
+    assert _native.pipeline12_route(pk.data_ptr(), out.data_ptr(), None, H, W, 1, ti.types.f16.code,
+                                    ti.types.u8.code)[0] == "recompute"
+    _native.check(_native.lib().mi_isp_pipeline12_reinhard(
+        pk.data_ptr(), out.data_ptr(), None, H, W, 1, 0, None, ti.types.f16.code, ti.types.u8.code, 0.8, 1.0, 1.0, 0.0,
+        ws.data_ptr(), _native.stream_ptr(dev)))
+    assert_close(out.cpu().numpy(), O.pipeline12_reinhard(packed, 0, True, None, "f16", "u8", gamma=0.8),
+                 "pipeline12 tile recompute chain, IDS")
 
 
 def test_pipeline12_params_and_ccm(ti, rng, dev):
