@@ -460,6 +460,40 @@ int mi_isp_chromatic_raw_batch(const void* const* src_host, void* const* cfa_hos
                                const mi_isp_chromatic* chromatic_host, int out_f32_plain, void* stream);
 int mi_isp_chromatic_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, int pattern,
                          const mi_isp_chromatic* chromatic_host, void* stream);
+/* ---- temporal noise reduction ("Temporal noise reduction") ----------------------------------------------
+ * Every raw pixel blended with the same camera's previous output where the scene has not moved, and returned untouched
+ * where it has; in f32 with one rounding per operation, left to right, never contracted: the output is the contract's
+ * bit for bit.  x(p) is the value raw noise reduction filters (above); h(p) the history plane hist_in, an H x W f32 plane
+ * that holds this stage's previous y for the same camera.  From the f32 settings the library computes, in double and
+ * rounded once to f32: rn2 = read_noise^2, c = threshold^2 and R[n] = 1 / n for n = 1 .. 9; wmax = max_weight.  T(p) = the taps (r + 2i, c + 2j),
+ * |i|, |j| <= 1, inside the frame and not set in the defect mask (the centre is a tap unless it is listed), in the order
+ * i = -1, 0, 1 and within a row j = -1, 0, 1; n = |T(p)|.
+ *   D = the sum over T(p), in that order, from its first kept term, of |x(q) - h(q)|;  m = D R[n]
+ *   var = gain max(h(p), 0) + rn2;  qv = (m m) / (c var)   (an IEEE division);  k = max(1 - qv, 0);  w = wmax k
+ *   y = x(p) when n == 0 or w == 0 (selected, not computed), else x(p) + w (h(p) - x(p))
+ *   hist_out(p) = y;  cfa = cast_work(y * g(p))      (g the lens shading gain of shading_host at p, 1 for NULL)
+ * hist_in NULL is an empty history: y = x(p) everywhere.  Finite inputs only.  Source kinds, levels, grids and defect maps
+ * as mi_isp_denoise_raw(_batch).  out_f32_plain != 0: there is no gain and no cast (shading_host must be NULL), hist_out
+ * is the plain f32 y for the next raw stage to take as MI_RAW_32F, and cfa is not written and may be NULL: the frame is
+ * written once.  hist_out must not overlap hist_in, the source, the CFA or another frame's
+ * planes.  One launch per 32 frames.
+ *  - mi_isp_temporal_raw_batch: n frames of one geometry; hist_in_host NULL, or one entry per frame (NULL: empty).
+ *  - mi_isp_temporal_cfa: a normalised H x W CFA of dtype MI_F16 / MI_F32 (no levels, gain or mask), out of the same dtype.
+ * Host-side checks before any launch (error text names "temporal"): gain finite >= 0, read_noise and threshold finite
+ * > 0 with squares that are finite and > 0 in f32, max_weight in [0, 1), shapes, dtypes, kinds, levels, grids, NULL
+ * pointers, overlaps.  n == 0 and H * W == 0 are successful no-ops. */
+typedef struct { float gain, read_noise, threshold, max_weight; } mi_isp_temporal;
+int mi_isp_temporal_raw(const void* src_dev, const float* hist_in_dev, float* hist_out_dev, void* cfa_dev, int H, int W,
+                        int src_kind, int ids_format, int work_dtype, const mi_isp_levels* levels_host,
+                        const mi_isp_shading* shading_host, const mi_isp_defects* defects_host,
+                        const mi_isp_temporal* temporal_host, int out_f32_plain, void* stream);
+int mi_isp_temporal_raw_batch(const void* const* src_host, const float* const* hist_in_host, float* const* hist_out_host,
+                              void* const* cfa_host, int n, int H, int W, int src_kind, int ids_format, int work_dtype,
+                              const mi_isp_levels* levels_host, const mi_isp_shading* shading_host,
+                              const mi_isp_defects* const* defects_host, const mi_isp_temporal* temporal_host,
+                              int out_f32_plain, void* stream);
+int mi_isp_temporal_cfa(const void* in_dev, const float* hist_in_dev, float* hist_out_dev, void* out_dev, int H, int W,
+                        int dtype, const mi_isp_temporal* temporal_host, void* stream);
 /* ---- output sharpening ("Output sharpening") ----------------------------------------------------------
  * An unsharp mask on the luma of a u8 image, in integer arithmetic: the output is the contract's bit for bit.  All values
  * signed 32-bit, >> arithmetic, coordinates outside the image clamped to the edge; b = (1, 2, 1) for radius 1 and

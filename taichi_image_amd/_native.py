@@ -77,6 +77,12 @@ class LocalContrast(ctypes.Structure):
     _fields_ = [("tiles_y", c_int32), ("tiles_x", c_int32), ("clip_q8", c_int32), ("strength_q6", c_int32)]
 
 
+class Temporal(ctypes.Structure):
+    """mi_isp_temporal: the temporal filter's noise model (gain, read_noise, in the loader's x units), the threshold in
+    noise standard deviations and the weight of the past on a static pixel."""
+    _fields_ = [("gain", c_float), ("read_noise", c_float), ("threshold", c_float), ("max_weight", c_float)]
+
+
 class ChromaDenoise(ctypes.Structure):
     """mi_isp_chroma_denoise: the window radius in cells (1, 2 or 3), the luma and chroma thresholds (0 .. 255) and the
     strength times 64 (0 .. 64)."""
@@ -195,6 +201,12 @@ SIGNATURES = {
                                                 _P]),
     "mi_isp_local_contrast_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(LocalContrast),
                                                    _P, _P]),
+    "mi_isp_temporal_raw": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading),
+                                    POINTER(Defects), POINTER(Temporal), c_int, _P]),
+    "mi_isp_temporal_raw_batch": (c_int, [POINTER(_P), POINTER(_P), POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int,
+                                          c_int, c_int, POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Temporal),
+                                          c_int, _P]),
+    "mi_isp_temporal_cfa": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, POINTER(Temporal), _P]),
     "mi_isp_chroma_denoise_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise), _P]),
     "mi_isp_chroma_denoise_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise),
                                                    _P]),

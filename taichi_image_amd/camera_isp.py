@@ -24,6 +24,7 @@ from . import defects as _defects
 from . import denoise as _dn
 from . import highlights as _hl
 from . import chromatic as _ca
+from . import temporal as _tn
 from . import lens as _lens
 from . import sharpen as _shp
 from . import chroma_denoise as _cdn
@@ -290,7 +291,8 @@ def camera_isp(name: str, dtype=types.f32):
                      chroma_denoise=None,
                      color_lut=None,
                      highlights=None,
-                     chromatic_aberration=None):
+                     chromatic_aberration=None,
+                     temporal_denoise=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -309,6 +311,7 @@ def camera_isp(name: str, dtype=types.f32):
             raw_denoise = _dn.check_raw_denoise(raw_denoise)
             highlights = _hl.check_highlights(highlights)
             chromatic_aberration = _ca.check_chromatic_aberration(chromatic_aberration)
+            temporal_denoise = _tn.check_temporal_denoise(temporal_denoise)
             sharpen = _shp.check_sharpen(sharpen)
             local_contrast = _lc.check_local_contrast(local_contrast)
             chroma_denoise = _cdn.check_chroma_denoise(chroma_denoise)
@@ -364,6 +367,10 @@ def camera_isp(name: str, dtype=types.f32):
             # chromatic aberration (an extension): the ChromaticAberration the loaders correct on the CFA, or None (the
             # loaders run exactly as without it).  DESIGN.md 3, "Chromatic aberration".
             self._chromatic = chromatic_aberration
+            # temporal noise reduction (an extension): the TemporalDenoise the loaders apply against the caller's
+            # TemporalHistory objects (history=), or None (the loaders run exactly as without it).  The ISP holds no
+            # per-camera state of its own.  DESIGN.md 3, "Temporal noise reduction".
+            self._temporal = temporal_denoise
             # output sharpening (an extension): the Sharpen applied to every u8 output of the tonemaps, or None (the
             # tonemaps run exactly as without it).  DESIGN.md 3, "Output sharpening".
             self._sharpen = sharpen
@@ -393,7 +400,7 @@ def camera_isp(name: str, dtype=types.f32):
                 transform: Optional[interpolate.ImageTransform] = None,
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
-                highlights=None, chromatic_aberration=None):
+                highlights=None, chromatic_aberration=None, temporal_denoise=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -409,7 +416,9 @@ def camera_isp(name: str, dtype=types.f32):
             chroma_denoise (the extension): None leaves it, False turns it off, a ChromaDenoise replaces it.
             color_lut (the extension): None leaves it, False turns it off, a ColorLut replaces it.
             highlights (the extension): None leaves it, False turns it off, a Highlights replaces it.
-            chromatic_aberration (the extension): None leaves it, False turns it off, a ChromaticAberration replaces it."""
+            chromatic_aberration (the extension): None leaves it, False turns it off, a ChromaticAberration replaces it.
+            temporal_denoise (the extension): None leaves it, False turns it off, a TemporalDenoise replaces it (the
+            histories are the caller's: reset() them when the new settings should not meet old frames)."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -421,6 +430,8 @@ def camera_isp(name: str, dtype=types.f32):
             new_hl = None if highlights is None or highlights is False else _hl.check_highlights(highlights)
             new_ca = (None if chromatic_aberration is None or chromatic_aberration is False
                       else _ca.check_chromatic_aberration(chromatic_aberration))
+            new_tn = (None if temporal_denoise is None or temporal_denoise is False
+                      else _tn.check_temporal_denoise(temporal_denoise))
             new_sharpen = None if sharpen is None or sharpen is False else _shp.check_sharpen(sharpen)
             new_lc = (None if local_contrast is None or local_contrast is False
                       else _lc.check_local_contrast(local_contrast))
@@ -479,6 +490,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._chromatic = None
             elif new_ca is not None:
                 self._chromatic = new_ca
+            if temporal_denoise is False:
+                self._temporal = None
+            elif new_tn is not None:
+                self._temporal = new_tn
             if sharpen is False:
                 self._sharpen = None
             elif new_sharpen is not None:
@@ -633,12 +648,20 @@ def camera_isp(name: str, dtype=types.f32):
             """The ChromaticAberration the loaders correct, or None."""
             return self._chromatic
 
-        def _corrected(self, srcs, h, w, kind, ids_format, lv, maps):
-            """The chromatic aberration route: the raw stages that are on, in the order highlight reconstruction,
-            chromatic aberration, raw noise reduction, one launch each for the raw frames srcs (one shape, source kind
-            `kind`), then the defect fix-up of each frame with a map (maps: one DefectMap or None per frame).  A stage
-            that is not the last writes the plain f32 y, which the next takes as an f32 source without levels; the last
-            applies the grid and the cast; all read the same masks.  DESIGN.md 3, "Chromatic aberration"."""
+        @property
+        def temporal_denoise(self) -> Optional[_tn.TemporalDenoise]:
+            """The TemporalDenoise the loaders apply against their history= objects, or None."""
+            return self._temporal
+
+        def _corrected(self, srcs, h, w, kind, ids_format, lv, maps, hists=None):
+            """The route of the raw chain with chromatic aberration or temporal noise reduction on: the raw stages that
+            are on, in the order highlight reconstruction, chromatic aberration, temporal noise reduction, raw noise
+            reduction, one launch each for the raw frames srcs (one shape, source kind `kind`), then the defect fix-up of
+            each frame with a map (maps: one DefectMap or None per frame).  A stage that is not the last writes the plain
+            f32 y, which the next takes as an f32 source without levels; the last applies the grid and the cast; all read
+            the same masks.  The temporal stage reads and writes the planes of hists (one checked TemporalHistory per
+            frame), which swap once its launch was issued; when it is not the last, its new history planes are the y the
+            next stage reads.  DESIGN.md 3, "Chromatic aberration" and "Temporal noise reduction"."""
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             n = len(srcs)
@@ -652,9 +675,12 @@ def camera_isp(name: str, dtype=types.f32):
                 hl_arg = self._highlights_arg()
                 stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_highlights_raw_batch(
                     i, o, n, h, w, k, f, dtype.code, pattern, l, s, p_maps, hl_arg, plain, stream))
-            ca_arg = self._chromatic._arg((h, w))
-            stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_chromatic_raw_batch(
-                i, o, n, h, w, k, f, dtype.code, pattern, l, s, p_maps, ca_arg, plain, stream))
+            if self._chromatic is not None:
+                ca_arg = self._chromatic._arg((h, w))
+                stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_chromatic_raw_batch(
+                    i, o, n, h, w, k, f, dtype.code, pattern, l, s, p_maps, ca_arg, plain, stream))
+            if self._temporal is not None:
+                stages.append(None)                      # (the stage with histories: below)
             if self._raw_denoise is not None:
                 dn_arg = self._raw_denoise._arg()
                 stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_denoise_raw_batch(
@@ -663,9 +689,21 @@ def camera_isp(name: str, dtype=types.f32):
             cur, cur_kind, cur_ids, cur_lv = srcs, kind, ids, lv
             for k, stage in enumerate(stages):
                 last = k == len(stages) - 1
-                outs = cfas if last else [torch.empty((h, w), dtype=torch.float32, device=self.device) for _ in srcs]
-                _native.check(stage(_native.ptr_array(cur), _native.ptr_array(outs), cur_kind, cur_ids, cur_lv,
-                                    sh if last else None, int(not last)))
+                if stage is None:
+                    planes = [hist._begin((h, w), self.device) for hist in hists]
+                    outs = cfas if last else [new for _, new in planes]
+                    _native.check(L.mi_isp_temporal_raw_batch(
+                        _native.ptr_array(cur), (ctypes.c_void_p * n)(*[None if old is None else old.data_ptr()
+                                                                        for old, _ in planes]),
+                        _native.ptr_array([new for _, new in planes]), _native.ptr_array(cfas) if last else None, n, h, w,
+                        cur_kind, cur_ids, dtype.code, cur_lv, sh if last else None, p_maps, self._temporal._arg(),
+                        int(not last), stream))
+                    for hist in hists:
+                        hist._commit()
+                else:
+                    outs = cfas if last else [torch.empty((h, w), dtype=torch.float32, device=self.device) for _ in srcs]
+                    _native.check(stage(_native.ptr_array(cur), _native.ptr_array(outs), cur_kind, cur_ids, cur_lv,
+                                        sh if last else None, int(not last)))
                 cur, cur_kind, cur_ids, cur_lv = outs, _native.MI_RAW_32F, 0, None
             for cfa, a in zip(cfas, args):
                 if a is not None:
@@ -751,7 +789,7 @@ def camera_isp(name: str, dtype=types.f32):
             hd, wd, scale = self._geometry(*image.shape[:2])
             return interpolate.resize_bilinear(image, (wd, hd), scale)
 
-        def _convert(self, image, mode, src_dtype, defects=None, undistort=None):
+        def _convert(self, image, mode, src_dtype, defects=None, undistort=None, history=None):
             if not isinstance(image, torch.Tensor):
                 raise TypeError("image must be a torch.Tensor")
             assert image.ndim == 2, "image must be a 2-D CFA"
@@ -765,11 +803,13 @@ def camera_isp(name: str, dtype=types.f32):
                                  "load_16f / load_32f take normalised values")
             if self._chromatic is not None:
                 self._chromatic.check_shape((h, w))      # (before anything is uploaded or launched)
+            hists = _tn.check_histories(self._temporal, None if history is None else [history], 1, (h, w), self.device)
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             src = image.to(self.device).contiguous()
-            if self._chromatic is not None:              # chromatic aberration, among the raw stages that are on
-                cfa = self._corrected([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
+            if self._chromatic is not None or self._temporal is not None:
+                # chromatic aberration or temporal noise reduction, among the raw stages that are on
+                cfa = self._corrected([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm], hists)[0]
             elif self._highlights is not None:           # highlight reconstruction (then raw noise reduction, if on)
                 cfa = self._reconstructed([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
             elif self._raw_denoise is not None:          # raw noise reduction: the filtered CFA, its defects fixed up
@@ -787,18 +827,20 @@ def camera_isp(name: str, dtype=types.f32):
                     float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(), stream))
             return self._process_image(cfa, lens)
 
-        def load_16u(self, image, defects=None, undistort=None):
+        def load_16u(self, image, defects=None, undistort=None, history=None):
             """camera_isp.py:318-321 (kernel :82-87).  defects (an extension): None or the DefectMap of this sensor.
-            undistort (an extension): None or the lens.LensDistortion of this camera ("Lens distortion")."""
-            return self._convert(image, 0, torch.uint16, defects, undistort)
+            undistort (an extension): None or the lens.LensDistortion of this camera ("Lens distortion").
+            history (an extension): with temporal_denoise on, the TemporalHistory of this camera ("Temporal
+            noise reduction"); None otherwise."""
+            return self._convert(image, 0, torch.uint16, defects, undistort, history)
 
-        def load_16f(self, image, defects=None, undistort=None):
+        def load_16f(self, image, defects=None, undistort=None, history=None):
             """camera_isp.py:323-326 (kernel :95-99: u16 converted numerically)."""
-            return self._convert(image, 2, torch.uint16, defects, undistort)
+            return self._convert(image, 2, torch.uint16, defects, undistort, history)
 
-        def load_32f(self, image, defects=None, undistort=None):
+        def load_32f(self, image, defects=None, undistort=None, history=None):
             """camera_isp.py:328-331 (kernel :89-93)."""
-            return self._convert(image, 1, torch.float32, defects, undistort)
+            return self._convert(image, 1, torch.float32, defects, undistort, history)
 
         def _check_lens(self, undistort, shape):
             """The lens of a frame of `shape` (None: none); ValueError for another frame shape or a table of another
@@ -871,25 +913,33 @@ def camera_isp(name: str, dtype=types.f32):
                 raise ValueError(f"{what} has {len(values)} entries for {n} frames")
             return [check(v, shape) for v in values]
 
-        def _load_packed(self, frames, bits, ids_format, defects, undistort, batch):
+        def _load_packed(self, frames, bits, ids_format, defects, undistort, batch, history=None):
             """Every packed loader: the frames checked (levels, defect maps and lenses too, before anything is uploaded or
             launched), loaded by their route - raw noise reduction, lens remap, or the plain load - and, with auto white
             balance on, their statistics added to the pending sums in one launch behind the loads.  defects, undistort:
-            None or one entry per frame.  batch: the caller is the batch surface (see _load_frames)."""
+            None or one entry per frame; history: with temporal noise reduction on, one TemporalHistory per frame.  batch:
+            the caller is the batch surface (see _load_frames)."""
             h, w = self._packed_shape(frames, bits)
             lv = self._levels(bits)
             maps = self._per_frame("defects", defects, len(frames), (h, w), _defects.check_defects)
             lenses = self._per_frame("undistort", undistort, len(frames), (h, w), self._check_lens)
             if self._chromatic is not None:
                 self._chromatic.check_shape((h, w))
+            if history is not None and not isinstance(history, (list, tuple)):
+                raise ValueError(f"history must be None or a list with one TemporalHistory per frame, got "
+                                 f"{type(history).__name__}")
+            hists = _tn.check_histories(self._temporal, history, len(frames), (h, w), self.device)
             srcs = [d.to(self.device).contiguous() for d in frames]
-            if self._chromatic is not None or self._highlights is not None or self._raw_denoise is not None:
-                # the raw stages - highlight reconstruction, chromatic aberration, raw noise reduction - that are on: one
-                # launch each, then per frame
+            if (self._chromatic is not None or self._temporal is not None or self._highlights is not None
+                    or self._raw_denoise is not None):
+                # the raw stages - highlight reconstruction, chromatic aberration, temporal noise reduction, raw noise
+                # reduction - that are on: one launch each, then per frame
                 kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
-                route = (self._corrected if self._chromatic is not None
-                         else self._reconstructed if self._highlights is not None else self._denoised)
-                cfas = route(srcs, h, w, kind, ids_format, lv, maps)
+                if self._chromatic is not None or self._temporal is not None:
+                    cfas = self._corrected(srcs, h, w, kind, ids_format, lv, maps, hists)
+                else:
+                    route = self._reconstructed if self._highlights is not None else self._denoised
+                    cfas = route(srcs, h, w, kind, ids_format, lv, maps)
                 rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
             elif lenses.count(None) < len(lenses):       # (some frame has a lens)
                 # lens distortion: the frames without a lens as the call without lenses, the others loaded at full
@@ -955,34 +1005,46 @@ def camera_isp(name: str, dtype=types.f32):
                     _tag_subsample(rgb, sub, st)
             return [self.resize_image(rgb) for rgb in rgbs] if separate else rgbs
 
-        def load_packed12(self, image_data, ids_format=False, defects=None, undistort=None):
+        def load_packed12(self, image_data, ids_format=False, defects=None, undistort=None, history=None):
             """camera_isp.py:333-340: unpack + demosaic (+ccm) fused in one pass over the packed frame.
             defects (an extension): None or the DefectMap of this sensor ("Defective pixels").
             undistort (an extension): None or the lens.LensDistortion of this camera ("Lens distortion"): the
-            frame is loaded at full resolution, then remapped at the resize geometry (the fused resize is not used)."""
+            frame is loaded at full resolution, then remapped at the resize geometry (the fused resize is not used).
+            history (an extension): with temporal_denoise on, the TemporalHistory of this camera: the frame is filtered
+            against it and becomes its new content ("Temporal noise reduction"); None otherwise."""
             return self._load_packed([image_data], 12, ids_format, None if defects is None else [defects],
-                                     None if undistort is None else [undistort], False)[0]
+                                     None if undistort is None else [undistort], False,
+                                     None if history is None else [history])[0]
 
-        def load_packed16(self, image_data, defects=None, undistort=None):
+        def load_packed16(self, image_data, defects=None, undistort=None, history=None):
             """camera_isp.py:342-347."""
             return self._load_packed([image_data], 16, False, None if defects is None else [defects],
-                                     None if undistort is None else [undistort], False)[0]
+                                     None if undistort is None else [undistort], False,
+                                     None if history is None else [history])[0]
 
         def load_packed12_batch(self, images_data: List[torch.Tensor], ids_format=False,
-                                defects=None, undistort=None) -> List[torch.Tensor]:
+                                defects=None, undistort=None, history=None) -> List[torch.Tensor]:
             """Extension (not in the reference): `[self.load_packed12(d, ids_format) for d in images_data]` for the cameras
             of one group - frames of one size - in ONE launch per 8 cameras (mi_isp_load_packed_batch): same results, bit
             for bit, without the other launches' dispatch, table build and drain (config 3: 43.0 -> 39.5 us per frame).
             defects: None, or one entry per frame (a DefectMap or None); the fix-ups of all frames take one launch.
-            undistort: None, or one entry per frame (a LensDistortion or None); the analytic remaps take one launch."""
+            undistort: None, or one entry per frame (a LensDistortion or None); the analytic remaps take one launch.
+            history: with temporal_denoise on, a list with the TemporalHistory of each frame's camera (no object twice);
+            the frames' temporal stage takes one launch."""
             _typecheck("images_data", images_data, list)
-            return self._load_packed(images_data, 12, ids_format, defects, undistort, True) if images_data else []
+            if not images_data:
+                _tn.check_histories(self._temporal, history, 0, (0, 0), self.device)
+                return []
+            return self._load_packed(images_data, 12, ids_format, defects, undistort, True, history)
 
         def load_packed16_batch(self, images_data: List[torch.Tensor], defects=None,
-                                undistort=None) -> List[torch.Tensor]:
+                                undistort=None, history=None) -> List[torch.Tensor]:
             """The same for `load_packed16` (camera_isp.py:342-347)."""
             _typecheck("images_data", images_data, list)
-            return self._load_packed(images_data, 16, False, defects, undistort, True) if images_data else []
+            if not images_data:
+                _tn.check_histories(self._temporal, history, 0, (0, 0), self.device)
+                return []
+            return self._load_packed(images_data, 16, False, defects, undistort, True, history)
 
         @property
         def color_correct_matrix(self) -> Optional[np.ndarray]:
@@ -1137,7 +1199,7 @@ def camera_isp(name: str, dtype=types.f32):
 
         def process_packed12(self, frames: List[torch.Tensor], gamma: float = 1.0, intensity: float = 1.0,
                              light_adapt: float = 1.0, color_adapt: float = 0.0, keep_images: bool = False,
-                             ids_format: bool = False, defects=None, undistort=None):
+                             ids_format: bool = False, defects=None, undistort=None, history=None):
             """Extension (not in the reference): one step of the reference's own bench in one call -
             `Processor.__call__` of bench/camera_isp.py:23-27:
 
@@ -1153,7 +1215,8 @@ def camera_isp(name: str, dtype=types.f32):
             keep_images=True returns `(outputs, images)`, the images holding what the reference leaves in them (p,
             camera_isp.py:211); by default only the outputs are returned, as the bench's Processor does.
             defects: None, or one entry per frame (a DefectMap or None); any map takes the two calls, the load with
-            `defects=`.  undistort: the same for lenses (a LensDistortion or None per frame)."""
+            `defects=`.  undistort: the same for lenses (a LensDistortion or None per frame).  history: with
+            temporal_denoise on (always the two calls), one TemporalHistory per frame."""
             _typecheck("frames", frames, list)
             _typecheck("keep_images", keep_images, bool)
             for n, v in (("gamma", gamma), ("intensity", intensity), ("light_adapt", light_adapt),
@@ -1181,6 +1244,8 @@ def camera_isp(name: str, dtype=types.f32):
                      and self._raw_denoise is None            # (raw noise reduction: the two calls below)
                      and self._highlights is None             # (highlight reconstruction: the two calls below)
                      and self._chromatic is None              # (chromatic aberration: the two calls below)
+                     and self._temporal is None               # (temporal noise reduction: the two calls below)
+                     and history is None                      # (a history without it: the load below rejects it)
                      and defects is None                      # (defective pixels: the two calls below)
                      and undistort is None                    # (lens distortion: the two calls below)
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8
@@ -1199,7 +1264,8 @@ def camera_isp(name: str, dtype=types.f32):
                 with torch.cuda.device(self.device):
                     fused = bool(group("mi_isp_camera_group_fits", h, w, self._demosaic_pattern.value, dtype.code, 8))
             if not fused:
-                images = self.load_packed12_batch(frames, ids_format, defects=defects, undistort=undistort)
+                images = self.load_packed12_batch(frames, ids_format, defects=defects, undistort=undistort,
+                                                  history=history)
                 outputs = self.tonemap_reinhard(images, gamma, intensity, light_adapt, color_adapt)
                 return (outputs, images) if keep_images else outputs
             if self._local_contrast is not None:

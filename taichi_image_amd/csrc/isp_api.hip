@@ -17,6 +17,7 @@
 #include "isp_denoise.h"
 #include "isp_highlights.h"
 #include "isp_chromatic.h"
+#include "isp_temporal.h"
 #include "isp_sharpen.h"
 #include "isp_chroma_denoise.h"
 #include "isp_color_lut.h"
@@ -1024,6 +1025,164 @@ extern "C" int mi_isp_chromatic_cfa(const void* in, void* out, int H, int W, int
   a.n_frames = 1;
   a.f[0] = {in, out, nullptr};
   return ca::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
+                    (hipStream_t)stream);
+}
+
+// ---- temporal noise reduction (isp_temporal.h; DESIGN.md 3, "Temporal noise reduction") ------------------------------
+// the operator's settings, checked on the host; fills the operator members of a (each rounded once from double)
+static int temporal_settings(tn::Args& a, const mi_isp_temporal* t, const char* who) {
+  MI_REQUIRE(t, "%s: null temporal settings", who);
+  MI_REQUIRE(std::isfinite(t->gain) && t->gain >= 0.f, "%s: temporal gain %g must be finite and >= 0", who, (double)t->gain);
+  MI_REQUIRE(std::isfinite(t->read_noise) && t->read_noise > 0.f, "%s: temporal read_noise %g must be finite and > 0", who,
+             (double)t->read_noise);
+  MI_REQUIRE(std::isfinite(t->threshold) && t->threshold > 0.f, "%s: temporal threshold %g must be finite and > 0", who,
+             (double)t->threshold);
+  MI_REQUIRE(std::isfinite(t->max_weight) && t->max_weight >= 0.f && t->max_weight < 1.f,
+             "%s: temporal max_weight %g must be in [0, 1)", who, (double)t->max_weight);
+  const double rn = t->read_noise, th = t->threshold;
+  a.gain = t->gain;
+  a.rn2 = (float)(rn * rn);
+  a.c = (float)(th * th);
+  a.wmax = t->max_weight;
+  MI_REQUIRE(std::isfinite(a.rn2) && a.rn2 > 0.f, "%s: temporal read_noise %g: its square must be finite and > 0 in f32", who,
+             rn);
+  MI_REQUIRE(std::isfinite(a.c) && a.c > 0.f, "%s: temporal threshold %g: its square must be finite and > 0 in f32", who, th);
+  a.rcp_n[0] = 0.f;
+  for (int n = 1; n < 10; ++n) a.rcp_n[n] = (float)(1.0 / (double)n);
+  return 0;
+}
+
+static int temporal_geometry(int H, int W, int work_dtype, const char* who) {
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad temporal shape %dx%d", who, H, W);
+  MI_REQUIRE(H < (1 << 22) && W < (1 << 24), "%s: temporal frame %dx%d too large", who, H, W);
+  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: temporal work dtype must be f16 or f32", who);
+  return 0;
+}
+
+static bool ranges_overlap(const void* p, size_t np, const void* q, size_t nq) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return p && q && a < b + nq && b < a + np;
+}
+
+// no frame's new history plane may overlap a plane that any frame of the call reads or writes
+static int temporal_overlaps(const void* const* src, size_t src_bytes, const float* const* hin, float* const* hout,
+                             void* const* cfa, size_t cfa_bytes, int n, size_t plane, const char* who) {
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) {
+      MI_REQUIRE(!ranges_overlap(hout[i], plane, src[j], src_bytes),
+                 "%s: temporal: the new history of frame %d overlaps the source of frame %d", who, i, j);
+      MI_REQUIRE(!(hin && ranges_overlap(hout[i], plane, hin[j], plane)),
+                 "%s: temporal: the new history of frame %d overlaps the history of frame %d", who, i, j);
+      MI_REQUIRE(!(cfa && ranges_overlap(hout[i], plane, cfa[j], cfa_bytes)),
+                 "%s: temporal: the new history of frame %d overlaps the CFA of frame %d", who, i, j);
+      MI_REQUIRE(i == j || !ranges_overlap(hout[i], plane, hout[j], plane),
+                 "%s: temporal: the new histories of frames %d and %d overlap", who, i, j);
+    }
+  return 0;
+}
+
+// n raw frames of one geometry: every frame's pointers (and defect mask) in the kernel arguments, 32 per launch
+static int temporal_raw_impl(const void* const* src, const float* const* hin, float* const* hout, void* const* cfa, int n,
+                             int H, int W, int kind, int ids_format, int work_dtype, const mi_isp_levels* levels,
+                             const mi_isp_shading* shading, const mi_isp_defects* const* defects, const mi_isp_temporal* t,
+                             int plain, void* stream, const char* who) {
+  tn::Args a = {};
+  if (int rc = temporal_settings(a, t, who)) return rc;
+  if (int rc = temporal_geometry(H, W, work_dtype, who)) return rc;
+  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad temporal source kind %d", who, kind);
+  MI_REQUIRE(n >= 0, "%s: temporal with %d frames", who, n);
+  if (n == 0 || H == 0 || W == 0) return 0;
+  MI_REQUIRE(src && hout && (cfa || plain), "%s: temporal: null frame list", who);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && hout[i], "%s: temporal: frame %d has a null pointer", who, i);
+    MI_REQUIRE(plain || cfa[i], "%s: temporal: frame %d has a null CFA", who, i);
+    MI_REQUIRE(plain || src[i] != cfa[i], "%s: temporal: frame %d: the CFA must not overwrite its source", who, i);
+  }
+  MI_REQUIRE(!plain || !shading, "%s: temporal: the plain f32 output takes no shading grid", who);
+  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
+  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: temporal: packed frames must be even size, got %dx%d", who, H, W);
+  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: temporal: the IDS layout is a packed-12 layout", who);
+  const size_t px = (size_t)H * (size_t)W;
+  const size_t src_bytes = kind == MI_RAW_PACKED12 ? px * 3 / 2 : (kind == MI_RAW_32F ? px * 4 : px * 2);
+  if (int rc = temporal_overlaps(src, src_bytes, hin, hout, plain ? nullptr : cfa, px * mi_dtype_size(work_dtype), n, px * 4,
+                                 who))
+    return rc;
+  a.H = H; a.W = W;
+  int src_kind;
+  if (packed) {
+    tile::Params p = {};
+    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
+    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
+    if (int rc = apply_levels(p, levels, bits, who)) return rc;
+    for (int s = 0; s < 4; ++s) {                     // the per-site decode of the shading path (apply_levels_shading)
+      a.black[s] = p.levels ? p.lv_black[s] : 0;
+      a.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
+    }
+    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
+  } else {
+    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
+      MI_REQUIRE(kind == MI_RAW_16U, "%s: temporal: levels apply to u16 codes only (source kind %d)", who, kind);
+      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
+      for (int s = 0; s < 4; ++s) a.k[s] = (float)(levels->white - levels->black[s]);
+      a.levels = 1;
+    }
+    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
+  }
+  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
+  a.mask_w = (W + 31) / 32;
+  for (int i = 0; i < n; ++i)
+    if (defects && defects[i]) {
+      MI_REQUIRE(defects[i]->n >= 0, "%s: temporal: negative defect count %d", who, (int)defects[i]->n);
+      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: temporal: frame %d: defects without a mask", who, i);
+    }
+  const int out = plain ? tn::OUT_PLAIN : (work_dtype == MI_F16 ? tn::OUT_F16 : tn::OUT_F32);
+  for (int i0 = 0; i0 < n; i0 += tn::MAX_FRAMES) {
+    a.n_frames = n - i0 < tn::MAX_FRAMES ? n - i0 : tn::MAX_FRAMES;
+    for (int i = 0; i < a.n_frames; ++i) {
+      const mi_isp_defects* m = defects ? defects[i0 + i] : nullptr;
+      a.f[i] = {src[i0 + i], plain ? nullptr : cfa[i0 + i], hin ? hin[i0 + i] : nullptr, hout[i0 + i],
+                (m && m->n > 0) ? m->mask_dev : nullptr};
+    }
+    if (int rc = tn::launch(a, src_kind, out, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_temporal_raw(const void* src, const float* hist_in, float* hist_out, void* cfa, int H, int W, int kind,
+                                   int ids_format, int work_dtype, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                   const mi_isp_defects* defects, const mi_isp_temporal* temporal, int out_f32_plain,
+                                   void* stream) {
+  return temporal_raw_impl(&src, &hist_in, &hist_out, &cfa, 1, H, W, kind, ids_format, work_dtype, levels, shading, &defects,
+                           temporal, out_f32_plain, stream, "temporal_raw");
+}
+
+extern "C" int mi_isp_temporal_raw_batch(const void* const* src, const float* const* hist_in, float* const* hist_out,
+                                         void* const* cfa, int n, int H, int W, int kind, int ids_format, int work_dtype,
+                                         const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                         const mi_isp_defects* const* defects, const mi_isp_temporal* temporal,
+                                         int out_f32_plain, void* stream) {
+  return temporal_raw_impl(src, hist_in, hist_out, cfa, n, H, W, kind, ids_format, work_dtype, levels, shading, defects,
+                           temporal, out_f32_plain, stream, "temporal_raw_batch");
+}
+
+extern "C" int mi_isp_temporal_cfa(const void* in, const float* hist_in, float* hist_out, void* out, int H, int W, int dtype,
+                                   const mi_isp_temporal* temporal, void* stream) {
+  const char* who = "temporal_cfa";
+  tn::Args a = {};
+  if (int rc = temporal_settings(a, temporal, who)) return rc;
+  if (int rc = temporal_geometry(H, W, dtype, who)) return rc;
+  if (H == 0 || W == 0) return 0;
+  MI_REQUIRE(in && out && hist_out, "%s: temporal: null pointer", who);
+  MI_REQUIRE(in != out, "%s: temporal: the output must not overwrite the input", who);
+  const size_t px = (size_t)H * (size_t)W;
+  const float* hins[1] = {hist_in};
+  if (int rc = temporal_overlaps(&in, px * mi_dtype_size(dtype), hins, &hist_out, &out, px * mi_dtype_size(dtype), 1, px * 4,
+                                 who))
+    return rc;
+  a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
+  a.n_frames = 1;
+  a.f[0] = {in, out, hist_in, hist_out, nullptr};
+  return tn::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? tn::OUT_F16 : tn::OUT_F32,
                     (hipStream_t)stream);
 }
 

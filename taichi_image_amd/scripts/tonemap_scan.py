@@ -209,6 +209,13 @@ def build_parser() -> argparse.ArgumentParser:
                       metavar=("R0", "R1", "R2", "B0", "B1", "B2"), default=None)
     tone.add_argument("--chromatic-center", dest="chromatic_center", type=float, nargs=2, metavar=("CY", "CX"), default=None)
     tone.add_argument("--chromatic-norm-radius", dest="chromatic_norm_radius", type=float, metavar="R", default=None)
+    # temporal noise reduction (an extension): the sensor's noise model as for --raw-denoise, the mean absolute frame
+    # difference (in noise standard deviations) at which the past is dropped, and the weight of the past on a static pixel;
+    # one history per camera folder, kept across the scan's frames (with --reverse too: it is still a sequence)
+    tone.add_argument("--temporal-denoise", dest="temporal_denoise", type=float, nargs=2, metavar=("GAIN", "READ_NOISE"),
+                      default=None)
+    tone.add_argument("--temporal-threshold", dest="temporal_threshold", type=float, metavar="SIGMAS", default=None)
+    tone.add_argument("--temporal-max-weight", dest="temporal_max_weight", type=float, metavar="W", default=None)
     # output sharpening (an extension): an unsharp mask on the luma of the u8 outputs; AMOUNT 0 .. 8, the blur radius (1 or
     # 2), the coring threshold in luma codes and the halo clamp (luma codes; default: none)
     tone.add_argument("--sharpen", dest="sharpen", type=float, metavar="AMOUNT", default=None)
@@ -246,6 +253,7 @@ def main(argv=None) -> int:
     from ..denoise import RawDenoise
     from ..highlights import Highlights
     from ..chromatic import ChromaticAberration
+    from ..temporal import TemporalDenoise, TemporalHistory
     from ..sharpen import Sharpen
     from ..local_contrast import LocalContrast
     from ..chroma_denoise import ChromaDenoise
@@ -278,6 +286,13 @@ def main(argv=None) -> int:
                                         norm_radius=args.chromatic_norm_radius)
     elif args.chromatic_center is not None or args.chromatic_norm_radius is not None:
         raise ValueError("--chromatic-center / --chromatic-norm-radius need --chromatic-aberration R0 R1 R2 B0 B1 B2")
+    temporal = None
+    if args.temporal_denoise is not None:                           # (also before any frame is read)
+        temporal = TemporalDenoise(args.temporal_denoise[0], args.temporal_denoise[1],
+                                   threshold=3.0 if args.temporal_threshold is None else args.temporal_threshold,
+                                   max_weight=0.75 if args.temporal_max_weight is None else args.temporal_max_weight)
+    elif args.temporal_threshold is not None or args.temporal_max_weight is not None:
+        raise ValueError("--temporal-threshold / --temporal-max-weight need --temporal-denoise GAIN READ_NOISE")
     sharpen = None
     if args.sharpen is not None:                                    # (also before any frame is read)
         sharpen = Sharpen(args.sharpen, radius=args.sharpen_radius, threshold=args.sharpen_threshold,
@@ -314,7 +329,9 @@ def main(argv=None) -> int:
                               black_level=black, white_level=args.white_level, lens_shading=shading,
                               auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen,
                               local_contrast=local_contrast, chroma_denoise=chroma_denoise, color_lut=color_lut,
-                              highlights=highlights, chromatic_aberration=chromatic)
+                              highlights=highlights, chromatic_aberration=chromatic, temporal_denoise=temporal)
+    # temporal noise reduction: the state of each camera folder, for the whole scan
+    histories = [TemporalHistory() if temporal is not None else None for _ in index.cameras]
     row_bytes = args.width * 3 // 2
     if args.write is not None:
         args.write.mkdir(exist_ok=True, parents=True)
@@ -327,8 +344,8 @@ def main(argv=None) -> int:
             shape = (frames[0].shape[0], args.width)
             maps = [DefectMap(coords[c.name], shape) if c.name in coords else None for c in index.cameras]
             lenses = [LensDistortion(shape=shape, **calib[c.name]) if c.name in calib else None for c in index.cameras]
-        images = [isp.load_packed12(f, ids_format=args.ids_format, defects=m, undistort=ln)
-                  for f, m, ln in zip(frames, maps, lenses)]
+        images = [isp.load_packed12(f, ids_format=args.ids_format, defects=m, undistort=ln, history=hist)
+                  for f, m, ln, hist in zip(frames, maps, lenses, histories)]
         outputs = isp.tonemap_reinhard(images, gamma=args.gamma, intensity=args.intensity,
                                        color_adapt=args.color_adapt, light_adapt=args.light_adapt)
         if args.write is not None:
