@@ -494,6 +494,46 @@ int mi_isp_temporal_raw_batch(const void* const* src_host, const float* const* h
                               int out_f32_plain, void* stream);
 int mi_isp_temporal_cfa(const void* in_dev, const float* hist_in_dev, float* hist_out_dev, void* out_dev, int H, int W,
                         int dtype, const mi_isp_temporal* temporal_host, void* stream);
+/* ---- exposure merge ("Exposure merge") ------------------------------------------------------------------
+ * E raw frames of one camera and one instant (2 <= E = n <= 4, the shortest exposure first, ratio[0] == 1, ratios
+ * strictly increasing and <= 65536) merged into one linear raw frame y in the units of the shortest; in f32 with one
+ * rounding per operation, left to right, never contracted, IEEE divisions: the output is the contract's bit for bit.
+ * x_e(p) is the value raw noise reduction filters (above) of frame e.  gain, read_noise: the noise model in the units of
+ * the shortest frame's x; saturation (in the units of x): a long frame's value at or above it is not used; knee: the
+ * usable weight falls linearly from 1 at saturation (1 - knee) to 0 at saturation; threshold: the mean absolute
+ * difference to the shortest frame, in noise standard deviations, at which a long frame is dropped.  From the f32
+ * settings the library computes, in double and rounded once to f32: inv_e = 1 / ratio_e, i2_e = 1 / ratio_e^2,
+ * rn2 = read_noise^2, c = threshold^2, rf = 1 / (saturation knee) and R[n] = 1 / n for n = 1 .. 9.  T(p) = the taps
+ * (r + 2i, c + 2j), |i|, |j| <= 1, inside the frame and not set in the defect mask, in the order i = -1, 0, 1 and within
+ * a row j = -1, 0, 1; n = |T(p)|.
+ *   s0 = x_0(p);  v0 = gain max(s0, 0) + rn2;  a0 = 1 / v0;  num = a0 s0;  den = a0
+ *   for e = 1 .. E - 1:  se(q) = x_e(q) inv_e;  D = the sum over T(p), from its first kept term, of |se(q) - x_0(q)|
+ *     m = D R[n];  ve = (gain max(x_e(p), 0) + rn2) i2_e;  qv = (m m) / (c (v0 + ve));  k = max(1 - qv, 0)
+ *     u = min(max((saturation - x_e(p)) rf, 0), 1);  w = (u k) / ve;  if w > 0: num = num + w se(p), den = den + w
+ *   y = x_0(p) when n == 0 or no long frame had w > 0 (selected, not computed), else num / den
+ *   out = cast_work(y * g(p))                        (g the lens shading gain of shading_host at p, 1 for NULL)
+ * Finite inputs only.  Source kinds, levels, grids and defect maps as mi_isp_denoise_raw(_batch); one defect map per
+ * bracket.  out_f32_plain != 0: there is no gain and no cast (shading_host must be NULL) and out is the plain f32 y for
+ * the next raw stage to take as MI_RAW_32F.  The output must not overlap a source frame or another bracket's output.
+ * One launch per 16 brackets.
+ *  - mi_isp_merge_raw: one bracket; src_host holds its n device pointers.
+ *  - mi_isp_merge_raw_batch: n_brackets brackets of one geometry; src_host holds n_brackets * n device pointers,
+ *    bracket-major; out_host and defects_host one entry per bracket.
+ *  - mi_isp_merge_cfa: n normalised H x W CFAs of dtype MI_F16 / MI_F32 (no levels, gain or mask), out of the same dtype.
+ * Host-side checks before any launch (error text names "exposure merge"): the settings above, every computed constant
+ * finite and > 0 in f32, shapes, dtypes, kinds, levels, grids, NULL pointers, overlaps.  n_brackets == 0 and H * W == 0
+ * are successful no-ops. */
+typedef struct { int32_t n; float ratio[4]; float gain, read_noise, saturation, knee, threshold; } mi_isp_exposure_merge;
+int mi_isp_merge_raw(const void* const* src_host, void* out_dev, int H, int W, int src_kind, int ids_format, int work_dtype,
+                     const mi_isp_levels* levels_host, const mi_isp_shading* shading_host,
+                     const mi_isp_defects* defects_host, const mi_isp_exposure_merge* merge_host, int out_f32_plain,
+                     void* stream);
+int mi_isp_merge_raw_batch(const void* const* src_host, void* const* out_host, int n_brackets, int H, int W, int src_kind,
+                           int ids_format, int work_dtype, const mi_isp_levels* levels_host,
+                           const mi_isp_shading* shading_host, const mi_isp_defects* const* defects_host,
+                           const mi_isp_exposure_merge* merge_host, int out_f32_plain, void* stream);
+int mi_isp_merge_cfa(const void* const* in_host, void* out_dev, int H, int W, int dtype,
+                     const mi_isp_exposure_merge* merge_host, void* stream);
 /* ---- output sharpening ("Output sharpening") ----------------------------------------------------------
  * An unsharp mask on the luma of a u8 image, in integer arithmetic: the output is the contract's bit for bit.  All values
  * signed 32-bit, >> arithmetic, coordinates outside the image clamped to the edge; b = (1, 2, 1) for radius 1 and

@@ -77,6 +77,14 @@ class LocalContrast(ctypes.Structure):
     _fields_ = [("tiles_y", c_int32), ("tiles_x", c_int32), ("clip_q8", c_int32), ("strength_q6", c_int32)]
 
 
+class ExposureMerge(ctypes.Structure):
+    """mi_isp_exposure_merge: the number of exposures, their ratios (the shortest first, ratio[0] == 1), the noise model
+    (gain, read_noise, in the units of the shortest frame's x), the saturation level and knee of the long frames and the
+    rejection threshold in noise standard deviations."""
+    _fields_ = [("n", c_int32), ("ratio", c_float * 4), ("gain", c_float), ("read_noise", c_float),
+                ("saturation", c_float), ("knee", c_float), ("threshold", c_float)]
+
+
 class Temporal(ctypes.Structure):
     """mi_isp_temporal: the temporal filter's noise model (gain, read_noise, in the loader's x units), the threshold in
     noise standard deviations and the weight of the past on a static pixel."""
@@ -207,6 +215,11 @@ SIGNATURES = {
                                           c_int, c_int, POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Temporal),
                                           c_int, _P]),
     "mi_isp_temporal_cfa": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, POINTER(Temporal), _P]),
+    "mi_isp_merge_raw": (c_int, [POINTER(_P), _P, c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading),
+                                 POINTER(Defects), POINTER(ExposureMerge), c_int, _P]),
+    "mi_isp_merge_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Levels),
+                                       POINTER(Shading), POINTER(_P), POINTER(ExposureMerge), c_int, _P]),
+    "mi_isp_merge_cfa": (c_int, [POINTER(_P), _P, c_int, c_int, c_int, POINTER(ExposureMerge), _P]),
     "mi_isp_chroma_denoise_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise), _P]),
     "mi_isp_chroma_denoise_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise),
                                                    _P]),

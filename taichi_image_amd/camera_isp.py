@@ -25,6 +25,7 @@ from . import denoise as _dn
 from . import highlights as _hl
 from . import chromatic as _ca
 from . import temporal as _tn
+from . import exposure_merge as _em
 from . import lens as _lens
 from . import sharpen as _shp
 from . import chroma_denoise as _cdn
@@ -292,7 +293,8 @@ def camera_isp(name: str, dtype=types.f32):
                      color_lut=None,
                      highlights=None,
                      chromatic_aberration=None,
-                     temporal_denoise=None):
+                     temporal_denoise=None,
+                     exposure_merge=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -312,6 +314,7 @@ def camera_isp(name: str, dtype=types.f32):
             highlights = _hl.check_highlights(highlights)
             chromatic_aberration = _ca.check_chromatic_aberration(chromatic_aberration)
             temporal_denoise = _tn.check_temporal_denoise(temporal_denoise)
+            exposure_merge = _em.check_exposure_merge(exposure_merge)
             sharpen = _shp.check_sharpen(sharpen)
             local_contrast = _lc.check_local_contrast(local_contrast)
             chroma_denoise = _cdn.check_chroma_denoise(chroma_denoise)
@@ -371,6 +374,9 @@ def camera_isp(name: str, dtype=types.f32):
             # TemporalHistory objects (history=), or None (the loaders run exactly as without it).  The ISP holds no
             # per-camera state of its own.  DESIGN.md 3, "Temporal noise reduction".
             self._temporal = temporal_denoise
+            # exposure merge (an extension): the ExposureMerge the bracket loaders apply to the E frames of each bracket,
+            # or None (the loaders run exactly as without it).  The stage has no state.  DESIGN.md 3, "Exposure merge".
+            self._merge = exposure_merge
             # output sharpening (an extension): the Sharpen applied to every u8 output of the tonemaps, or None (the
             # tonemaps run exactly as without it).  DESIGN.md 3, "Output sharpening".
             self._sharpen = sharpen
@@ -400,7 +406,7 @@ def camera_isp(name: str, dtype=types.f32):
                 transform: Optional[interpolate.ImageTransform] = None,
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
-                highlights=None, chromatic_aberration=None, temporal_denoise=None):
+                highlights=None, chromatic_aberration=None, temporal_denoise=None, exposure_merge=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -418,7 +424,8 @@ def camera_isp(name: str, dtype=types.f32):
             highlights (the extension): None leaves it, False turns it off, a Highlights replaces it.
             chromatic_aberration (the extension): None leaves it, False turns it off, a ChromaticAberration replaces it.
             temporal_denoise (the extension): None leaves it, False turns it off, a TemporalDenoise replaces it (the
-            histories are the caller's: reset() them when the new settings should not meet old frames)."""
+            histories are the caller's: reset() them when the new settings should not meet old frames).
+            exposure_merge (the extension): None leaves it, False turns it off, an ExposureMerge replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -432,6 +439,8 @@ def camera_isp(name: str, dtype=types.f32):
                       else _ca.check_chromatic_aberration(chromatic_aberration))
             new_tn = (None if temporal_denoise is None or temporal_denoise is False
                       else _tn.check_temporal_denoise(temporal_denoise))
+            new_em = (None if exposure_merge is None or exposure_merge is False
+                      else _em.check_exposure_merge(exposure_merge))
             new_sharpen = None if sharpen is None or sharpen is False else _shp.check_sharpen(sharpen)
             new_lc = (None if local_contrast is None or local_contrast is False
                       else _lc.check_local_contrast(local_contrast))
@@ -494,6 +503,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._temporal = None
             elif new_tn is not None:
                 self._temporal = new_tn
+            if exposure_merge is False:
+                self._merge = None
+            elif new_em is not None:
+                self._merge = new_em
             if sharpen is False:
                 self._sharpen = None
             elif new_sharpen is not None:
@@ -653,15 +666,32 @@ def camera_isp(name: str, dtype=types.f32):
             """The TemporalDenoise the loaders apply against their history= objects, or None."""
             return self._temporal
 
-        def _corrected(self, srcs, h, w, kind, ids_format, lv, maps, hists=None):
-            """The route of the raw chain with chromatic aberration or temporal noise reduction on: the raw stages that
-            are on, in the order highlight reconstruction, chromatic aberration, temporal noise reduction, raw noise
-            reduction, one launch each for the raw frames srcs (one shape, source kind `kind`), then the defect fix-up of
+        @property
+        def exposure_merge(self) -> Optional[_em.ExposureMerge]:
+            """The ExposureMerge the bracket loaders apply, or None."""
+            return self._merge
+
+        def _merge_state(self, bracket, what):
+            """ValueError for a single-frame loader while exposure merge is on, or a bracket loader while it is off
+            (before anything is uploaded or launched)."""
+            if bracket and self._merge is None:
+                raise ValueError(f"{what} takes exposure brackets, but exposure_merge is off: pass "
+                                 f"exposure_merge=ExposureMerge(...) to the camera or to set()")
+            if not bracket and self._merge is not None:
+                raise ValueError(f"exposure_merge is on: {what} takes single frames; use the bracket loaders "
+                                 f"(load_packed12_bracket, load_packed16_bracket, load_16u_bracket, load_16f_bracket, "
+                                 f"load_32f_bracket, load_packed12_bracket_batch, load_packed16_bracket_batch)")
+
+        def _corrected(self, srcs, h, w, kind, ids_format, lv, maps, hists=None, brackets=None):
+            """The route of the raw chain with exposure merge, chromatic aberration or temporal noise reduction on: the raw
+            stages that are on, in the order exposure merge, highlight reconstruction, chromatic aberration, temporal noise
+            reduction, raw noise reduction, one launch each for the raw frames srcs (one shape, source kind `kind`; with
+            exposure merge on brackets holds the E frames of each, and srcs their first), then the defect fix-up of
             each frame with a map (maps: one DefectMap or None per frame).  A stage that is not the last writes the plain
             f32 y, which the next takes as an f32 source without levels; the last applies the grid and the cast; all read
             the same masks.  The temporal stage reads and writes the planes of hists (one checked TemporalHistory per
             frame), which swap once its launch was issued; when it is not the last, its new history planes are the y the
-            next stage reads.  DESIGN.md 3, "Chromatic aberration" and "Temporal noise reduction"."""
+            next stage reads.  DESIGN.md 3, "Exposure merge", "Chromatic aberration" and "Temporal noise reduction"."""
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             n = len(srcs)
@@ -671,6 +701,11 @@ def camera_isp(name: str, dtype=types.f32):
             pattern = self._demosaic_pattern.value
             ids = int(bool(ids_format))
             stages = []
+            if brackets is not None:                     # exposure merge: n * E frames in, n out
+                em_arg = self._merge._arg()
+                flat = _native.ptr_array([f for b in brackets for f in b])
+                stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_merge_raw_batch(
+                    flat, o, n, h, w, k, f, dtype.code, l, s, p_maps, em_arg, plain, stream))
             if self._highlights is not None:
                 hl_arg = self._highlights_arg()
                 stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_highlights_raw_batch(
@@ -794,6 +829,7 @@ def camera_isp(name: str, dtype=types.f32):
                 raise TypeError("image must be a torch.Tensor")
             assert image.ndim == 2, "image must be a 2-D CFA"
             assert image.dtype == src_dtype, f"image must be {src_dtype}, got {image.dtype}"
+            self._merge_state(False, ("load_16u", "load_32f", "load_16f")[mode])
             h, w = image.shape
             dm = _defects.check_defects(defects, (h, w))
             lens = self._check_lens(undistort, (h, w))
@@ -919,6 +955,7 @@ def camera_isp(name: str, dtype=types.f32):
             balance on, their statistics added to the pending sums in one launch behind the loads.  defects, undistort:
             None or one entry per frame; history: with temporal noise reduction on, one TemporalHistory per frame.  batch:
             the caller is the batch surface (see _load_frames)."""
+            self._merge_state(False, f"load_packed{bits}")
             h, w = self._packed_shape(frames, bits)
             lv = self._levels(bits)
             maps = self._per_frame("defects", defects, len(frames), (h, w), _defects.check_defects)
@@ -1045,6 +1082,117 @@ def camera_isp(name: str, dtype=types.f32):
                 _tn.check_histories(self._temporal, history, 0, (0, 0), self.device)
                 return []
             return self._load_packed(images_data, 16, False, defects, undistort, True, history)
+
+        def _convert_bracket(self, frames, mode, src_dtype, defects=None, undistort=None, history=None):
+            """The bracket form of _convert: the E frames of one bracket (exposure merge on), merged and taken through
+            the raw stages that are on; everything is checked before anything is uploaded or launched."""
+            what = ("load_16u_bracket", "load_32f_bracket", "load_16f_bracket")[mode]
+            self._merge_state(True, what)
+            frames = _em.check_bracket(frames, self._merge)
+            assert frames[0].ndim == 2, "the frames must be 2-D CFAs"
+            assert frames[0].dtype == src_dtype, f"the frames must be {src_dtype}, got {frames[0].dtype}"
+            h, w = frames[0].shape
+            dm = _defects.check_defects(defects, (h, w))
+            lens = self._check_lens(undistort, (h, w))
+            lv = self._levels(16)
+            if lv is not None and mode != 0:
+                raise ValueError("black_level / white_level apply to raw codes (load_16u, load_packed12/16); "
+                                 "load_16f / load_32f take normalised values")
+            if self._chromatic is not None:
+                self._chromatic.check_shape((h, w))
+            hists = _tn.check_histories(self._temporal, None if history is None else [history], 1, (h, w), self.device)
+            srcs = [f.to(self.device).contiguous() for f in frames]
+            cfa = self._corrected([srcs[0]], h, w, _native.MI_RAW_16U + mode, False, lv, [dm], hists, brackets=[srcs])[0]
+            if self._awb is not None:                    # auto white balance: the statistics of frame 0 (the output's units)
+                _native.check(_native.lib().mi_isp_awb_stats_cfa(
+                    srcs[0].data_ptr(), h, w, mode, lv, _native.shading_arg(self._shading), float(self._awb.clip),
+                    float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(),
+                    _native.stream_ptr(self.device)))
+            return self._process_image(cfa, lens)
+
+        def load_16u_bracket(self, frames, defects=None, undistort=None, history=None):
+            """Extension: `load_16u` of an exposure bracket (exposure_merge on): frames holds the E frames of one camera
+            and one instant, the shortest exposure first; they are merged into one linear raw frame in the units of the
+            shortest ("Exposure merge"), which then takes the raw stages that are on.  defects: the one
+            DefectMap of the sensor; history: with temporal_denoise on, the TemporalHistory of this camera."""
+            return self._convert_bracket(frames, 0, torch.uint16, defects, undistort, history)
+
+        def load_16f_bracket(self, frames, defects=None, undistort=None, history=None):
+            """The same for `load_16f`."""
+            return self._convert_bracket(frames, 2, torch.uint16, defects, undistort, history)
+
+        def load_32f_bracket(self, frames, defects=None, undistort=None, history=None):
+            """The same for `load_32f`."""
+            return self._convert_bracket(frames, 1, torch.float32, defects, undistort, history)
+
+        def _load_packed_brackets(self, brackets, bits, ids_format, defects, undistort, history):
+            """Every packed bracket loader: the brackets checked (levels, defect maps, lenses and histories too, before
+            anything is uploaded or launched), merged in ONE launch and taken through the raw stages that are on; with auto
+            white balance on the statistics of every bracket's frame 0 are added to the pending sums.  defects, undistort,
+            history: None or one entry per bracket."""
+            what = f"load_packed{bits}_bracket"
+            self._merge_state(True, what)
+            if not isinstance(brackets, (list, tuple)):
+                raise ValueError(f"{what}: brackets must be a list of brackets, got {type(brackets).__name__}")
+            brackets = [_em.check_bracket(b, self._merge, f"bracket {i}") for i, b in enumerate(brackets)]
+            n = len(brackets)
+            if history is not None and not isinstance(history, (list, tuple)):
+                raise ValueError(f"history must be None or a list with one TemporalHistory per bracket, got "
+                                 f"{type(history).__name__}")
+            if n == 0:
+                _tn.check_histories(self._temporal, history, 0, (0, 0), self.device)
+                return []
+            f0 = brackets[0][0]
+            for i, b in enumerate(brackets):
+                if b[0].shape != f0.shape or b[0].dtype != f0.dtype:
+                    raise ValueError(f"bracket {i} holds {tuple(b[0].shape)} {b[0].dtype} frames, bracket 0 "
+                                     f"{tuple(f0.shape)} {f0.dtype}: the brackets of a call share a shape")
+            h, w = self._packed_shape([f for b in brackets for f in b], bits)
+            lv = self._levels(bits)
+            maps = self._per_frame("defects", defects, n, (h, w), _defects.check_defects)
+            lenses = self._per_frame("undistort", undistort, n, (h, w), self._check_lens)
+            if self._chromatic is not None:
+                self._chromatic.check_shape((h, w))
+            hists = _tn.check_histories(self._temporal, history, n, (h, w), self.device)
+            srcs = [[f.to(self.device).contiguous() for f in b] for b in brackets]
+            first = [b[0] for b in srcs]
+            kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
+            cfas = self._corrected(first, h, w, kind, ids_format, lv, maps, hists, brackets=srcs)
+            rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
+            if self._awb is not None:                    # auto white balance: the statistics of each bracket's frame 0
+                _native.check(_native.lib().mi_isp_awb_stats_packed(
+                    _native.ptr_array(first), n, h, w, bits, int(bool(ids_format)), lv,
+                    _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor),
+                    int(self._awb.stride), self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
+            return rgbs
+
+        def load_packed12_bracket(self, frames, ids_format=False, defects=None, undistort=None, history=None):
+            """Extension: `load_packed12` of an exposure bracket (exposure_merge on): frames holds the E packed frames of
+            one camera and one instant, the shortest exposure first ("Exposure merge").  defects: the one
+            DefectMap of the sensor; history: with temporal_denoise on, the TemporalHistory of this camera, which then
+            holds the merged frame."""
+            self._merge_state(True, "load_packed12_bracket")
+            return self._load_packed_brackets([frames], 12, ids_format, None if defects is None else [defects],
+                                              None if undistort is None else [undistort],
+                                              None if history is None else [history])[0]
+
+        def load_packed16_bracket(self, frames, defects=None, undistort=None, history=None):
+            """The same for `load_packed16`."""
+            self._merge_state(True, "load_packed16_bracket")
+            return self._load_packed_brackets([frames], 16, False, None if defects is None else [defects],
+                                              None if undistort is None else [undistort],
+                                              None if history is None else [history])[0]
+
+        def load_packed12_bracket_batch(self, brackets, ids_format=False, defects=None, undistort=None,
+                                        history=None) -> List[torch.Tensor]:
+            """`[self.load_packed12_bracket(b, ids_format) for b in brackets]` for the cameras of one group - brackets of
+            one size - with ONE merge launch per 16 brackets: same results, bit for bit.  defects, undistort, history: None,
+            or one entry per bracket."""
+            return self._load_packed_brackets(brackets, 12, ids_format, defects, undistort, history)
+
+        def load_packed16_bracket_batch(self, brackets, defects=None, undistort=None, history=None) -> List[torch.Tensor]:
+            """The same for `load_packed16_bracket`."""
+            return self._load_packed_brackets(brackets, 16, False, defects, undistort, history)
 
         @property
         def color_correct_matrix(self) -> Optional[np.ndarray]:
@@ -1223,6 +1371,7 @@ def camera_isp(name: str, dtype=types.f32):
                          ("color_adapt", color_adapt)):
                 _typecheck(n, v, float)
             assert len(frames) > 0, "need at least one frame"
+            self._merge_state(False, "process_packed12")
             L = _native.lib()
             f0 = frames[0]
             lv = self._levels(12)                            # (sensor levels: checked before anything runs)

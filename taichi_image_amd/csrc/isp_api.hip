@@ -18,6 +18,7 @@
 #include "isp_highlights.h"
 #include "isp_chromatic.h"
 #include "isp_temporal.h"
+#include "isp_exposure_merge.h"
 #include "isp_sharpen.h"
 #include "isp_chroma_denoise.h"
 #include "isp_color_lut.h"
@@ -1183,6 +1184,176 @@ extern "C" int mi_isp_temporal_cfa(const void* in, const float* hist_in, float* 
   a.n_frames = 1;
   a.f[0] = {in, out, hist_in, hist_out, nullptr};
   return tn::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? tn::OUT_F16 : tn::OUT_F32,
+                    (hipStream_t)stream);
+}
+
+// ---- exposure merge (isp_exposure_merge.h; DESIGN.md 3, "Exposure merge") --------------------------------------------
+// the operator's settings, checked on the host; fills the operator members of a (each rounded once from double)
+static int merge_settings(em::Args& a, const mi_isp_exposure_merge* m, const char* who) {
+  MI_REQUIRE(m, "%s: null exposure merge settings", who);
+  MI_REQUIRE(m->n >= 2 && m->n <= em::MAX_E, "%s: exposure merge takes 2 to 4 exposures, got %d", who, (int)m->n);
+  MI_REQUIRE(m->ratio[0] == 1.f, "%s: exposure merge ratio[0] %g must be 1 (the shortest exposure first)", who,
+             (double)m->ratio[0]);
+  for (int e = 1; e < m->n; ++e)
+    MI_REQUIRE(std::isfinite(m->ratio[e]) && m->ratio[e] > m->ratio[e - 1] && m->ratio[e] <= 65536.f,
+               "%s: exposure merge ratio[%d] %g must be finite, above ratio[%d] and <= 65536", who, e, (double)m->ratio[e],
+               e - 1);
+  MI_REQUIRE(std::isfinite(m->gain) && m->gain >= 0.f, "%s: exposure merge gain %g must be finite and >= 0", who,
+             (double)m->gain);
+  MI_REQUIRE(std::isfinite(m->read_noise) && m->read_noise > 0.f, "%s: exposure merge read_noise %g must be finite and > 0",
+             who, (double)m->read_noise);
+  MI_REQUIRE(std::isfinite(m->saturation) && m->saturation > 0.f, "%s: exposure merge saturation %g must be finite and > 0",
+             who, (double)m->saturation);
+  MI_REQUIRE(std::isfinite(m->knee) && m->knee > 0.f && m->knee <= 1.f, "%s: exposure merge knee %g must be in (0, 1]", who,
+             (double)m->knee);
+  MI_REQUIRE(std::isfinite(m->threshold) && m->threshold > 0.f, "%s: exposure merge threshold %g must be finite and > 0", who,
+             (double)m->threshold);
+  const double rn = m->read_noise, th = m->threshold;
+  a.E = m->n;
+  for (int e = 0; e < em::MAX_E; ++e) {
+    const double q = e < m->n ? (double)m->ratio[e] : 1.0;
+    a.inv[e] = (float)(1.0 / q);
+    a.i2[e] = (float)(1.0 / (q * q));
+    MI_REQUIRE(std::isfinite(a.inv[e]) && a.inv[e] > 0.f && std::isfinite(a.i2[e]) && a.i2[e] > 0.f,
+               "%s: exposure merge ratio[%d] %g: 1 / ratio and 1 / ratio^2 must be finite and > 0 in f32", who, e, q);
+  }
+  a.gain = m->gain;
+  a.rn2 = (float)(rn * rn);
+  a.c = (float)(th * th);
+  a.sat = m->saturation;
+  a.rf = (float)(1.0 / ((double)m->saturation * (double)m->knee));
+  MI_REQUIRE(std::isfinite(a.rn2) && a.rn2 > 0.f, "%s: exposure merge read_noise %g: its square must be finite and > 0 in f32",
+             who, rn);
+  MI_REQUIRE(std::isfinite(a.c) && a.c > 0.f, "%s: exposure merge threshold %g: its square must be finite and > 0 in f32", who,
+             th);
+  MI_REQUIRE(std::isfinite(a.rf) && a.rf > 0.f,
+             "%s: exposure merge: 1 / (saturation * knee) must be finite and > 0 in f32 (saturation %g, knee %g)", who,
+             (double)m->saturation, (double)m->knee);
+  a.rcp_n[0] = 0.f;
+  for (int n = 1; n < 10; ++n) a.rcp_n[n] = (float)(1.0 / (double)n);
+  return 0;
+}
+
+static int merge_geometry(int H, int W, int work_dtype, const char* who) {
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad exposure merge shape %dx%d", who, H, W);
+  MI_REQUIRE(H < (1 << 22) && W < (1 << 24), "%s: exposure merge frame %dx%d too large", who, H, W);
+  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: exposure merge work dtype must be f16 or f32", who);
+  return 0;
+}
+
+// n brackets of one geometry (src: n * E pointers, bracket-major): every bracket's pointers (and defect mask) in the kernel
+// arguments, 16 per launch
+static int merge_raw_impl(const void* const* src, void* const* out, int n, int H, int W, int kind, int ids_format,
+                          int work_dtype, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                          const mi_isp_defects* const* defects, const mi_isp_exposure_merge* m, int plain, void* stream,
+                          const char* who) {
+  em::Args a = {};
+  if (int rc = merge_settings(a, m, who)) return rc;
+  if (int rc = merge_geometry(H, W, work_dtype, who)) return rc;
+  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad exposure merge source kind %d", who, kind);
+  MI_REQUIRE(n >= 0, "%s: exposure merge with %d brackets", who, n);
+  if (n == 0 || H == 0 || W == 0) return 0;
+  MI_REQUIRE(src && out, "%s: exposure merge: null bracket list", who);
+  const int E = a.E;
+  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
+  MI_REQUIRE(!plain || !shading, "%s: exposure merge: the plain f32 output takes no shading grid", who);
+  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: exposure merge: packed frames must be even size, got %dx%d", who, H,
+             W);
+  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: exposure merge: the IDS layout is a packed-12 layout", who);
+  const size_t px = (size_t)H * (size_t)W;
+  const size_t src_bytes = kind == MI_RAW_PACKED12 ? px * 3 / 2 : (kind == MI_RAW_32F ? px * 4 : px * 2);
+  const size_t out_bytes = plain ? px * 4 : px * mi_dtype_size(work_dtype);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(out[i], "%s: exposure merge: bracket %d has a null output", who, i);
+    for (int e = 0; e < E; ++e)
+      MI_REQUIRE(src[(size_t)i * E + e], "%s: exposure merge: bracket %d has a null frame %d", who, i, e);
+  }
+  for (int i = 0; i < n; ++i)                         // no output may overlap a frame any bracket of the call reads
+    for (int j = 0; j < n; ++j) {
+      for (int e = 0; e < E; ++e)
+        MI_REQUIRE(!ranges_overlap(out[i], out_bytes, src[(size_t)j * E + e], src_bytes),
+                   "%s: exposure merge: the output of bracket %d overlaps frame %d of bracket %d", who, i, e, j);
+      MI_REQUIRE(i == j || !ranges_overlap(out[i], out_bytes, out[j], out_bytes),
+                 "%s: exposure merge: the outputs of brackets %d and %d overlap", who, i, j);
+    }
+  a.H = H; a.W = W;
+  int src_kind;
+  if (packed) {
+    tile::Params p = {};
+    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
+    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
+    if (int rc = apply_levels(p, levels, bits, who)) return rc;
+    for (int s = 0; s < 4; ++s) {                     // the per-site decode of the shading path (apply_levels_shading)
+      a.black[s] = p.levels ? p.lv_black[s] : 0;
+      a.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
+    }
+    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
+  } else {
+    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
+      MI_REQUIRE(kind == MI_RAW_16U, "%s: exposure merge: levels apply to u16 codes only (source kind %d)", who, kind);
+      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
+      for (int s = 0; s < 4; ++s) a.k[s] = (float)(levels->white - levels->black[s]);
+      a.levels = 1;
+    }
+    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
+  }
+  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
+  a.mask_w = (W + 31) / 32;
+  for (int i = 0; i < n; ++i)
+    if (defects && defects[i]) {
+      MI_REQUIRE(defects[i]->n >= 0, "%s: exposure merge: negative defect count %d", who, (int)defects[i]->n);
+      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: exposure merge: bracket %d: defects without a mask", who, i);
+    }
+  const int o = plain ? em::OUT_PLAIN : (work_dtype == MI_F16 ? em::OUT_F16 : em::OUT_F32);
+  for (int i0 = 0; i0 < n; i0 += em::MAX_BRACKETS) {
+    a.n_brackets = n - i0 < em::MAX_BRACKETS ? n - i0 : em::MAX_BRACKETS;
+    for (int i = 0; i < a.n_brackets; ++i) {
+      const mi_isp_defects* d = defects ? defects[i0 + i] : nullptr;
+      em::Bracket& b = a.b[i];
+      b = {};
+      for (int e = 0; e < E; ++e) b.src[e] = src[(size_t)(i0 + i) * E + e];
+      b.dst = out[i0 + i];
+      b.mask = (d && d->n > 0) ? d->mask_dev : nullptr;
+    }
+    if (int rc = em::launch(a, src_kind, o, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_merge_raw(const void* const* src, void* out, int H, int W, int kind, int ids_format, int work_dtype,
+                                const mi_isp_levels* levels, const mi_isp_shading* shading, const mi_isp_defects* defects,
+                                const mi_isp_exposure_merge* merge, int out_f32_plain, void* stream) {
+  return merge_raw_impl(src, &out, 1, H, W, kind, ids_format, work_dtype, levels, shading, &defects, merge, out_f32_plain,
+                        stream, "merge_raw");
+}
+
+extern "C" int mi_isp_merge_raw_batch(const void* const* src, void* const* out, int n, int H, int W, int kind, int ids_format,
+                                      int work_dtype, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                      const mi_isp_defects* const* defects, const mi_isp_exposure_merge* merge,
+                                      int out_f32_plain, void* stream) {
+  return merge_raw_impl(src, out, n, H, W, kind, ids_format, work_dtype, levels, shading, defects, merge, out_f32_plain,
+                        stream, "merge_raw_batch");
+}
+
+extern "C" int mi_isp_merge_cfa(const void* const* in, void* out, int H, int W, int dtype,
+                                const mi_isp_exposure_merge* merge, void* stream) {
+  const char* who = "merge_cfa";
+  em::Args a = {};
+  if (int rc = merge_settings(a, merge, who)) return rc;
+  if (int rc = merge_geometry(H, W, dtype, who)) return rc;
+  if (H == 0 || W == 0) return 0;
+  MI_REQUIRE(in && out, "%s: exposure merge: null pointer", who);
+  const size_t bytes = (size_t)H * (size_t)W * mi_dtype_size(dtype);
+  for (int e = 0; e < a.E; ++e) {
+    MI_REQUIRE(in[e], "%s: exposure merge: null frame %d", who, e);
+    MI_REQUIRE(!ranges_overlap(out, bytes, in[e], bytes), "%s: exposure merge: the output overlaps frame %d", who, e);
+  }
+  a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
+  a.n_brackets = 1;
+  a.b[0] = {};
+  for (int e = 0; e < a.E; ++e) a.b[0].src[e] = in[e];
+  a.b[0].dst = out;
+  return em::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? em::OUT_F16 : em::OUT_F32,
                     (hipStream_t)stream);
 }
 
