@@ -90,6 +90,11 @@ int mi_isp_mosaic(const void* rgb_dev, void* cfa_dev, int H, int W, int dtype, i
  * the matrix sees rgb.bgr, and clamp(0, 1, x) is min(1, x). */
 int mi_isp_rgb_to_yuv420(const void* rgb_dev, void* yuv_dev, int H, int W, int in_dtype, int out_dtype,
                          void* stream);
+/* 1 if mi_isp_rgb_to_yuv420 runs its vector kernel on these arguments (W % 16 == 0, both pointers 16-byte aligned, a
+ * chroma plane of a multiple of 16 bytes), 0 for the kernel of one thread per 2x2 block.  Host only: the pointers'
+ * values are read, nothing is launched or dereferenced; the launch asks the same predicate.  Negative with a message
+ * for arguments mi_isp_rgb_to_yuv420 refuses. */
+int mi_isp_rgb_to_yuv420_is_vector(const void* rgb_dev, const void* yuv_dev, int H, int W, int out_dtype);
 /* yuv420_rgb_kernel (yuv_420.py:68-92): the inverse; H, W are the RGB image's. */
 int mi_isp_yuv420_to_rgb(const void* yuv_dev, void* rgb_dev, int H, int W, int in_dtype, int out_dtype,
                          void* stream);
@@ -179,6 +184,15 @@ int mi_isp_tonemap_linear(const void* src_dev, void* dst_dev, int H, int W, int 
 int mi_isp_tonemap_reinhard(const void* src_dev, void* dst_dev, int H, int W, int in_dtype,
                             int out_dtype, float gamma, float intensity, float light_adapt,
                             float color_adapt, void* ws_dev, void* stream);
+/* What mi_isp_tonemap_linear / mi_isp_tonemap_reinhard launch on these arguments, from the shape, the dtypes and the
+ * pointers' values alone (host only; the launches read the same function).  One group is 8 pixels; a pass whose source
+ * and destination are aligned (16 bytes, u8: 8) runs whole waves of 64 whole groups on its straight-line FULL path and the
+ * rest - the groups behind the last whole wave, a ragged last group, every group of an unaligned view - on the general
+ * one.  out_host[0]: blocks of a storing pass (and of the first bounds pass), [1]: blocks of tonemap_reinhard's
+ * statistics and second bounds passes, [2]: FULL groups of a storing pass, [3]: its general groups, a ragged one
+ * included.  Non-zero with a message for arguments the tonemaps refuse. */
+int mi_isp_tonemap_pass_geometry(int H, int W, int in_dtype, int out_dtype, const void* src_dev, const void* dst_dev,
+                                 int64_t out_host[4]);
 
 /* ---- fused hot path ---------------------------------------------------------------------- */
 /* ISP.load_packed12 / load_packed16 (camera_isp.py:333-347,371-373,302-315) in one pass over

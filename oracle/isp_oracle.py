@@ -102,6 +102,8 @@ def decode12(values: np.ndarray, dtype: str = "u16", scaled: bool = False, ids_f
     shape = values.shape
     assert shape[-1] % 3 == 0
     v = decode12_pairs(np.ascontiguousarray(values).reshape(-1), ids_format)
+    # direct (packed.py:103-104): `arr[i] = value` with a u16 value - a numeric conversion for a float array, an integer
+    # narrowing for u8 (astype wraps: the low byte, no saturation)
     out = _write_scaled(v, dtype, 4095.0) if scaled else v.astype(NP_DTYPE[dtype])
     return out.reshape(shape[:-1] + (shape[-1] * 2 // 3,))
 

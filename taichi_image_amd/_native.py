@@ -126,6 +126,7 @@ SIGNATURES = {
     "mi_isp_demosaic": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "mi_isp_mosaic": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "mi_isp_rgb_to_yuv420": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "mi_isp_rgb_to_yuv420_is_vector": (c_int, [_P, _P, c_int, c_int, c_int]),
     "mi_isp_yuv420_to_rgb": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "mi_isp_resize_bilinear": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, _P]),
     "mi_isp_transform": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
@@ -144,6 +145,7 @@ SIGNATURES = {
     "mi_isp_linear": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_float, c_int, _P, _P]),
     "mi_isp_tonemap_linear": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P]),
     "mi_isp_tonemap_reinhard": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, _P, _P]),
+    "mi_isp_tonemap_pass_geometry": (c_int, [c_int, c_int, c_int, c_int, _P, _P, POINTER(c_int64)]),
     "mi_isp_load_packed": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int, c_int,
                                    c_float, _P]),
     "mi_isp_load_packed_metered": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), c_int, c_int, c_int,
@@ -368,6 +370,23 @@ def pipeline12_route(packed_ptr, out_ptr, work_image_ptr, H, W, ids_format, work
     check(lib().mi_isp_pipeline12_route(packed_ptr, out_ptr, work_image_ptr or None, int(H), int(W), int(bool(ids_format)),
                                         int(work_code), int(out_code), ctypes.byref(r)))
     return ROUTES[r.route], r
+
+
+def rgb_to_yuv420_is_vector(rgb_ptr, yuv_ptr, H, W, out_code):
+    """mi_isp_rgb_to_yuv420_is_vector: True when mi_isp_rgb_to_yuv420 runs its vector kernel on these arguments.
+    Addresses as integers; nothing is launched or dereferenced."""
+    rc = lib().mi_isp_rgb_to_yuv420_is_vector(rgb_ptr, yuv_ptr, int(H), int(W), int(out_code))
+    if rc < 0:
+        check(rc)
+    return bool(rc)
+
+
+def tonemap_pass_geometry(H, W, in_code, out_code, src_ptr, dst_ptr):
+    """mi_isp_tonemap_pass_geometry: (blocks of a storing pass, blocks of a reduce pass, FULL groups, general groups) of
+    the stateless tonemaps on these arguments.  Addresses as integers; nothing is launched or dereferenced."""
+    out = (c_int64 * 4)()
+    check(lib().mi_isp_tonemap_pass_geometry(int(H), int(W), int(in_code), int(out_code), src_ptr, dst_ptr, out))
+    return tuple(int(v) for v in out)
 
 
 def levels_arg(black, white):

@@ -18,6 +18,11 @@ constexpr int EW_THREADS = 256;
 // pass's partials (pull_finalize) reads little in total and leaves few partials itself
 constexpr int PASS_THREADS = 512;
 constexpr int PASS_MAX_BLOCKS = 1024;              // capacity of the partial rows; pass_blocks() picks the grid
+// the 8-pixel groups of an RGB pass that take its FULL path: whole waves (64 groups) of whole groups, when the pass can
+// take it at all (rgb_pass_kernel's can_full); shared with the host's mi_isp_tonemap_pass_geometry
+__host__ __device__ static inline int64_t pass_full_groups(int64_t n_px, bool can_full) {
+  return can_full ? (n_px / 8) / 64 * 64 : 0;
+}
 
 static inline int grid_for(int64_t work_items, int cap = 256 * 16) {
   int64_t b = (work_items + EW_THREADS - 1) / EW_THREADS;
@@ -48,8 +53,11 @@ MI_DEV void unpack_pair(uint32_t w, bool ids, uint32_t& p0, uint32_t& p1) {
 }
 
 template <class T> MI_DEV T write_value(uint32_t v, bool scaled, float k) {
-  // packed.py:98-104: scaled -> cast(f32(v) * k); direct -> numeric conversion
-  return scaled ? cast_out<T>((float)v * k) : cast_out<T>((float)v);
+  // packed.py:98-104: scaled -> cast(f32(v) * k); direct -> `arr[i] = value` with a u16 value: a numeric conversion for
+  // a float array, an integer narrowing for u8 (the low byte: 0x1AB -> 0xAB, no saturation)
+  if (scaled) return cast_out<T>((float)v * k);
+  if constexpr (std::is_integral<T>::value) return (T)v;
+  else return cast_out<T>((float)v);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -658,7 +666,7 @@ __global__ __launch_bounds__(PASS_THREADS, 4) void rgb_pass_kernel(const PassArg
   // FULL needs all 64 groups of the wave whole: n_full is a multiple of 64 groups and `tid` strides by
   // whole waves, so `g < n_full` is wave-uniform.
   const bool can_full = a.vec_in && (!STORES || (a.vec_out && a.transform == MI_T_NONE));
-  const int64_t n_full = can_full ? (a.n_px / 8) / 64 * 64 : 0;
+  const int64_t n_full = pass_full_groups(a.n_px, can_full);
   // the first group's loads are in flight while the prologue folds the producer's partials
 
   constexpr int PREFETCH = 1;                       // deeper (2-3 groups) measured slower on gfx950
@@ -848,6 +856,21 @@ __global__ __launch_bounds__(PASS_THREADS, 4) void rgb_pass_kernel(const PassArg
   const bool unit_bounds = (MODE == PM_STATS || MODE == PM_RH_MINMAX || MODE == PM_RH_STORE) && a.no_nan && lo == 0.f && inv == 1.f;
   // the colour-adapt variant (three pows per pixel) only exists for the modes that evaluate reinhard_px
   constexpr bool HAS_REINHARD = MODE == PM_RH_MINMAX || MODE == PM_RH_STORE || MODE == PM_ISP_RH_P1 || MODE == PM_ISP_RH_P2R;
+  // The general loop keeps the FULL loop's split at the last whole wave even where nothing takes the FULL path (n_full == 0:
+  // an unaligned view): a lane then meets the same groups in the same order wherever the buffers lie, so the lanes' f32
+  // sums of the statistics - and through them every bit of the result - do not depend on the alignment of a view.
+  const int64_t n_split = pass_full_groups(a.n_px, true);
+  auto general = [&](auto ca0_c) {
+    int64_t lim = n_split;
+    for (int64_t g = n_full + tid;; g += stride) {
+      if (g >= lim) {
+        if (lim == n_groups) break;
+        lim = n_groups; g = n_split + tid;
+        if (g >= lim) break;
+      }
+      group(std::false_type{}, ca0_c, std::false_type{}, g, raws[0]);
+    }
+  };
   if (!HAS_REINHARD || rk.ca == 0.f) {
     for (int64_t g = tid; g < n_full; g += PREFETCH * stride) {
 #pragma unroll
@@ -858,7 +881,7 @@ __global__ __launch_bounds__(PASS_THREADS, 4) void rgb_pass_kernel(const PassArg
           else group(std::true_type{}, std::true_type{}, std::false_type{}, g + d * stride, raws[d]);
         }
     }
-    for (int64_t g = n_full + tid; g < n_groups; g += stride) group(std::false_type{}, std::true_type{}, std::false_type{}, g, raws[0]);
+    general(std::true_type{});
   } else {
     // colour adaptation (three pows per pixel): whole groups keep the wave-cooperative IO
     for (int64_t g = tid; g < n_full; g += PREFETCH * stride) {
@@ -866,7 +889,7 @@ __global__ __launch_bounds__(PASS_THREADS, 4) void rgb_pass_kernel(const PassArg
       for (int d = 0; d < PREFETCH; ++d)
         if (g + d * stride < n_full) group(std::true_type{}, std::false_type{}, std::false_type{}, g + d * stride, raws[d]);
     }
-    for (int64_t g = n_full + tid; g < n_groups; g += stride) group(std::false_type{}, std::false_type{}, std::false_type{}, g, raws[0]);
+    general(std::false_type{});
   }
 
   if constexpr (PULL_FIN >= 0) {
@@ -1425,6 +1448,16 @@ int subsample(const void* img, void* sub, int H, int W, int stride, int dtype, h
   });
 }
 
+// What the stateless tonemaps launch for these arguments: the groups' IO (PassArgs::vec_in / vec_out) and the grids of the
+// storing passes (tonemap_linear's two passes; tonemap_reinhard's first and last) and of the reduce passes in between.
+// mi_isp_tonemap_pass_geometry reports it; the launches below read it.
+struct TonemapGeometry { int vec_in, vec_out, store_blocks, reduce_blocks; };
+static TonemapGeometry tonemap_geometry(const void* src, const void* dst, int H, int W, int in_dtype, int out_dtype) {
+  const int cap = mi_partial_cap(H, W);
+  const int64_t n_px = (int64_t)H * W;
+  return {vec_ok(src, in_dtype), vec_ok(dst, out_dtype), pass_blocks(n_px, cap), pass_blocks(n_px, cap, true)};
+}
+
 int tail_blocks(int H, int W) { return pass_blocks((int64_t)H * W, mi_partial_cap(H, W)); }
 // The three data passes after the bounds pass of tonemap.py:146-154, chained by pulled finalizes
 // (PassArgs::pull_mode): pass 1 folds the bounds partials `bounds` of whoever produced the image,
@@ -1443,12 +1476,13 @@ int tonemap_reinhard_tail(const void* src, void* dst, int H, int W, int in_dtype
   float* bounds2_part = partials + 6 * (size_t)cap;
   PassArgs a = {};
   a.src = src; a.dst = dst; a.fp = fp; a.fp_w = fp; a.n_px = (int64_t)H * W;
-  a.vec_in = vec_ok(src, in_dtype); a.vec_out = vec_ok(dst, out_dtype);
+  const TonemapGeometry geo = tonemap_geometry(src, dst, H, W, in_dtype, out_dtype);
+  a.vec_in = geo.vec_in; a.vec_out = geo.vec_out;
   a.gamma_inv = 1.0f / gamma; a.la = la; a.ca = ca;
   a.out_scale = mi_scale_factor(out_dtype); a.transform = MI_T_NONE; a.H = H; a.W = W;
   a.pull_npx = (float)a.n_px; a.pull_intensity = intensity;
   a.no_nan = bounds.bounds_post > 0;               // the fused pipeline's image (clamped by the tile kernel)
-  const int nb = pass_blocks(a.n_px, cap), nbr = pass_blocks(a.n_px, cap, true);
+  const int nb = geo.store_blocks, nbr = geo.reduce_blocks;
   // measurement aid: MI_ISP_PULL_DEBUG=0 runs single passes (which > 0) on the scalars a full run left
   // in FrameParams, without the pulled finalize
 #ifdef MI_ISP_MEASURE
@@ -1632,6 +1666,24 @@ template <class F> static int dispatch_dtype2(int in_dtype, int out_dtype, F&& f
   });
 }
 
+// rgb_yuv420_vec_kernel or rgb_yuv420_kernel: whole 8-pixel groups with every row of every plane 16-byte aligned (the
+// second chroma plane starts one plane's bytes behind the first) take the vector kernel
+static bool yuv420_takes_vector(const void* rgb, const void* yuv, int H, int W, int out_dtype) {
+  return W % 16 == 0 && ((uintptr_t)rgb & 15) == 0 && ((uintptr_t)yuv & 15) == 0 &&
+         ((size_t)(H / 2) * (W / 2) * mi_dtype_size_dev(out_dtype)) % 16 == 0;
+}
+
+extern "C" int mi_isp_rgb_to_yuv420_is_vector(const void* rgb, const void* yuv, int H, int W, int out_dtype) {
+  // (1 is an answer here: what mi_isp_rgb_to_yuv420 refuses is -1)
+  if (!rgb || !yuv) { mi_set_error("rgb_to_yuv420_is_vector: null pointer"); return -1; }
+  if (!(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0)) {
+    mi_set_error("rgb_to_yuv420_is_vector: image must be even size, got %dx%d", H, W);
+    return -1;
+  }
+  if (!mi_valid_dtype(out_dtype)) { mi_set_error("rgb_to_yuv420_is_vector: bad dtype %d", out_dtype); return -1; }
+  return yuv420_takes_vector(rgb, yuv, H, W, out_dtype) ? 1 : 0;
+}
+
 extern "C" int mi_isp_rgb_to_yuv420(const void* rgb, void* yuv, int H, int W, int in_dtype, int out_dtype,
                                     void* stream) {
   MI_REQUIRE(rgb && yuv, "rgb_to_yuv420: null pointer");
@@ -1641,10 +1693,7 @@ extern "C" int mi_isp_rgb_to_yuv420(const void* rgb, void* yuv, int H, int W, in
   return dispatch_dtype2(in_dtype, out_dtype, [&](auto ti_tag, auto to_tag) {
     using TI = decltype(ti_tag);
     using TO = decltype(to_tag);
-    // vector path: whole 8-pixel groups, and every row of every plane 16-byte aligned
-    const bool vec = W % 16 == 0 && ((uintptr_t)rgb & 15) == 0 && ((uintptr_t)yuv & 15) == 0 &&
-                     ((size_t)(H / 2) * (W / 2) * sizeof(TO)) % 16 == 0;
-    if (vec)
+    if (yuv420_takes_vector(rgb, yuv, H, W, out_dtype))
       hipLaunchKernelGGL((rgb_yuv420_vec_kernel<TI, TO>), dim3(grid_for((int64_t)(H / 2) * (W / 8))), dim3(EW_THREADS), 0,
                          s, static_cast<const TI*>(rgb), static_cast<TO*>(yuv), H, W);
     else
@@ -2211,6 +2260,20 @@ static int tonemap_check(const void* src, const void* dst, int H, int W, int in_
   return 0;
 }
 
+extern "C" int mi_isp_tonemap_pass_geometry(int H, int W, int in_dtype, int out_dtype, const void* src, const void* dst,
+                                            int64_t out[4]) {
+  MI_REQUIRE(src && dst && out, "tonemap_pass_geometry: null pointer");
+  MI_REQUIRE(H > 0 && W > 0, "tonemap_pass_geometry: bad shape");
+  MI_REQUIRE(mi_valid_dtype(in_dtype) && mi_valid_dtype(out_dtype), "tonemap_pass_geometry: bad dtype");
+  const TonemapGeometry g = tonemap_geometry(src, dst, H, W, in_dtype, out_dtype);
+  const int64_t n_px = (int64_t)H * W;
+  out[0] = g.store_blocks;
+  out[1] = g.reduce_blocks;
+  out[2] = pass_full_groups(n_px, g.vec_in && g.vec_out);      // a storing pass without a transform (rgb_pass_kernel's can_full)
+  out[3] = (n_px + 7) / 8 - out[2];
+  return 0;
+}
+
 extern "C" int mi_isp_tonemap_linear(const void* src, void* dst, int H, int W, int in_dtype, int out_dtype,
                                      float gamma, void* ws, void* stream) {
   if (int rc = tonemap_check(src, dst, H, W, in_dtype, out_dtype, gamma, ws)) return rc;
@@ -2220,10 +2283,11 @@ extern "C" int mi_isp_tonemap_linear(const void* src, void* dst, int H, int W, i
   const int cap = mi_partial_cap(H, W);
   PassArgs a = {};
   a.src = src; a.dst = dst; a.fp = fp; a.partials = partials; a.part_stride = cap; a.n_px = (int64_t)H * W;
-  a.vec_in = vec_ok(src, in_dtype); a.vec_out = vec_ok(dst, out_dtype);
+  const TonemapGeometry geo = tonemap_geometry(src, dst, H, W, in_dtype, out_dtype);
+  a.vec_in = geo.vec_in; a.vec_out = geo.vec_out;
   a.gamma_inv = 1.0f / gamma;                      // tonemap.py:16: 1/gamma evaluated in f32
   a.out_scale = mi_scale_factor(out_dtype); a.transform = MI_T_NONE; a.H = H; a.W = W;
-  const int nb = pass_blocks(a.n_px, cap);
+  const int nb = geo.store_blocks;
   if (int rc = launch_pass(PM_MINMAX, in_dtype, out_dtype, a, nb, s)) return rc;       // tonemap.py:23
   a.pull_mode = FIN_BOUNDS; a.pull_partials = partials; a.pull_stride = cap; a.pull_n = nb; a.fp_w = fp;
   return launch_pass(PM_LINEAR_STORE, in_dtype, out_dtype, a, nb, s);
@@ -2239,10 +2303,11 @@ extern "C" int mi_isp_tonemap_reinhard(const void* src, void* dst, int H, int W,
   const int cap = mi_partial_cap(H, W);
   PassArgs a = {};
   a.src = src; a.dst = dst; a.fp = fp; a.partials = partials; a.part_stride = cap; a.n_px = (int64_t)H * W;
-  a.vec_in = vec_ok(src, in_dtype); a.vec_out = vec_ok(dst, out_dtype);
+  const TonemapGeometry geo = tonemap_geometry(src, dst, H, W, in_dtype, out_dtype);
+  a.vec_in = geo.vec_in; a.vec_out = geo.vec_out;
   a.gamma_inv = 1.0f / gamma; a.la = light_adapt; a.ca = color_adapt;
   a.out_scale = mi_scale_factor(out_dtype); a.transform = MI_T_NONE; a.H = H; a.W = W;
-  const int nb = pass_blocks(a.n_px, cap);
+  const int nb = geo.store_blocks;
   if (int rc = launch_pass(PM_MINMAX, in_dtype, out_dtype, a, nb, s)) return rc;      // tonemap.py:146
   const PullSrc bounds = {partials, cap, nb, 0};
   return tonemap_reinhard_tail(src, dst, H, W, in_dtype, out_dtype, gamma, intensity, light_adapt, color_adapt, fp,

@@ -82,6 +82,12 @@ def test_argument_validation_reports_errors():
     assert L.mi_isp_load_packed_metered_is_fused(3072, 4096, 12, 0, 2, 8) == 1
     assert L.mi_isp_load_packed_metered_is_fused(3072, 4096, 12, 0, 2, 4) == 0 and L.mi_isp_load_packed_metered_is_fused(70, 204, 12, 0, 2, 8) == 0
     assert L.mi_isp_load_packed_metered_is_fused(3072, 4096, 16, 0, 2, 8) == 0 and L.mi_isp_load_packed_metered_is_fused(3072, 4096, 12, 1, 2, 8) == 0
+    # which YUV kernel and which tonemap grids a call gets, from the pointers' values alone (tests/test_gpu_call_surface_matrix.py)
+    a = 0x7F0000000000
+    assert (L.mi_isp_rgb_to_yuv420_is_vector(a, a + 4096, 6, 16, 1), L.mi_isp_rgb_to_yuv420_is_vector(a, a + 4096, 6, 16, 0),
+            L.mi_isp_rgb_to_yuv420_is_vector(a, a + 4100, 8, 32, 1), L.mi_isp_rgb_to_yuv420_is_vector(a, None, 8, 32, 1)) == (1, 0, 0, -1)
+    assert (_native.tonemap_pass_geometry(1031, 2052, 2, 0, a, a + (1 << 30)), _native.tonemap_pass_geometry(50, 70, 2, 0, a, a + (1 << 30) + 1)) \
+        == ((512, 256, 264448, 4), (1, 1, 0, 438))
     assert L.mi_isp_whole_frame_set_poll_limit(0) == 0
     # the camera-group entry points (round 4) validate before they touch a device too
     f = ctypes.c_float
