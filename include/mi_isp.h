@@ -548,6 +548,41 @@ int mi_isp_merge_raw_batch(const void* const* src_host, void* const* out_host, i
                            const mi_isp_exposure_merge* merge_host, int out_f32_plain, void* stream);
 int mi_isp_merge_cfa(const void* const* in_host, void* out_dev, int H, int W, int dtype,
                      const mi_isp_exposure_merge* merge_host, void* stream);
+/* ---- local tone mapping ("Local tone mapping") ------------------------------------------------------------
+ * Every pixel of a work-dtype RGB image (H x W x 3 interleaved, MI_F16 or MI_F32) times a gain that depends only on an
+ * edge-aware local mean of its log-luminance, read from a bilateral grid (splat, blur, slice).  Integer and single f32
+ * operations only (the logarithm and the exponential are the piecewise-linear ones of the f32 bit pattern), so the output
+ * is the contract's bit for bit.  Every line one operation; f32 operations round to nearest and are never contracted,
+ * divisions are IEEE, bits() is the f32 bit pattern as int32, >> arithmetic, float-to-int truncates toward zero,
+ * integer-to-f32 rounds to nearest even:
+ *   li(t) = (bits(min(max(t, floor), white)) - bits(floor)) >> 12
+ *   span = li(white);  zs = f32((bins - 1) / span);  kq = f32(strength * 4096)         (in double, rounded once)
+ *   Y = ((r + b) * 0.25) + (g * 0.5);  l = li(Y);  z = f32(l) * zs
+ *   splat: zi = min(int(z + 0.5), bins - 1);  cnt[y / cell, x / cell, zi] += 1;  sum[same] += l           (u32, exact)
+ *   blur:  Nb = f32(B(cnt)), Sb = f32(B(sum));  B = the separable [1 2 1] filter along all three axes, zero outside the
+ *          grid, accumulated exactly in 64-bit integers, converted once
+ *   slice: gy = clamp((y + 0.5) * (1 / cell) - 0.5, 0, GH - 1);  y0 = min(int(gy), max(GH - 2, 0));  y1 = min(y0 + 1, GH - 1)
+ *          fy = gy - y0;  the same for x;  z0 = min(int(z), bins - 2);  fz = z - z0;  lerp(a, b, f) = a + ((b - a) * f)
+ *          for Nb and for Sb separately: along x on the four (y, z) rows, then along y, then along z
+ *          base = S / N when N > 0, f32(l) otherwise
+ *   gain = float_from_bits(0x3F800000 + int((f32(li(anchor)) - base) * kq));  out_c = cast(v_c * gain) for c = r, g, b
+ * GH = ceil(H / cell), GW = ceil(W / cell); the planes cnt, sum (u32) and Nb, Sb (f32) are [GH][GW][bins].  Inputs must be
+ * finite.  Settings: 0 <= strength <= 1; white > 0; 0 < floor < white with floor a normal f32, white / floor <= 2^24 and
+ * li(white) >= 1; floor <= anchor <= white; cell 8, 16, 32 or 64; 2 <= bins <= 32; every value finite.
+ *  - mi_isp_local_tonemap_workspace_bytes: the bytes of ws_dev for n images of H x W (0 for bad arguments).
+ *  - mi_isp_local_tonemap_batch: n images of one geometry, in place; three launches (splat, blur, apply) per 32 images,
+ *    ordered by the stream, no host synchronisation.  images_host: n device pointers, read on the host, each aligned to
+ *    its element; ws_dev: 16-byte aligned device memory, contents irrelevant before and after the call.
+ *  - mi_isp_local_tonemap_grids: splat and blur of one image into the caller's four planes (GH * GW * bins elements each,
+ *    4-byte aligned, not overlapping); the image is not written.  For tests and measurements.
+ * Host-side checks before any launch (error text names "local_tonemap"): the settings, n >= 0, 0 <= H, W <= 32768, the
+ * dtype, NULL pointers, alignment.  n == 0 and H * W == 0 are successful no-ops. */
+typedef struct { float strength, white, floor, anchor; int32_t cell, bins; } mi_isp_local_tonemap;
+size_t mi_isp_local_tonemap_workspace_bytes(int n, int H, int W, const mi_isp_local_tonemap* settings_host);
+int mi_isp_local_tonemap_batch(void* const* images_host, int n, int H, int W, int dtype,
+                               const mi_isp_local_tonemap* settings_host, void* ws_dev, void* stream);
+int mi_isp_local_tonemap_grids(const void* image_dev, int H, int W, int dtype, const mi_isp_local_tonemap* settings_host,
+                               uint32_t* cnt_dev, uint32_t* sum_dev, float* nb_dev, float* sb_dev, void* stream);
 /* ---- output sharpening ("Output sharpening") ----------------------------------------------------------
  * An unsharp mask on the luma of a u8 image, in integer arithmetic: the output is the contract's bit for bit.  All values
  * signed 32-bit, >> arithmetic, coordinates outside the image clamped to the edge; b = (1, 2, 1) for radius 1 and

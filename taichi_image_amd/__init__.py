@@ -6,7 +6,7 @@ mirror the modules of uc-vision/taichi_image; every op dispatches through ctypes
 libmi355_isp.so (hand-written HIP for gfx950).  There is no CPU fallback.
 """
 from . import types  # noqa: F401
-from . import packed, bayer, interpolate, tonemap, camera_isp, pipeline, distributed, color, ingest, defects, lens, white_balance, denoise, sharpen, local_contrast, chroma_denoise, color_lut, highlights, chromatic, temporal, exposure_merge  # noqa: F401
+from . import packed, bayer, interpolate, tonemap, camera_isp, pipeline, distributed, color, ingest, defects, lens, white_balance, denoise, sharpen, local_contrast, chroma_denoise, color_lut, highlights, chromatic, temporal, exposure_merge, local_tonemap  # noqa: F401
 from .bayer import BayerPattern  # noqa: F401
 from .interpolate import ImageTransform  # noqa: F401
 from .camera_isp import Camera16, Camera32  # noqa: F401
@@ -22,5 +22,6 @@ from .highlights import Highlights  # noqa: F401
 from .chromatic import ChromaticAberration  # noqa: F401
 from .temporal import TemporalDenoise, TemporalHistory, check_temporal_denoise, temporal_cfa  # noqa: F401
 from .exposure_merge import ExposureMerge, check_exposure_merge, merge_cfa  # noqa: F401
+from .local_tonemap import LocalTonemap, check_local_tonemap  # noqa: F401
 
 __version__ = "0.1.0"

@@ -77,6 +77,13 @@ class LocalContrast(ctypes.Structure):
     _fields_ = [("tiles_y", c_int32), ("tiles_x", c_int32), ("clip_q8", c_int32), ("strength_q6", c_int32)]
 
 
+class LocalTonemap(ctypes.Structure):
+    """mi_isp_local_tonemap: the strength (0 .. 1), the white and floor of the log-luminance range, the anchor whose gain is
+    1, the cell side in pixels (8, 16, 32 or 64) and the luminance bins (2 .. 32)."""
+    _fields_ = [("strength", c_float), ("white", c_float), ("floor", c_float), ("anchor", c_float), ("cell", c_int32),
+                ("bins", c_int32)]
+
+
 class ExposureMerge(ctypes.Structure):
     """mi_isp_exposure_merge: the number of exposures, their ratios (the shortest first, ratio[0] == 1), the noise model
     (gain, read_noise, in the units of the shortest frame's x), the saturation level and knee of the long frames and the
@@ -222,6 +229,9 @@ SIGNATURES = {
     "mi_isp_merge_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Levels),
                                        POINTER(Shading), POINTER(_P), POINTER(ExposureMerge), c_int, _P]),
     "mi_isp_merge_cfa": (c_int, [POINTER(_P), _P, c_int, c_int, c_int, POINTER(ExposureMerge), _P]),
+    "mi_isp_local_tonemap_workspace_bytes": (c_size_t, [c_int, c_int, c_int, POINTER(LocalTonemap)]),
+    "mi_isp_local_tonemap_batch": (c_int, [POINTER(_P), c_int, c_int, c_int, c_int, POINTER(LocalTonemap), _P, _P]),
+    "mi_isp_local_tonemap_grids": (c_int, [_P, c_int, c_int, c_int, POINTER(LocalTonemap), _P, _P, _P, _P, _P]),
     "mi_isp_chroma_denoise_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise), _P]),
     "mi_isp_chroma_denoise_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise),
                                                    _P]),

@@ -31,6 +31,7 @@ from . import sharpen as _shp
 from . import chroma_denoise as _cdn
 from . import color_lut as _clut
 from . import local_contrast as _lc
+from . import local_tonemap as _ltm
 from . import white_balance as _wb
 from . import distributed as _dist
 
@@ -294,7 +295,8 @@ def camera_isp(name: str, dtype=types.f32):
                      highlights=None,
                      chromatic_aberration=None,
                      temporal_denoise=None,
-                     exposure_merge=None):
+                     exposure_merge=None,
+                     local_tonemap=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -315,6 +317,7 @@ def camera_isp(name: str, dtype=types.f32):
             chromatic_aberration = _ca.check_chromatic_aberration(chromatic_aberration)
             temporal_denoise = _tn.check_temporal_denoise(temporal_denoise)
             exposure_merge = _em.check_exposure_merge(exposure_merge)
+            local_tonemap = _ltm.check_local_tonemap(local_tonemap)
             sharpen = _shp.check_sharpen(sharpen)
             local_contrast = _lc.check_local_contrast(local_contrast)
             chroma_denoise = _cdn.check_chroma_denoise(chroma_denoise)
@@ -377,6 +380,10 @@ def camera_isp(name: str, dtype=types.f32):
             # exposure merge (an extension): the ExposureMerge the bracket loaders apply to the E frames of each bracket,
             # or None (the loaders run exactly as without it).  The stage has no state.  DESIGN.md 3, "Exposure merge".
             self._merge = exposure_merge
+            # local tone mapping (an extension): the LocalTonemap every loader applies in place to the image it returns,
+            # behind demosaic, resize, lens remap and defect fix-up, or None (the loaders run exactly as without it).
+            # DESIGN.md 3, "Local tone mapping".
+            self._ltm = local_tonemap
             # output sharpening (an extension): the Sharpen applied to every u8 output of the tonemaps, or None (the
             # tonemaps run exactly as without it).  DESIGN.md 3, "Output sharpening".
             self._sharpen = sharpen
@@ -406,7 +413,8 @@ def camera_isp(name: str, dtype=types.f32):
                 transform: Optional[interpolate.ImageTransform] = None,
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
-                highlights=None, chromatic_aberration=None, temporal_denoise=None, exposure_merge=None):
+                highlights=None, chromatic_aberration=None, temporal_denoise=None, exposure_merge=None,
+                local_tonemap=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -425,7 +433,8 @@ def camera_isp(name: str, dtype=types.f32):
             chromatic_aberration (the extension): None leaves it, False turns it off, a ChromaticAberration replaces it.
             temporal_denoise (the extension): None leaves it, False turns it off, a TemporalDenoise replaces it (the
             histories are the caller's: reset() them when the new settings should not meet old frames).
-            exposure_merge (the extension): None leaves it, False turns it off, an ExposureMerge replaces it."""
+            exposure_merge (the extension): None leaves it, False turns it off, an ExposureMerge replaces it.
+            local_tonemap (the extension): None leaves it, False turns it off, a LocalTonemap replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -441,6 +450,8 @@ def camera_isp(name: str, dtype=types.f32):
                       else _tn.check_temporal_denoise(temporal_denoise))
             new_em = (None if exposure_merge is None or exposure_merge is False
                       else _em.check_exposure_merge(exposure_merge))
+            new_ltm = (None if local_tonemap is None or local_tonemap is False
+                       else _ltm.check_local_tonemap(local_tonemap))
             new_sharpen = None if sharpen is None or sharpen is False else _shp.check_sharpen(sharpen)
             new_lc = (None if local_contrast is None or local_contrast is False
                       else _lc.check_local_contrast(local_contrast))
@@ -507,6 +518,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._merge = None
             elif new_em is not None:
                 self._merge = new_em
+            if local_tonemap is False:
+                self._ltm = None
+            elif new_ltm is not None:
+                self._ltm = new_ltm
             if sharpen is False:
                 self._sharpen = None
             elif new_sharpen is not None:
@@ -746,6 +761,20 @@ def camera_isp(name: str, dtype=types.f32):
             return cfas
 
         @property
+        def local_tonemap(self) -> Optional[_ltm.LocalTonemap]:
+            """The LocalTonemap the loaders apply to the images they return, or None."""
+            return self._ltm
+
+        def _tone_mapped(self, rgbs):
+            """The images of a loader call as the caller gets them: with local tone mapping on, mapped in place by ONE call
+            behind everything else of the load on the same stream (the images carry no metering subsample then, so the
+            metering and the tonemaps see the mapped image); else as they are.  DESIGN.md 3, "Local tone mapping"."""
+            if self._ltm is not None and rgbs:
+                _ltm.apply(rgbs, self._ltm)
+                _written_in_place(rgbs)
+            return rgbs
+
+        @property
         def sharpen(self) -> Optional[_shp.Sharpen]:
             """The Sharpen the tonemaps apply to their u8 outputs, or None."""
             return self._sharpen
@@ -861,7 +890,7 @@ def camera_isp(name: str, dtype=types.f32):
                 _native.check(L.mi_isp_awb_stats_cfa(
                     src.data_ptr(), h, w, mode, lv, _native.shading_arg(self._shading), float(self._awb.clip),
                     float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(), stream))
-            return self._process_image(cfa, lens)
+            return self._tone_mapped([self._process_image(cfa, lens)])[0]
 
         def load_16u(self, image, defects=None, undistort=None, history=None):
             """camera_isp.py:318-321 (kernel :82-87).  defects (an extension): None or the DefectMap of this sensor.
@@ -996,7 +1025,7 @@ def camera_isp(name: str, dtype=types.f32):
                     _native.ptr_array(srcs), len(srcs), h, w, bits, int(bool(ids_format)), lv,
                     _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor),
                     int(self._awb.stride), self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
-            return rgbs
+            return self._tone_mapped(rgbs)
 
         def _load_frames(self, srcs, h, w, bits, ids_format, lv, maps, batch, full=False):
             """The load itself: the checked h x w packed frames srcs (on the device; maps: a DefectMap or None each) to
@@ -1017,7 +1046,8 @@ def camera_isp(name: str, dtype=types.f32):
                 hd, wd, scale = h, w, 0.0
             # the image and, on the way, the stride-subsampled copy update_metering will ask for (camera_isp.py:168-170):
             # the load kernel holds those pixels anyway, the strided gather over six 4K images costs 25 us per call
-            metered = not (full or fused or separate) and bool(
+            # (local tone mapping rewrites the image behind the load: no subsample of the unmapped one)
+            metered = not (full or fused or separate) and self._ltm is None and bool(
                 L.mi_isp_load_packed_metered_is_fused(h, w, bits, ids, dtype.code, st))
             rgbs = [torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device) for _ in srcs]
             subs = [torch.empty(((hd + st - 1) // st, (wd + st - 1) // st, 3), dtype=torch_dtype, device=self.device)
@@ -1108,7 +1138,7 @@ def camera_isp(name: str, dtype=types.f32):
                     srcs[0].data_ptr(), h, w, mode, lv, _native.shading_arg(self._shading), float(self._awb.clip),
                     float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(),
                     _native.stream_ptr(self.device)))
-            return self._process_image(cfa, lens)
+            return self._tone_mapped([self._process_image(cfa, lens)])[0]
 
         def load_16u_bracket(self, frames, defects=None, undistort=None, history=None):
             """Extension: `load_16u` of an exposure bracket (exposure_merge on): frames holds the E frames of one camera
@@ -1164,7 +1194,7 @@ def camera_isp(name: str, dtype=types.f32):
                     _native.ptr_array(first), n, h, w, bits, int(bool(ids_format)), lv,
                     _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor),
                     int(self._awb.stride), self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
-            return rgbs
+            return self._tone_mapped(rgbs)
 
         def load_packed12_bracket(self, frames, ids_format=False, defects=None, undistort=None, history=None):
             """Extension: `load_packed12` of an exposure bracket (exposure_merge on): frames holds the E packed frames of
@@ -1362,6 +1392,7 @@ def camera_isp(name: str, dtype=types.f32):
             two calls above.
             keep_images=True returns `(outputs, images)`, the images holding what the reference leaves in them (p,
             camera_isp.py:211); by default only the outputs are returned, as the bench's Processor does.
+            local_tonemap= on always takes the two calls.
             defects: None, or one entry per frame (a DefectMap or None); any map takes the two calls, the load with
             `defects=`.  undistort: the same for lenses (a LensDistortion or None per frame).  history: with
             temporal_denoise on (always the two calls), one TemporalHistory per frame."""
@@ -1394,6 +1425,7 @@ def camera_isp(name: str, dtype=types.f32):
                      and self._highlights is None             # (highlight reconstruction: the two calls below)
                      and self._chromatic is None              # (chromatic aberration: the two calls below)
                      and self._temporal is None               # (temporal noise reduction: the two calls below)
+                     and self._ltm is None                    # (local tone mapping: the two calls below)
                      and history is None                      # (a history without it: the load below rejects it)
                      and defects is None                      # (defective pixels: the two calls below)
                      and undistort is None                    # (lens distortion: the two calls below)

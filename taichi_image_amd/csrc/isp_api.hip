@@ -23,6 +23,7 @@
 #include "isp_chroma_denoise.h"
 #include "isp_color_lut.h"
 #include "isp_local_contrast.h"
+#include "isp_local_tonemap.h"
 #include <mutex>
 #include <atomic>
 
@@ -1355,6 +1356,116 @@ extern "C" int mi_isp_merge_cfa(const void* const* in, void* out, int H, int W, 
   a.b[0].dst = out;
   return em::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? em::OUT_F16 : em::OUT_F32,
                     (hipStream_t)stream);
+}
+
+// ---- local tone mapping (isp_local_tonemap.h; DESIGN.md 3, "Local tone mapping") -------------------------------------
+static int32_t f32_bits(float v) {
+  int32_t b;
+  memcpy(&b, &v, sizeof(b));
+  return b;
+}
+
+// the settings checked, and the constants of the contract from them into a (H, W, the planes and the images are the
+// caller's)
+static int local_tonemap_settings(const mi_isp_local_tonemap* s, ltm::Args& a, const char* who) {
+  MI_REQUIRE(s, "%s: null local_tonemap settings", who);
+  MI_REQUIRE(std::isfinite(s->strength) && s->strength >= 0.f && s->strength <= 1.f,
+             "%s: local_tonemap strength %g outside [0, 1]", who, (double)s->strength);
+  MI_REQUIRE(std::isfinite(s->white) && s->white > 0.f, "%s: local_tonemap white %g must be finite and > 0", who,
+             (double)s->white);
+  MI_REQUIRE(std::isnormal(s->floor) && s->floor > 0.f && s->floor < s->white,
+             "%s: local_tonemap floor %g must be a normal f32 within (0, white = %g)", who, (double)s->floor, (double)s->white);
+  MI_REQUIRE((double)s->white / (double)s->floor <= 16777216.0, "%s: local_tonemap white / floor = %g above 2^24", who,
+             (double)s->white / (double)s->floor);
+  MI_REQUIRE(std::isfinite(s->anchor) && s->anchor >= s->floor && s->anchor <= s->white,
+             "%s: local_tonemap anchor %g outside [floor = %g, white = %g]", who, (double)s->anchor, (double)s->floor,
+             (double)s->white);
+  MI_REQUIRE(s->cell == 8 || s->cell == 16 || s->cell == 32 || s->cell == 64, "%s: local_tonemap cell %d not 8, 16, 32 or 64",
+             who, (int)s->cell);
+  MI_REQUIRE(s->bins >= 2 && s->bins <= ltm::MAX_BINS, "%s: local_tonemap bins %d outside 2 .. %d", who, (int)s->bins,
+             ltm::MAX_BINS);
+  const int32_t fb = f32_bits(s->floor);
+  const int32_t span = (f32_bits(s->white) - fb) >> 12;
+  MI_REQUIRE(span >= 1, "%s: local_tonemap white %g within 2^-11 stops of floor %g", who, (double)s->white, (double)s->floor);
+  a.cell = s->cell;
+  a.cell_shift = s->cell == 8 ? 3 : (s->cell == 16 ? 4 : (s->cell == 32 ? 5 : 6));
+  a.bins = s->bins;
+  a.floor_v = s->floor; a.white = s->white; a.floor_bits = fb;
+  a.zs = (float)((double)(s->bins - 1) / (double)span);
+  a.kq = (float)((double)s->strength * 4096.0);
+  a.la = (float)((f32_bits(s->anchor) - fb) >> 12);
+  a.inv_cell = 1.0f / (float)s->cell;
+  return 0;
+}
+
+static int local_tonemap_shape(int H, int W, int dtype, const char* who) {
+  MI_REQUIRE(H >= 0 && W >= 0 && H <= ltm::MAX_SIDE && W <= ltm::MAX_SIDE, "%s: local_tonemap image %dx%d outside 0 .. %d", who,
+             H, W, ltm::MAX_SIDE);
+  MI_REQUIRE(dtype == MI_F16 || dtype == MI_F32, "%s: local_tonemap takes MI_F16 or MI_F32 images, got dtype %d", who, dtype);
+  return 0;
+}
+
+extern "C" size_t mi_isp_local_tonemap_workspace_bytes(int n, int H, int W, const mi_isp_local_tonemap* s) {
+  ltm::Args a = {};
+  if (n <= 0 || H <= 0 || W <= 0 || H > ltm::MAX_SIDE || W > ltm::MAX_SIDE ||
+      local_tonemap_settings(s, a, "local_tonemap_workspace_bytes"))
+    return 0;
+  return ltm::workspace_bytes(n, H, W, s->cell, s->bins);
+}
+
+extern "C" int mi_isp_local_tonemap_batch(void* const* images, int n, int H, int W, int dtype, const mi_isp_local_tonemap* s,
+                                          void* ws, void* stream) {
+  const char* who = "local_tonemap_batch";
+  ltm::Args a = {};
+  if (int rc = local_tonemap_settings(s, a, who)) return rc;
+  MI_REQUIRE(n >= 0, "%s: local_tonemap with %d images", who, n);
+  if (int rc = local_tonemap_shape(H, W, dtype, who)) return rc;
+  if (n == 0 || (size_t)H * (size_t)W == 0) return 0;
+  MI_REQUIRE(images, "%s: null local_tonemap image list", who);
+  MI_REQUIRE(ws && mi_aligned(ws, 16), "%s: local_tonemap workspace null or not 16-byte aligned", who);
+  for (int i = 0; i < n; ++i)
+    MI_REQUIRE(images[i] && mi_aligned(images[i], mi_dtype_size(dtype)),
+               "%s: local_tonemap image %d null or not aligned to its element", who, i);
+  a.H = H; a.W = W;
+  a.GH = (H + s->cell - 1) / s->cell; a.GW = (W + s->cell - 1) / s->cell;
+  a.plane = ltm::plane_elems(H, W, s->cell, s->bins);
+  uint32_t* base = static_cast<uint32_t*>(ws);
+  for (int i0 = 0; i0 < n; i0 += ltm::MAX_IMAGES) {
+    a.n_images = n - i0 < ltm::MAX_IMAGES ? n - i0 : ltm::MAX_IMAGES;
+    // the four planes of the workspace, n images each; this launch's images start at i0
+    a.cnt = base + (0 * (size_t)n + i0) * a.plane;
+    a.sum = base + (1 * (size_t)n + i0) * a.plane;
+    a.nb = reinterpret_cast<float*>(base + (2 * (size_t)n + i0) * a.plane);
+    a.sb = reinterpret_cast<float*>(base + (3 * (size_t)n + i0) * a.plane);
+    for (int i = 0; i < a.n_images; ++i) a.im[i] = images[i0 + i];
+    if (int rc = ltm::launch(a, dtype, 0, 2, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_local_tonemap_grids(const void* image, int H, int W, int dtype, const mi_isp_local_tonemap* s,
+                                          uint32_t* cnt, uint32_t* sum, float* nb, float* sb, void* stream) {
+  const char* who = "local_tonemap_grids";
+  ltm::Args a = {};
+  if (int rc = local_tonemap_settings(s, a, who)) return rc;
+  if (int rc = local_tonemap_shape(H, W, dtype, who)) return rc;
+  if ((size_t)H * (size_t)W == 0) return 0;
+  MI_REQUIRE(image && mi_aligned(image, mi_dtype_size(dtype)), "%s: local_tonemap image null or not aligned to its element", who);
+  MI_REQUIRE(cnt && sum && nb && sb, "%s: null local_tonemap plane", who);
+  MI_REQUIRE(mi_aligned(cnt, 4) && mi_aligned(sum, 4) && mi_aligned(nb, 4) && mi_aligned(sb, 4),
+             "%s: local_tonemap plane not 4-byte aligned", who);
+  const size_t bytes = ltm::grid_nodes(H, W, s->cell, s->bins) * 4;
+  const uintptr_t p[4] = {(uintptr_t)cnt, (uintptr_t)sum, (uintptr_t)nb, (uintptr_t)sb};
+  for (int i = 0; i < 4; ++i)
+    for (int j = i + 1; j < 4; ++j)
+      MI_REQUIRE(p[i] + bytes <= p[j] || p[j] + bytes <= p[i], "%s: local_tonemap planes %d and %d overlap", who, i, j);
+  a.H = H; a.W = W;
+  a.GH = (H + s->cell - 1) / s->cell; a.GW = (W + s->cell - 1) / s->cell;
+  a.plane = 0;
+  a.n_images = 1;
+  a.cnt = cnt; a.sum = sum; a.nb = nb; a.sb = sb;
+  a.im[0] = const_cast<void*>(image);
+  return ltm::launch(a, dtype, 0, 1, (hipStream_t)stream);
 }
 
 // ---- output sharpening (isp_sharpen.h; DESIGN.md 3, "Output sharpening") ---------------------------------------------

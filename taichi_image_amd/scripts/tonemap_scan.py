@@ -216,6 +216,11 @@ def build_parser() -> argparse.ArgumentParser:
                       default=None)
     tone.add_argument("--temporal-threshold", dest="temporal_threshold", type=float, metavar="SIGMAS", default=None)
     tone.add_argument("--temporal-max-weight", dest="temporal_max_weight", type=float, metavar="W", default=None)
+    # local tone mapping (an extension): the loaded linear images times an edge-aware local gain (bilateral grid), in front of
+    # the global curve; STRENGTH 0 .. 1, the luminance floor of the logarithm (default 2^-10) and the cell side in pixels
+    tone.add_argument("--local-tonemap", dest="local_tonemap", type=float, metavar="STRENGTH", default=None)
+    tone.add_argument("--local-tonemap-floor", dest="local_tonemap_floor", type=float, metavar="FLOOR", default=None)
+    tone.add_argument("--local-tonemap-cell", dest="local_tonemap_cell", type=int, metavar="PIXELS", default=None)
     # output sharpening (an extension): an unsharp mask on the luma of the u8 outputs; AMOUNT 0 .. 8, the blur radius (1 or
     # 2), the coring threshold in luma codes and the halo clamp (luma codes; default: none)
     tone.add_argument("--sharpen", dest="sharpen", type=float, metavar="AMOUNT", default=None)
@@ -254,6 +259,7 @@ def main(argv=None) -> int:
     from ..highlights import Highlights
     from ..chromatic import ChromaticAberration
     from ..temporal import TemporalDenoise, TemporalHistory
+    from ..local_tonemap import LocalTonemap
     from ..sharpen import Sharpen
     from ..local_contrast import LocalContrast
     from ..chroma_denoise import ChromaDenoise
@@ -293,6 +299,13 @@ def main(argv=None) -> int:
                                    max_weight=0.75 if args.temporal_max_weight is None else args.temporal_max_weight)
     elif args.temporal_threshold is not None or args.temporal_max_weight is not None:
         raise ValueError("--temporal-threshold / --temporal-max-weight need --temporal-denoise GAIN READ_NOISE")
+    local_tonemap = None
+    if args.local_tonemap is not None:                              # (also before any frame is read)
+        local_tonemap = LocalTonemap(args.local_tonemap,
+                                     floor=2.0 ** -10 if args.local_tonemap_floor is None else args.local_tonemap_floor,
+                                     cell=32 if args.local_tonemap_cell is None else args.local_tonemap_cell)
+    elif args.local_tonemap_floor is not None or args.local_tonemap_cell is not None:
+        raise ValueError("--local-tonemap-floor / --local-tonemap-cell need --local-tonemap STRENGTH")
     sharpen = None
     if args.sharpen is not None:                                    # (also before any frame is read)
         sharpen = Sharpen(args.sharpen, radius=args.sharpen_radius, threshold=args.sharpen_threshold,
@@ -329,7 +342,8 @@ def main(argv=None) -> int:
                               black_level=black, white_level=args.white_level, lens_shading=shading,
                               auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen,
                               local_contrast=local_contrast, chroma_denoise=chroma_denoise, color_lut=color_lut,
-                              highlights=highlights, chromatic_aberration=chromatic, temporal_denoise=temporal)
+                              highlights=highlights, chromatic_aberration=chromatic, temporal_denoise=temporal,
+                              local_tonemap=local_tonemap)
     # temporal noise reduction: the state of each camera folder, for the whole scan
     histories = [TemporalHistory() if temporal is not None else None for _ in index.cameras]
     row_bytes = args.width * 3 // 2
