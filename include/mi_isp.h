@@ -657,6 +657,28 @@ int mi_isp_chroma_denoise_rgb_batch(const uint8_t* const* src_host, uint8_t* con
                                     const mi_isp_chroma_denoise* settings_host, void* stream);
 int mi_isp_chroma_denoise_yuv420_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
                                        const mi_isp_chroma_denoise* settings_host, void* stream);
+/* ---- luma noise reduction ("Luma noise reduction") ---------------------------------------------------------
+ * An edge-preserving mean of the luma over a (2r + 1)^2 window of a u8 image, in integer arithmetic: the output is the
+ * contract's bit for bit.  All values signed integers, >> arithmetic, // floor division; t0 = threshold and t1 =
+ * threshold_bright (0 .. 255 luma codes), S = strength_q6 (the strength times 64, 0 .. 64), r = radius (1, 2 or 3).  Per
+ * pixel p:
+ *   L = (77 R + 150 G + 29 B + 128) >> 8;  T = t0 + (((t1 - t0) L(p) + 128) >> 8)
+ *   the taps q = p + (i, j), |i|, |j| <= r, INSIDE the image (a pixel outside it is no tap: no padding) with
+ *   |L(q) - L(p)| <= T;  n = their number (the centre always counts), s = the sum of their L
+ *   m = (2 s + n) // (2 n);  delta = (S (m - L(p)) + 32) >> 6;  out_c = clamp(I_c + delta, 0, 255) for c = R, G, B
+ *  - mi_isp_luma_denoise_rgb_batch: n interleaved H x W x 3 images of one geometry, one launch per 32 images.
+ *  - mi_isp_luma_denoise_yuv420_batch: n planar YUV 4:2:0 images (H * 3 / 2 rows of W bytes; H, W of the Y plane, both
+ *    even): the filter with L = Y, out = clamp(Y + delta, 0, 255); the chroma rows are copied.
+ * src_host / dst_host: n device pointers each, read on the host.  The stencil cannot run in place: src[i] != dst[i], and
+ * no output may overlap an input or another output.  Host-side checks before any launch (error text names
+ * "luma_denoise"): the settings' ranges, n >= 0, H, W >= 0 (both even for the planar form), NULL pointers, src == dst,
+ * overlapping images.  n == 0 and H * W == 0 are successful no-ops.  No host synchronisation; the launches run on
+ * `stream`. */
+typedef struct { int32_t radius, threshold, threshold_bright, strength_q6; } mi_isp_luma_denoise;
+int mi_isp_luma_denoise_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                                  const mi_isp_luma_denoise* settings_host, void* stream);
+int mi_isp_luma_denoise_yuv420_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
+                                     const mi_isp_luma_denoise* settings_host, void* stream);
 /* ---- 3D colour LUT ("Colour LUT") --------------------------------------------------------------------------
  * Tetrahedral interpolation in an N x N x N table on interleaved u8 RGB images, in integer arithmetic: the output is the
  * contract's bit for bit.  The table T[r][g][b] holds the output colour (u8 R, G, B) at input (255 r, 255 g, 255 b) / (N - 1);

@@ -6,7 +6,7 @@ mirror the modules of uc-vision/taichi_image; every op dispatches through ctypes
 libmi355_isp.so (hand-written HIP for gfx950).  There is no CPU fallback.
 """
 from . import types  # noqa: F401
-from . import packed, bayer, interpolate, tonemap, camera_isp, pipeline, distributed, color, ingest, defects, lens, white_balance, denoise, sharpen, local_contrast, chroma_denoise, color_lut, highlights, chromatic, temporal, exposure_merge, local_tonemap  # noqa: F401
+from . import packed, bayer, interpolate, tonemap, camera_isp, pipeline, distributed, color, ingest, defects, lens, white_balance, denoise, sharpen, local_contrast, chroma_denoise, luma_denoise, color_lut, highlights, chromatic, temporal, exposure_merge, local_tonemap  # noqa: F401
 from .bayer import BayerPattern  # noqa: F401
 from .interpolate import ImageTransform  # noqa: F401
 from .camera_isp import Camera16, Camera32  # noqa: F401
@@ -17,6 +17,7 @@ from .denoise import RawDenoise  # noqa: F401
 from .sharpen import Sharpen  # noqa: F401
 from .local_contrast import LocalContrast  # noqa: F401
 from .chroma_denoise import ChromaDenoise  # noqa: F401
+from .luma_denoise import LumaDenoise  # noqa: F401
 from .color_lut import ColorLut  # noqa: F401
 from .highlights import Highlights  # noqa: F401
 from .chromatic import ChromaticAberration  # noqa: F401

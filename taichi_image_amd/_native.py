@@ -104,6 +104,12 @@ class ChromaDenoise(ctypes.Structure):
     _fields_ = [("radius", c_int32), ("luma_threshold", c_int32), ("chroma_threshold", c_int32), ("strength_q6", c_int32)]
 
 
+class LumaDenoise(ctypes.Structure):
+    """mi_isp_luma_denoise: the window radius in pixels (1, 2 or 3), the thresholds in the dark and in the bright (0 .. 255
+    luma codes) and the strength times 64 (0 .. 64)."""
+    _fields_ = [("radius", c_int32), ("threshold", c_int32), ("threshold_bright", c_int32), ("strength_q6", c_int32)]
+
+
 class ColorLut(ctypes.Structure):
     """mi_isp_color_lut: the table's points per axis (2 .. 65) and the strength times 64 (0 .. 64)."""
     _fields_ = [("n_points", c_int32), ("strength_q6", c_int32)]
@@ -235,6 +241,8 @@ SIGNATURES = {
     "mi_isp_chroma_denoise_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise), _P]),
     "mi_isp_chroma_denoise_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise),
                                                    _P]),
+    "mi_isp_luma_denoise_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(LumaDenoise), _P]),
+    "mi_isp_luma_denoise_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(LumaDenoise), _P]),
     "mi_isp_color_lut_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, _P, POINTER(ColorLut), _P]),
     "mi_isp_color_lut_rgb_batch_path": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, _P, POINTER(ColorLut), c_int,
                                                 _P]),

@@ -29,6 +29,7 @@ from . import exposure_merge as _em
 from . import lens as _lens
 from . import sharpen as _shp
 from . import chroma_denoise as _cdn
+from . import luma_denoise as _ydn
 from . import color_lut as _clut
 from . import local_contrast as _lc
 from . import local_tonemap as _ltm
@@ -296,7 +297,8 @@ def camera_isp(name: str, dtype=types.f32):
                      chromatic_aberration=None,
                      temporal_denoise=None,
                      exposure_merge=None,
-                     local_tonemap=None):
+                     local_tonemap=None,
+                     luma_denoise=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -321,6 +323,7 @@ def camera_isp(name: str, dtype=types.f32):
             sharpen = _shp.check_sharpen(sharpen)
             local_contrast = _lc.check_local_contrast(local_contrast)
             chroma_denoise = _cdn.check_chroma_denoise(chroma_denoise)
+            luma_denoise = _ydn.check_luma_denoise(luma_denoise)
             color_lut = _clut.check_color_lut(color_lut)
 
             self.bayer_pattern = bayer_pattern
@@ -394,6 +397,10 @@ def camera_isp(name: str, dtype=types.f32):
             # local contrast and sharpening, or None (the tonemaps run exactly as without it).  DESIGN.md 3, "Chroma noise
             # reduction".
             self._chroma_denoise = chroma_denoise
+            # luma noise reduction (an extension): the LumaDenoise applied to every u8 output of the tonemaps, behind chroma
+            # noise reduction and before local contrast and sharpening, or None (the tonemaps run exactly as without it).
+            # DESIGN.md 3, "Luma noise reduction".
+            self._luma_denoise = luma_denoise
             # 3D colour LUT (an extension): the ColorLut every u8 RGB output of the tonemaps is mapped through, in place,
             # before the other output operators, or None (the tonemaps run exactly as without it).  DESIGN.md 3, "Colour
             # LUT".
@@ -414,7 +421,7 @@ def camera_isp(name: str, dtype=types.f32):
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
                 highlights=None, chromatic_aberration=None, temporal_denoise=None, exposure_merge=None,
-                local_tonemap=None):
+                local_tonemap=None, luma_denoise=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -434,7 +441,8 @@ def camera_isp(name: str, dtype=types.f32):
             temporal_denoise (the extension): None leaves it, False turns it off, a TemporalDenoise replaces it (the
             histories are the caller's: reset() them when the new settings should not meet old frames).
             exposure_merge (the extension): None leaves it, False turns it off, an ExposureMerge replaces it.
-            local_tonemap (the extension): None leaves it, False turns it off, a LocalTonemap replaces it."""
+            local_tonemap (the extension): None leaves it, False turns it off, a LocalTonemap replaces it.
+            luma_denoise (the extension): None leaves it, False turns it off, a LumaDenoise replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -457,6 +465,8 @@ def camera_isp(name: str, dtype=types.f32):
                       else _lc.check_local_contrast(local_contrast))
             new_cdn = (None if chroma_denoise is None or chroma_denoise is False
                        else _cdn.check_chroma_denoise(chroma_denoise))
+            new_ydn = (None if luma_denoise is None or luma_denoise is False
+                       else _ydn.check_luma_denoise(luma_denoise))
             new_clut = None if color_lut is None or color_lut is False else _clut.check_color_lut(color_lut)
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
@@ -534,6 +544,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._chroma_denoise = None
             elif new_cdn is not None:
                 self._chroma_denoise = new_cdn
+            if luma_denoise is False:
+                self._luma_denoise = None
+            elif new_ydn is not None:
+                self._luma_denoise = new_ydn
             if color_lut is False:
                 self._color_lut = None
             elif new_clut is not None:
@@ -806,6 +820,11 @@ def camera_isp(name: str, dtype=types.f32):
             return self._chroma_denoise
 
         @property
+        def luma_denoise(self) -> Optional[_ydn.LumaDenoise]:
+            """The LumaDenoise the tonemaps apply to their u8 outputs, or None."""
+            return self._luma_denoise
+
+        @property
         def color_lut(self) -> Optional[_clut.ColorLut]:
             """The ColorLut the tonemaps map their u8 RGB outputs through, or None."""
             return self._color_lut
@@ -814,12 +833,15 @@ def camera_isp(name: str, dtype=types.f32):
             """The u8 outputs of a tonemap as the caller gets them: the colour LUT, in place on `outputs` (the tonemap's
             own freshly allocated RGB tensors; planar YUV outputs have been through it before their conversion:
             tonemap_reinhard_yuv420), then chroma noise reduction (a stencil: new tensors, which take the place of
-            `outputs`), then local contrast, in place on those, then sharpening; with none set, `outputs` themselves.
-            DESIGN.md 3, "Colour LUT", "Chroma noise reduction", "Local contrast" and "Output sharpening"."""
+            `outputs`), then luma noise reduction (another stencil, likewise), then local contrast, in place on those,
+            then sharpening; with none set, `outputs` themselves.  DESIGN.md 3, "Colour LUT", "Chroma noise reduction",
+            "Luma noise reduction", "Local contrast" and "Output sharpening"."""
             if self._color_lut is not None and outputs and not yuv420:
                 _clut.apply(outputs, self._color_lut, inplace=True)
             if self._chroma_denoise is not None and outputs:
                 outputs = _cdn.apply(outputs, self._chroma_denoise, yuv420)
+            if self._luma_denoise is not None and outputs:
+                outputs = _ydn.apply(outputs, self._luma_denoise, yuv420)
             if self._local_contrast is not None and outputs:
                 _lc.apply(outputs, self._local_contrast, yuv420, inplace=True)
             return self._sharpened(outputs, yuv420)
@@ -1350,7 +1372,8 @@ def camera_isp(name: str, dtype=types.f32):
             With sharpen= set, the Y plane of each YUV image is sharpened (sharpen.unsharp_mask_yuv420), which is not the
             YUV image of a sharpened RGB output; local_contrast= likewise equalises the Y plane
             (local_contrast.clahe_yuv420), and chroma_denoise= filters the U and V planes
-            (chroma_denoise.chroma_denoise_yuv420), before both.  A 3D LUT has no planar form: with color_lut= set the RGB
+            (chroma_denoise.chroma_denoise_yuv420) and luma_denoise= the Y plane (luma_denoise.luma_denoise_yuv420), before
+            both.  A 3D LUT has no planar form: with color_lut= set the RGB
             outputs are written, mapped through the table and converted (the unfused branch), then the planar operators
             run."""
             from . import color

@@ -21,6 +21,7 @@
 #include "isp_exposure_merge.h"
 #include "isp_sharpen.h"
 #include "isp_chroma_denoise.h"
+#include "isp_luma_denoise.h"
 #include "isp_color_lut.h"
 #include "isp_local_contrast.h"
 #include "isp_local_tonemap.h"
@@ -1634,6 +1635,70 @@ extern "C" int mi_isp_chroma_denoise_rgb_batch(const uint8_t* const* src, uint8_
 extern "C" int mi_isp_chroma_denoise_yuv420_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
                                                   const mi_isp_chroma_denoise* settings, void* stream) {
   return chroma_denoise_impl(src, dst, n, H, W, settings, false, stream, "chroma_denoise_yuv420_batch");
+}
+
+// ---- luma noise reduction (isp_luma_denoise.h; DESIGN.md 3, "Luma noise reduction") -----------------------------------
+// n u8 images of one geometry (rgb: H x W x 3; else planar YUV 4:2:0 with an H x W Y plane, whose chroma rows are copied):
+// every image's pointers in the kernel arguments, 32 per launch
+static int luma_denoise_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                             const mi_isp_luma_denoise* s, bool rgb, void* stream, const char* who) {
+  MI_REQUIRE(s, "%s: null luma_denoise settings", who);
+  MI_REQUIRE(s->radius >= 1 && s->radius <= 3, "%s: luma_denoise radius %d (1, 2 or 3)", who, (int)s->radius);
+  MI_REQUIRE(s->threshold >= 0 && s->threshold <= 255, "%s: luma_denoise threshold %d outside 0 .. 255", who,
+             (int)s->threshold);
+  MI_REQUIRE(s->threshold_bright >= 0 && s->threshold_bright <= 255, "%s: luma_denoise threshold_bright %d outside 0 .. 255",
+             who, (int)s->threshold_bright);
+  MI_REQUIRE(s->strength_q6 >= 0 && s->strength_q6 <= 64, "%s: luma_denoise strength_q6 %d outside 0 .. 64", who,
+             (int)s->strength_q6);
+  MI_REQUIRE(n >= 0, "%s: luma_denoise with %d images", who, n);
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad luma_denoise shape %dx%d", who, H, W);
+  // (one 256-thread block per tile: the launch's work-items per image must stay below 2^32)
+  MI_REQUIRE(H < (1 << 22) && W < (1 << 24) &&
+                 (uint64_t)((W + ydn::TILE_W - 1) / ydn::TILE_W) * (uint64_t)((H + ydn::TILE_H - 1) / ydn::TILE_H) < (1u << 24),
+             "%s: luma_denoise image %dx%d too large", who, H, W);
+  MI_REQUIRE(rgb || (H % 2 == 0 && W % 2 == 0),
+             "%s: the Y plane of a luma_denoise YUV 4:2:0 image must have even sides, got %dx%d", who, H, W);
+  MI_REQUIRE(src && dst, "%s: null luma_denoise image list", who);
+  if (n == 0 || (size_t)H * (size_t)W == 0) return 0;
+  const size_t bytes = rgb ? (size_t)H * W * 3 : (size_t)H * W * 3 / 2;
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && dst[i], "%s: luma_denoise image %d has a null pointer", who, i);
+    MI_REQUIRE(src[i] != dst[i], "%s: luma_denoise image %d: the filter cannot run in place", who, i);
+  }
+  // a written image overlaps no read image and no other written image
+  for (int i = 0; i < n; ++i) {
+    const uintptr_t d = (uintptr_t)dst[i];
+    for (int j = 0; j < n; ++j) {
+      const uintptr_t sj = (uintptr_t)src[j], dj = (uintptr_t)dst[j];
+      MI_REQUIRE(d + bytes <= sj || sj + bytes <= d, "%s: luma_denoise output %d overlaps input %d", who, i, j);
+      MI_REQUIRE(i == j || d + bytes <= dj || dj + bytes <= d, "%s: luma_denoise outputs %d and %d overlap", who, i, j);
+    }
+  }
+  ydn::Args a = {};
+  a.H = H; a.W = W;
+  a.t0 = s->threshold; a.t1 = s->threshold_bright; a.strength_q6 = s->strength_q6;
+  for (int i0 = 0; i0 < n; i0 += ydn::MAX_IMAGES) {
+    a.n_images = n - i0 < ydn::MAX_IMAGES ? n - i0 : ydn::MAX_IMAGES;
+    for (int i = 0; i < a.n_images; ++i) a.im[i] = {src[i0 + i], dst[i0 + i]};
+    if (int rc = ydn::launch(a, rgb, s->radius, (hipStream_t)stream)) return rc;
+    if (!rgb) {
+      shp::Args uv = {};                              // the chroma rows
+      uv.n_images = a.n_images;
+      for (int i = 0; i < a.n_images; ++i) uv.im[i] = a.im[i];
+      if (int rc = shp::launch_copy(uv, (size_t)H * W, (size_t)H * W / 2, (hipStream_t)stream)) return rc;
+    }
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_luma_denoise_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                             const mi_isp_luma_denoise* settings, void* stream) {
+  return luma_denoise_impl(src, dst, n, H, W, settings, true, stream, "luma_denoise_rgb_batch");
+}
+
+extern "C" int mi_isp_luma_denoise_yuv420_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
+                                                const mi_isp_luma_denoise* settings, void* stream) {
+  return luma_denoise_impl(src, dst, n, H, W, settings, false, stream, "luma_denoise_yuv420_batch");
 }
 
 // ---- 3D colour LUT (isp_color_lut.h; DESIGN.md 3, "Colour LUT") ------------------------------------------------------------

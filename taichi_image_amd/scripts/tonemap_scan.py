@@ -239,6 +239,13 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--chroma-denoise-radius", dest="chroma_denoise_radius", type=int, default=None)
     tone.add_argument("--chroma-denoise-thresholds", dest="chroma_denoise_thresholds", type=int, nargs=2,
                       metavar=("LUMA", "CHROMA"), default=None)
+    # luma noise reduction (an extension): an edge-preserving mean of the luma of the u8 outputs, behind chroma noise
+    # reduction and before local contrast and sharpening; STRENGTH 0 .. 1, the window radius in pixels (1, 2 or 3) and the
+    # thresholds in the dark and in the bright (luma codes)
+    tone.add_argument("--luma-denoise", dest="luma_denoise", type=float, metavar="STRENGTH", default=None)
+    tone.add_argument("--luma-denoise-radius", dest="luma_denoise_radius", type=int, default=None)
+    tone.add_argument("--luma-denoise-thresholds", dest="luma_denoise_thresholds", type=int, nargs=2,
+                      metavar=("DARK", "BRIGHT"), default=None)
     # 3D colour LUT (an extension): a .cube file every u8 output is mapped through (tetrahedral interpolation), before the
     # other output operators; STRENGTH 0 .. 1 blends between the input and the table's colour
     tone.add_argument("--color-lut", dest="color_lut", type=Path, metavar="FILE.cube", default=None)
@@ -263,6 +270,7 @@ def main(argv=None) -> int:
     from ..sharpen import Sharpen
     from ..local_contrast import LocalContrast
     from ..chroma_denoise import ChromaDenoise
+    from ..luma_denoise import LumaDenoise
     from ..color_lut import ColorLut
     args = build_parser().parse_args(argv)
     if args.scan is None and args.images is None:
@@ -325,6 +333,13 @@ def main(argv=None) -> int:
                                        args.chroma_denoise)
     elif args.chroma_denoise_radius is not None or args.chroma_denoise_thresholds is not None:
         raise ValueError("--chroma-denoise-radius / --chroma-denoise-thresholds need --chroma-denoise STRENGTH")
+    luma_denoise = None
+    if args.luma_denoise is not None:                               # (also before any frame is read)
+        t0, t1 = args.luma_denoise_thresholds or (6, 6)
+        luma_denoise = LumaDenoise(2 if args.luma_denoise_radius is None else args.luma_denoise_radius, t0, t1,
+                                   args.luma_denoise)
+    elif args.luma_denoise_radius is not None or args.luma_denoise_thresholds is not None:
+        raise ValueError("--luma-denoise-radius / --luma-denoise-thresholds need --luma-denoise STRENGTH")
     color_lut = None
     if args.color_lut is not None:                                  # (read and checked before any frame is read)
         color_lut = ColorLut.from_cube(args.color_lut, 1.0 if args.color_lut_strength is None else args.color_lut_strength)
@@ -343,7 +358,7 @@ def main(argv=None) -> int:
                               auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen,
                               local_contrast=local_contrast, chroma_denoise=chroma_denoise, color_lut=color_lut,
                               highlights=highlights, chromatic_aberration=chromatic, temporal_denoise=temporal,
-                              local_tonemap=local_tonemap)
+                              local_tonemap=local_tonemap, luma_denoise=luma_denoise)
     # temporal noise reduction: the state of each camera folder, for the whole scan
     histories = [TemporalHistory() if temporal is not None else None for _ in index.cameras]
     row_bytes = args.width * 3 // 2
