@@ -623,27 +623,32 @@ def camera_isp(name: str, dtype=types.f32):
                 float(1.0 - self.moving_alpha), self._awb_state.data_ptr(), self._awb_gains.data_ptr(),
                 _native.shading_arg(self._shading), self._awb_E.data_ptr(), _native.stream_ptr(self.device)))
 
+        def _awb_stats_cfa(self, src, h, w, mode, lv):
+            """With auto white balance on, the statistics of the h x w CFA src (mi_isp_load_convert mode `mode`, levels lv)
+            added to the pending sums, on the loads' stream; nothing with it off."""
+            if self._awb is not None:
+                _native.check(_native.lib().mi_isp_awb_stats_cfa(
+                    src.data_ptr(), h, w, mode, lv, _native.shading_arg(self._shading), float(self._awb.clip),
+                    float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(),
+                    _native.stream_ptr(self.device)))
+
+        def _awb_stats_packed(self, srcs, h, w, bits, ids_format, lv):
+            """The same for the packed frames srcs of one shape, in one launch."""
+            if self._awb is not None:
+                _native.check(_native.lib().mi_isp_awb_stats_packed(
+                    _native.ptr_array(srcs), len(srcs), h, w, bits, int(bool(ids_format)), lv,
+                    _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor),
+                    int(self._awb.stride), self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
+
+        def _raw_stage_on(self):
+            """True when a loader of single frames goes through _raw_chain."""
+            return (self._highlights is not None or self._chromatic is not None or self._temporal is not None
+                    or self._raw_denoise is not None)
+
         @property
         def raw_denoise(self) -> Optional[_dn.RawDenoise]:
             """The RawDenoise the loaders apply, or None."""
             return self._raw_denoise
-
-        def _denoised(self, srcs, h, w, kind, ids_format, lv, maps):
-            """The raw noise reduction route: the filtered, gained, cast work-dtype CFAs of the raw frames srcs (one shape,
-            mi_isp_denoise_raw_batch source kind `kind`) in one launch, then the defect fix-up of each frame with a map (maps:
-            one DefectMap or None per frame).  DESIGN.md 3, "Raw noise reduction"."""
-            L = _native.lib()
-            stream = _native.stream_ptr(self.device)
-            cfas = [torch.empty((h, w), dtype=torch_dtype, device=self.device) for _ in srcs]
-            args = [None if m is None else m._arg(self.device) for m in maps]       # (kept alive through the call)
-            p_maps = (ctypes.c_void_p * len(maps))(*[None if a is None else ctypes.addressof(a) for a in args])
-            _native.check(L.mi_isp_denoise_raw_batch(
-                _native.ptr_array(srcs), _native.ptr_array(cfas), len(srcs), h, w, kind, int(bool(ids_format)), dtype.code,
-                lv, _native.shading_arg(self._applied_shading()), p_maps, self._raw_denoise._arg(), stream))
-            for cfa, a in zip(cfas, args):
-                if a is not None:
-                    _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, a, stream))
-            return cfas
 
         @property
         def highlights(self) -> Optional[_hl.Highlights]:
@@ -658,32 +663,6 @@ def camera_isp(name: str, dtype=types.f32):
             if self.correct_colors:
                 return self._highlights._arg(_hl.check_white_balance(self.white_balance))
             return self._highlights._arg()
-
-        def _reconstructed(self, srcs, h, w, kind, ids_format, lv, maps):
-            """The highlight reconstruction route: the reconstructed, gained, cast work-dtype CFAs of the raw frames srcs
-            (one shape, mi_isp_highlights_raw_batch source kind `kind`) in one launch, then the defect fix-up of each frame
-            with a map (maps: one DefectMap or None per frame).  With raw noise reduction on as well the launch writes the
-            plain f32 y, which the filter then takes as an f32 source with the same grid and maps.  DESIGN.md 3,
-            "Highlight reconstruction"."""
-            L = _native.lib()
-            stream = _native.stream_ptr(self.device)
-            plain = self._raw_denoise is not None
-            cfas = [torch.empty((h, w), dtype=torch_dtype, device=self.device) for _ in srcs]
-            ys = [torch.empty((h, w), dtype=torch.float32, device=self.device) for _ in srcs] if plain else cfas
-            args = [None if m is None else m._arg(self.device) for m in maps]       # (kept alive through the call)
-            p_maps = (ctypes.c_void_p * len(maps))(*[None if a is None else ctypes.addressof(a) for a in args])
-            sh = _native.shading_arg(self._applied_shading())
-            _native.check(L.mi_isp_highlights_raw_batch(
-                _native.ptr_array(srcs), _native.ptr_array(ys), len(srcs), h, w, kind, int(bool(ids_format)), dtype.code,
-                self._demosaic_pattern.value, lv, None if plain else sh, p_maps, self._highlights_arg(), int(plain), stream))
-            if plain:
-                _native.check(L.mi_isp_denoise_raw_batch(
-                    _native.ptr_array(ys), _native.ptr_array(cfas), len(srcs), h, w, _native.MI_RAW_32F, 0, dtype.code,
-                    None, sh, p_maps, self._raw_denoise._arg(), stream))
-            for cfa, a in zip(cfas, args):
-                if a is not None:
-                    _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, a, stream))
-            return cfas
 
         @property
         def chromatic_aberration(self) -> Optional[_ca.ChromaticAberration]:
@@ -711,21 +690,27 @@ def camera_isp(name: str, dtype=types.f32):
                                  f"(load_packed12_bracket, load_packed16_bracket, load_16u_bracket, load_16f_bracket, "
                                  f"load_32f_bracket, load_packed12_bracket_batch, load_packed16_bracket_batch)")
 
-        def _corrected(self, srcs, h, w, kind, ids_format, lv, maps, hists=None, brackets=None):
-            """The route of the raw chain with exposure merge, chromatic aberration or temporal noise reduction on: the raw
-            stages that are on, in the order exposure merge, highlight reconstruction, chromatic aberration, temporal noise
-            reduction, raw noise reduction, one launch each for the raw frames srcs (one shape, source kind `kind`; with
-            exposure merge on brackets holds the E frames of each, and srcs their first), then the defect fix-up of
-            each frame with a map (maps: one DefectMap or None per frame).  A stage that is not the last writes the plain
-            f32 y, which the next takes as an f32 source without levels; the last applies the grid and the cast; all read
-            the same masks.  The temporal stage reads and writes the planes of hists (one checked TemporalHistory per
-            frame), which swap once its launch was issued; when it is not the last, its new history planes are the y the
-            next stage reads.  DESIGN.md 3, "Exposure merge", "Chromatic aberration" and "Temporal noise reduction"."""
+        def _map_args(self, maps):
+            """(the mi_isp_defects of each DefectMap of maps, None for None; the array of their addresses for a _batch
+            entry point).  The first is what keeps the second's targets alive: hold it through the call."""
+            args = [None if m is None else m._arg(self.device) for m in maps]
+            return args, (ctypes.c_void_p * len(maps))(*[None if a is None else ctypes.addressof(a) for a in args])
+
+        def _raw_chain(self, srcs, h, w, kind, ids_format, lv, maps, hists=None, brackets=None):
+            """The raw chain, the one route of every loader with a raw stage on: the raw stages that are on, in the order
+            exposure merge, highlight reconstruction, chromatic aberration, temporal noise reduction, raw noise reduction,
+            one launch each for the raw frames srcs (one shape, source kind `kind`; with exposure merge on brackets holds
+            the E frames of each, and srcs their first), then the defect fix-up of each frame with a map (maps: one
+            DefectMap or None per frame).  A stage that is not the last writes the plain f32 y, which the next takes as an
+            f32 source without levels; the last applies the grid and the cast; all read the same masks.  The temporal
+            stage reads and writes the planes of hists (one checked TemporalHistory per frame), which swap once its launch
+            was issued; when it is not the last, its new history planes are the y the next stage reads.  DESIGN.md 3, "Raw
+            noise reduction", "Highlight reconstruction", "Exposure merge", "Chromatic aberration" and "Temporal noise
+            reduction"."""
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             n = len(srcs)
-            args = [None if m is None else m._arg(self.device) for m in maps]       # (kept alive through the call)
-            p_maps = (ctypes.c_void_p * len(maps))(*[None if a is None else ctypes.addressof(a) for a in args])
+            args, p_maps = self._map_args(maps)
             sh = _native.shading_arg(self._applied_shading())
             pattern = self._demosaic_pattern.value
             ids = int(bool(ids_format))
@@ -894,13 +879,8 @@ def camera_isp(name: str, dtype=types.f32):
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             src = image.to(self.device).contiguous()
-            if self._chromatic is not None or self._temporal is not None:
-                # chromatic aberration or temporal noise reduction, among the raw stages that are on
-                cfa = self._corrected([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm], hists)[0]
-            elif self._highlights is not None:           # highlight reconstruction (then raw noise reduction, if on)
-                cfa = self._reconstructed([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
-            elif self._raw_denoise is not None:          # raw noise reduction: the filtered CFA, its defects fixed up
-                cfa = self._denoised([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])[0]
+            if self._raw_stage_on():                     # the raw stages that are on: one launch each
+                cfa = self._raw_chain([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm], hists)[0]
             else:
                 cfa = torch.empty((h, w), dtype=torch_dtype, device=self.device)
                 # (NULL levels and a NULL grid are exactly the plain mi_isp_load_convert, include/mi_isp.h)
@@ -908,10 +888,7 @@ def camera_isp(name: str, dtype=types.f32):
                                                             _native.shading_arg(self._applied_shading()), stream))
                 if dm is not None:                       # defective pixels: the CFA's listed sites, in place
                     _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, dm._arg(self.device), stream))
-            if self._awb is not None:                    # auto white balance: the statistics of the source
-                _native.check(L.mi_isp_awb_stats_cfa(
-                    src.data_ptr(), h, w, mode, lv, _native.shading_arg(self._shading), float(self._awb.clip),
-                    float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(), stream))
+            self._awb_stats_cfa(src, h, w, mode, lv)     # auto white balance: the statistics of the source
             return self._tone_mapped([self._process_image(cfa, lens)])[0]
 
         def load_16u(self, image, defects=None, undistort=None, history=None):
@@ -962,8 +939,7 @@ def camera_isp(name: str, dtype=types.f32):
                     ccm, dtype.code, hd, wd, float(scale), None if subs is None else subs[0].data_ptr(), st, lv, sh,
                     maps[0]._arg(self.device), lists[0][0].data_ptr(), lists[0][1], stream))
                 return
-            args = [None if m is None else m._arg(self.device) for m in maps]       # (kept alive through the call)
-            p_maps = (ctypes.c_void_p * len(maps))(*[None if a is None else ctypes.addressof(a) for a in args])
+            args, p_maps = self._map_args(maps)
             p_lists = (ctypes.c_void_p * len(maps))(*[None if l is None else l[0].data_ptr() for l in lists])
             counts = (ctypes.c_int32 * len(maps))(*[0 if l is None else l[1] for l in lists])
             _native.check(L.mi_isp_defects_fix_packed_batch(
@@ -1018,16 +994,11 @@ def camera_isp(name: str, dtype=types.f32):
                                  f"{type(history).__name__}")
             hists = _tn.check_histories(self._temporal, history, len(frames), (h, w), self.device)
             srcs = [d.to(self.device).contiguous() for d in frames]
-            if (self._chromatic is not None or self._temporal is not None or self._highlights is not None
-                    or self._raw_denoise is not None):
+            if self._raw_stage_on():
                 # the raw stages - highlight reconstruction, chromatic aberration, temporal noise reduction, raw noise
                 # reduction - that are on: one launch each, then per frame
                 kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
-                if self._chromatic is not None or self._temporal is not None:
-                    cfas = self._corrected(srcs, h, w, kind, ids_format, lv, maps, hists)
-                else:
-                    route = self._reconstructed if self._highlights is not None else self._denoised
-                    cfas = route(srcs, h, w, kind, ids_format, lv, maps)
+                cfas = self._raw_chain(srcs, h, w, kind, ids_format, lv, maps, hists)
                 rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
             elif lenses.count(None) < len(lenses):       # (some frame has a lens)
                 # lens distortion: the frames without a lens as the call without lenses, the others loaded at full
@@ -1042,11 +1013,7 @@ def camera_isp(name: str, dtype=types.f32):
                 rgbs = [out[i] for i in range(len(srcs))]
             else:
                 rgbs = self._load_frames(srcs, h, w, bits, ids_format, lv, maps, batch)
-            if self._awb is not None:                    # auto white balance: the statistics of the sources
-                _native.check(_native.lib().mi_isp_awb_stats_packed(
-                    _native.ptr_array(srcs), len(srcs), h, w, bits, int(bool(ids_format)), lv,
-                    _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor),
-                    int(self._awb.stride), self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
+            self._awb_stats_packed(srcs, h, w, bits, ids_format, lv)     # auto white balance: the statistics of the sources
             return self._tone_mapped(rgbs)
 
         def _load_frames(self, srcs, h, w, bits, ids_format, lv, maps, batch, full=False):
@@ -1154,12 +1121,8 @@ def camera_isp(name: str, dtype=types.f32):
                 self._chromatic.check_shape((h, w))
             hists = _tn.check_histories(self._temporal, None if history is None else [history], 1, (h, w), self.device)
             srcs = [f.to(self.device).contiguous() for f in frames]
-            cfa = self._corrected([srcs[0]], h, w, _native.MI_RAW_16U + mode, False, lv, [dm], hists, brackets=[srcs])[0]
-            if self._awb is not None:                    # auto white balance: the statistics of frame 0 (the output's units)
-                _native.check(_native.lib().mi_isp_awb_stats_cfa(
-                    srcs[0].data_ptr(), h, w, mode, lv, _native.shading_arg(self._shading), float(self._awb.clip),
-                    float(self._awb.floor), int(self._awb.stride), self._awb_pending.data_ptr(),
-                    _native.stream_ptr(self.device)))
+            cfa = self._raw_chain([srcs[0]], h, w, _native.MI_RAW_16U + mode, False, lv, [dm], hists, brackets=[srcs])[0]
+            self._awb_stats_cfa(srcs[0], h, w, mode, lv)   # auto white balance: the statistics of frame 0 (the output's units)
             return self._tone_mapped([self._process_image(cfa, lens)])[0]
 
         def load_16u_bracket(self, frames, defects=None, undistort=None, history=None):
@@ -1209,13 +1172,9 @@ def camera_isp(name: str, dtype=types.f32):
             srcs = [[f.to(self.device).contiguous() for f in b] for b in brackets]
             first = [b[0] for b in srcs]
             kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
-            cfas = self._corrected(first, h, w, kind, ids_format, lv, maps, hists, brackets=srcs)
+            cfas = self._raw_chain(first, h, w, kind, ids_format, lv, maps, hists, brackets=srcs)
             rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
-            if self._awb is not None:                    # auto white balance: the statistics of each bracket's frame 0
-                _native.check(_native.lib().mi_isp_awb_stats_packed(
-                    _native.ptr_array(first), n, h, w, bits, int(bool(ids_format)), lv,
-                    _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor),
-                    int(self._awb.stride), self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
+            self._awb_stats_packed(first, h, w, bits, ids_format, lv)    # auto white balance: each bracket's frame 0
             return self._tone_mapped(rgbs)
 
         def load_packed12_bracket(self, frames, ids_format=False, defects=None, undistort=None, history=None):

@@ -655,6 +655,77 @@ extern "C" int mi_isp_awb_rebuild(int pattern, float* gains, const mi_isp_shadin
   return awb::launch_update(u, (hipStream_t)stream);
 }
 
+// ---- the raw stages' shared source (isp_raw_source.h) ----------------------------------------------------------------
+// How a stage words the errors of the shared checks, "<who>: <prefix><text>": its noun, the prefix (raw noise reduction has
+// none) and what its frame lists count.  The texts are the entry points' behaviour: tests/test_raw_stage_errors_cpu.py.
+struct RawStage { const char* noun; const char* prefix; const char* item; };
+static const RawStage kDenoise = {"denoise", "", "frame"}, kHighlights = {"highlights", "highlights: ", "frame"},
+                      kChromatic = {"chromatic aberration", "chromatic aberration: ", "frame"},
+                      kTemporal = {"temporal", "temporal: ", "frame"}, kMerge = {"exposure merge", "exposure merge: ", "bracket"};
+
+static int raw_geometry(int H, int W, int work_dtype, const RawStage& st, const char* who) {
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad %s shape %dx%d", who, st.noun, H, W);
+  MI_REQUIRE(H < (1 << 22) && W < (1 << 24), "%s: %s frame %dx%d too large", who, st.noun, H, W);
+  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: %s work dtype must be f16 or f32", who, st.noun);
+  return 0;
+}
+
+static int raw_kind(int kind, const RawStage& st, const char* who) {
+  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad %s source kind %d", who, st.noun, kind);
+  return 0;
+}
+
+// the rules that need no levels: the plain f32 output takes no grid, packed frames are even, IDS is a packed-12 layout
+static int raw_source_rules(int H, int W, int kind, int ids_format, const mi_isp_shading* shading, int plain,
+                            const RawStage& st, const char* who) {
+  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
+  MI_REQUIRE(!plain || !shading, "%s: %sthe plain f32 output takes no shading grid", who, st.prefix);
+  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: %spacked frames must be even size, got %dx%d", who, st.prefix, H, W);
+  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: %sthe IDS layout is a packed-12 layout", who, st.prefix);
+  return 0;
+}
+
+// fills a (the shape, the decode of `kind` under the levels, the grid, mask_w) and src_kind, and checks the n defect maps
+static int raw_source_setup(raw::Source& a, int& src_kind, int H, int W, int kind, int ids_format,
+                            const mi_isp_levels* levels, const mi_isp_shading* shading,
+                            const mi_isp_defects* const* defects, int n, const RawStage& st, const char* who) {
+  a.H = H; a.W = W;
+  if (kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16) {
+    tile::Params p = {};
+    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
+    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
+    if (int rc = apply_levels(p, levels, bits, who)) return rc;
+    for (int s = 0; s < 4; ++s) {                     // the per-site decode of the shading path (apply_levels_shading)
+      a.black[s] = p.levels ? p.lv_black[s] : 0;
+      a.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
+    }
+    src_kind = bits == 16 ? raw::SRC_P16 : (ids_format ? raw::SRC_P12_IDS : raw::SRC_P12);
+  } else {
+    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
+      MI_REQUIRE(kind == MI_RAW_16U, "%s: %slevels apply to u16 codes only (source kind %d)", who, st.prefix, kind);
+      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
+      for (int s = 0; s < 4; ++s) a.k[s] = (float)(levels->white - levels->black[s]);
+      a.levels = 1;
+    }
+    src_kind = kind == MI_RAW_16U ? raw::SRC_U16 : (kind == MI_RAW_32F ? raw::SRC_F32 : raw::SRC_U16F);
+  }
+  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
+  a.mask_w = (W + 31) / 32;
+  for (int i = 0; i < n; ++i)
+    if (defects && defects[i]) {
+      MI_REQUIRE(defects[i]->n >= 0, "%s: %snegative defect count %d", who, st.prefix, (int)defects[i]->n);
+      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: %s%s %d: defects without a mask", who, st.prefix, st.item,
+                 i);
+    }
+  return 0;
+}
+
+// the mask a kernel reads for frame i: a map with no listed pixel needs none
+static const uint32_t* mask_of(const mi_isp_defects* const* defects, int i) {
+  const mi_isp_defects* m = defects ? defects[i] : nullptr;
+  return (m && m->n > 0) ? m->mask_dev : nullptr;
+}
+
 // ---- raw noise reduction (isp_denoise.h; DESIGN.md 3, "Raw noise reduction") ----------------------------------------
 // the filter's settings, checked on the host; fills the filter members of a
 static int denoise_settings(dn::Args& a, const mi_isp_denoise* d, const char* who) {
@@ -676,63 +747,26 @@ static int denoise_settings(dn::Args& a, const mi_isp_denoise* d, const char* wh
   return 0;
 }
 
-static int denoise_geometry(int H, int W, int work_dtype, const char* who) {
-  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad denoise shape %dx%d", who, H, W);
-  MI_REQUIRE(H < (1 << 22) && W < (1 << 24), "%s: denoise frame %dx%d too large", who, H, W);
-  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: denoise work dtype must be f16 or f32", who);
-  return 0;
-}
-
 // n raw frames of one geometry: every frame's pointers (and defect mask) in the kernel arguments, 32 per launch
 static int denoise_raw_impl(const void* const* src, void* const* cfa, int n, int H, int W, int kind, int ids_format,
                             int work_dtype, const mi_isp_levels* levels, const mi_isp_shading* shading,
                             const mi_isp_defects* const* defects, const mi_isp_denoise* d, void* stream, const char* who) {
   dn::Args a = {};
   if (int rc = denoise_settings(a, d, who)) return rc;
-  if (int rc = denoise_geometry(H, W, work_dtype, who)) return rc;
-  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad denoise source kind %d", who, kind);
+  if (int rc = raw_geometry(H, W, work_dtype, kDenoise, who)) return rc;
+  if (int rc = raw_kind(kind, kDenoise, who)) return rc;
   MI_REQUIRE(n >= 0 && (src || n == 0) && (cfa || n == 0), "%s: null frame list", who);
   for (int i = 0; i < n; ++i) {
     MI_REQUIRE(src[i] && cfa[i], "%s: frame %d has a null pointer", who, i);
     MI_REQUIRE(src[i] != cfa[i], "%s: frame %d: the CFA must not overwrite its source", who, i);
   }
-  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
-  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: packed frames must be even size, got %dx%d", who, H, W);
-  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: the IDS layout is a packed-12 layout", who);
-  a.H = H; a.W = W;
+  if (int rc = raw_source_rules(H, W, kind, ids_format, shading, 0, kDenoise, who)) return rc;
   int src_kind;
-  if (packed) {
-    tile::Params p = {};
-    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
-    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
-    if (int rc = apply_levels(p, levels, bits, who)) return rc;
-    for (int s = 0; s < 4; ++s) {                     // the per-site decode of the shading path (apply_levels_shading)
-      a.black[s] = p.levels ? p.lv_black[s] : 0;
-      a.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
-    }
-    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
-  } else {
-    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
-      MI_REQUIRE(kind == MI_RAW_16U, "%s: levels apply to u16 codes only (source kind %d)", who, kind);
-      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
-      for (int s = 0; s < 4; ++s) a.k[s] = (float)(levels->white - levels->black[s]);
-      a.levels = 1;
-    }
-    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
-  }
-  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
-  a.mask_w = (W + 31) / 32;
-  for (int i = 0; i < n; ++i)
-    if (defects && defects[i]) {
-      MI_REQUIRE(defects[i]->n >= 0, "%s: negative defect count %d", who, (int)defects[i]->n);
-      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: frame %d: defects without a mask", who, i);
-    }
+  if (int rc = raw_source_setup(a, src_kind, H, W, kind, ids_format, levels, shading, defects, n, kDenoise, who))
+    return rc;
   for (int i0 = 0; i0 < n; i0 += dn::MAX_FRAMES) {
     a.n_frames = n - i0 < dn::MAX_FRAMES ? n - i0 : dn::MAX_FRAMES;
-    for (int i = 0; i < a.n_frames; ++i) {
-      const mi_isp_defects* m = defects ? defects[i0 + i] : nullptr;
-      a.f[i] = {src[i0 + i], cfa[i0 + i], (m && m->n > 0) ? m->mask_dev : nullptr};
-    }
+    for (int i = 0; i < a.n_frames; ++i) a.f[i] = {src[i0 + i], cfa[i0 + i], mask_of(defects, i0 + i)};
     if (int rc = dn::launch(a, src_kind, work_dtype, d->radius, (hipStream_t)stream)) return rc;
   }
   return 0;
@@ -759,13 +793,13 @@ extern "C" int mi_isp_denoise_cfa(const void* in, void* out, int H, int W, int d
   const char* who = "denoise_cfa";
   dn::Args a = {};
   if (int rc = denoise_settings(a, denoise, who)) return rc;
-  if (int rc = denoise_geometry(H, W, dtype, who)) return rc;
+  if (int rc = raw_geometry(H, W, dtype, kDenoise, who)) return rc;
   MI_REQUIRE(in && out, "%s: null pointer", who);
   MI_REQUIRE(in != out, "%s: the output must not overwrite the input", who);
   a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
   a.n_frames = 1;
   a.f[0] = {in, out, nullptr};
-  return dn::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype, denoise->radius, (hipStream_t)stream);
+  return dn::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype, denoise->radius, (hipStream_t)stream);
 }
 
 // ---- highlight reconstruction (isp_highlights.h; DESIGN.md 3, "Highlight reconstruction") ----------------------------
@@ -790,13 +824,6 @@ static int highlights_settings(hl::Args& a, const mi_isp_highlights* h, int patt
   return 0;
 }
 
-static int highlights_geometry(int H, int W, int work_dtype, const char* who) {
-  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad highlights shape %dx%d", who, H, W);
-  MI_REQUIRE(H < (1 << 22) && W < (1 << 24), "%s: highlights frame %dx%d too large", who, H, W);
-  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: highlights work dtype must be f16 or f32", who);
-  return 0;
-}
-
 // n raw frames of one geometry: every frame's pointers (and defect mask) in the kernel arguments, 32 per launch
 static int highlights_raw_impl(const void* const* src, void* const* cfa, int n, int H, int W, int kind, int ids_format,
                                int work_dtype, int pattern, const mi_isp_levels* levels, const mi_isp_shading* shading,
@@ -804,8 +831,8 @@ static int highlights_raw_impl(const void* const* src, void* const* cfa, int n, 
                                const char* who) {
   hl::Args a = {};
   if (int rc = highlights_settings(a, h, pattern, who)) return rc;
-  if (int rc = highlights_geometry(H, W, work_dtype, who)) return rc;
-  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad highlights source kind %d", who, kind);
+  if (int rc = raw_geometry(H, W, work_dtype, kHighlights, who)) return rc;
+  if (int rc = raw_kind(kind, kHighlights, who)) return rc;
   MI_REQUIRE(n >= 0, "%s: highlights with %d frames", who, n);
   if (n == 0 || H == 0 || W == 0) return 0;
   MI_REQUIRE(src && cfa, "%s: highlights: null frame list", who);
@@ -813,45 +840,14 @@ static int highlights_raw_impl(const void* const* src, void* const* cfa, int n, 
     MI_REQUIRE(src[i] && cfa[i], "%s: highlights: frame %d has a null pointer", who, i);
     MI_REQUIRE(src[i] != cfa[i], "%s: highlights: frame %d: the CFA must not overwrite its source", who, i);
   }
-  MI_REQUIRE(!plain || !shading, "%s: highlights: the plain f32 output takes no shading grid", who);
-  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
-  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: highlights: packed frames must be even size, got %dx%d", who, H, W);
-  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: highlights: the IDS layout is a packed-12 layout", who);
-  a.H = H; a.W = W;
+  if (int rc = raw_source_rules(H, W, kind, ids_format, shading, plain, kHighlights, who)) return rc;
   int src_kind;
-  if (packed) {
-    tile::Params p = {};
-    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
-    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
-    if (int rc = apply_levels(p, levels, bits, who)) return rc;
-    for (int s = 0; s < 4; ++s) {                     // the per-site decode of the shading path (apply_levels_shading)
-      a.black[s] = p.levels ? p.lv_black[s] : 0;
-      a.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
-    }
-    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
-  } else {
-    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
-      MI_REQUIRE(kind == MI_RAW_16U, "%s: highlights: levels apply to u16 codes only (source kind %d)", who, kind);
-      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
-      for (int s = 0; s < 4; ++s) a.k[s] = (float)(levels->white - levels->black[s]);
-      a.levels = 1;
-    }
-    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
-  }
-  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
-  a.mask_w = (W + 31) / 32;
-  for (int i = 0; i < n; ++i)
-    if (defects && defects[i]) {
-      MI_REQUIRE(defects[i]->n >= 0, "%s: highlights: negative defect count %d", who, (int)defects[i]->n);
-      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: highlights: frame %d: defects without a mask", who, i);
-    }
+  if (int rc = raw_source_setup(a, src_kind, H, W, kind, ids_format, levels, shading, defects, n, kHighlights, who))
+    return rc;
   const int out = plain ? hl::OUT_PLAIN : (work_dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32);
   for (int i0 = 0; i0 < n; i0 += hl::MAX_FRAMES) {
     a.n_frames = n - i0 < hl::MAX_FRAMES ? n - i0 : hl::MAX_FRAMES;
-    for (int i = 0; i < a.n_frames; ++i) {
-      const mi_isp_defects* m = defects ? defects[i0 + i] : nullptr;
-      a.f[i] = {src[i0 + i], cfa[i0 + i], (m && m->n > 0) ? m->mask_dev : nullptr};
-    }
+    for (int i = 0; i < a.n_frames; ++i) a.f[i] = {src[i0 + i], cfa[i0 + i], mask_of(defects, i0 + i)};
     if (int rc = hl::launch(a, src_kind, out, (hipStream_t)stream)) return rc;
   }
   return 0;
@@ -878,14 +874,14 @@ extern "C" int mi_isp_highlights_cfa(const void* in, void* out, int H, int W, in
   const char* who = "highlights_cfa";
   hl::Args a = {};
   if (int rc = highlights_settings(a, highlights, pattern, who)) return rc;
-  if (int rc = highlights_geometry(H, W, dtype, who)) return rc;
+  if (int rc = raw_geometry(H, W, dtype, kHighlights, who)) return rc;
   if (H == 0 || W == 0) return 0;
   MI_REQUIRE(in && out, "%s: highlights: null pointer", who);
   MI_REQUIRE(in != out, "%s: highlights: the output must not overwrite the input", who);
   a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
   a.n_frames = 1;
   a.f[0] = {in, out, nullptr};
-  return hl::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
+  return hl::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
                     (hipStream_t)stream);
 }
 
@@ -947,7 +943,7 @@ static int chromatic_raw_impl(const void* const* src, void* const* cfa, int n, i
                               const char* who) {
   ca::Args a = {};
   if (int rc = chromatic_settings(a, s, pattern, H, W, work_dtype, who)) return rc;
-  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad chromatic aberration source kind %d", who, kind);
+  if (int rc = raw_kind(kind, kChromatic, who)) return rc;
   MI_REQUIRE(n >= 0, "%s: chromatic aberration with %d frames", who, n);
   if (n == 0 || H == 0 || W == 0) return 0;
   MI_REQUIRE(src && cfa, "%s: chromatic aberration: null frame list", who);
@@ -955,46 +951,14 @@ static int chromatic_raw_impl(const void* const* src, void* const* cfa, int n, i
     MI_REQUIRE(src[i] && cfa[i], "%s: chromatic aberration: frame %d has a null pointer", who, i);
     MI_REQUIRE(src[i] != cfa[i], "%s: chromatic aberration: frame %d: the CFA must not overwrite its source", who, i);
   }
-  MI_REQUIRE(!plain || !shading, "%s: chromatic aberration: the plain f32 output takes no shading grid", who);
-  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
-  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: chromatic aberration: packed frames must be even size, got %dx%d",
-             who, H, W);
-  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: chromatic aberration: the IDS layout is a packed-12 layout", who);
-  a.H = H; a.W = W;
+  if (int rc = raw_source_rules(H, W, kind, ids_format, shading, plain, kChromatic, who)) return rc;
   int src_kind;
-  if (packed) {
-    tile::Params p = {};
-    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
-    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
-    if (int rc = apply_levels(p, levels, bits, who)) return rc;
-    for (int k = 0; k < 4; ++k) {                     // the per-site decode of the shading path (apply_levels_shading)
-      a.black[k] = p.levels ? p.lv_black[k] : 0;
-      a.k[k] = p.levels ? p.lv_k[k] : p.k_decode;
-    }
-    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
-  } else {
-    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
-      MI_REQUIRE(kind == MI_RAW_16U, "%s: chromatic aberration: levels apply to u16 codes only (source kind %d)", who, kind);
-      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
-      for (int k = 0; k < 4; ++k) a.k[k] = (float)(levels->white - levels->black[k]);
-      a.levels = 1;
-    }
-    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
-  }
-  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
-  a.mask_w = (W + 31) / 32;
-  for (int i = 0; i < n; ++i)
-    if (defects && defects[i]) {
-      MI_REQUIRE(defects[i]->n >= 0, "%s: chromatic aberration: negative defect count %d", who, (int)defects[i]->n);
-      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: chromatic aberration: frame %d: defects without a mask", who, i);
-    }
+  if (int rc = raw_source_setup(a, src_kind, H, W, kind, ids_format, levels, shading, defects, n, kChromatic, who))
+    return rc;
   const int out = plain ? hl::OUT_PLAIN : (work_dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32);
   for (int i0 = 0; i0 < n; i0 += ca::MAX_FRAMES) {
     a.n_frames = n - i0 < ca::MAX_FRAMES ? n - i0 : ca::MAX_FRAMES;
-    for (int i = 0; i < a.n_frames; ++i) {
-      const mi_isp_defects* m = defects ? defects[i0 + i] : nullptr;
-      a.f[i] = {src[i0 + i], cfa[i0 + i], (m && m->n > 0) ? m->mask_dev : nullptr};
-    }
+    for (int i = 0; i < a.n_frames; ++i) a.f[i] = {src[i0 + i], cfa[i0 + i], mask_of(defects, i0 + i)};
     if (int rc = ca::launch(a, src_kind, out, (hipStream_t)stream)) return rc;
   }
   return 0;
@@ -1027,7 +991,7 @@ extern "C" int mi_isp_chromatic_cfa(const void* in, void* out, int H, int W, int
   a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
   a.n_frames = 1;
   a.f[0] = {in, out, nullptr};
-  return ca::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
+  return ca::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
                     (hipStream_t)stream);
 }
 
@@ -1052,13 +1016,6 @@ static int temporal_settings(tn::Args& a, const mi_isp_temporal* t, const char* 
   MI_REQUIRE(std::isfinite(a.c) && a.c > 0.f, "%s: temporal threshold %g: its square must be finite and > 0 in f32", who, th);
   a.rcp_n[0] = 0.f;
   for (int n = 1; n < 10; ++n) a.rcp_n[n] = (float)(1.0 / (double)n);
-  return 0;
-}
-
-static int temporal_geometry(int H, int W, int work_dtype, const char* who) {
-  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad temporal shape %dx%d", who, H, W);
-  MI_REQUIRE(H < (1 << 22) && W < (1 << 24), "%s: temporal frame %dx%d too large", who, H, W);
-  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: temporal work dtype must be f16 or f32", who);
   return 0;
 }
 
@@ -1091,8 +1048,8 @@ static int temporal_raw_impl(const void* const* src, const float* const* hin, fl
                              int plain, void* stream, const char* who) {
   tn::Args a = {};
   if (int rc = temporal_settings(a, t, who)) return rc;
-  if (int rc = temporal_geometry(H, W, work_dtype, who)) return rc;
-  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad temporal source kind %d", who, kind);
+  if (int rc = raw_geometry(H, W, work_dtype, kTemporal, who)) return rc;
+  if (int rc = raw_kind(kind, kTemporal, who)) return rc;
   MI_REQUIRE(n >= 0, "%s: temporal with %d frames", who, n);
   if (n == 0 || H == 0 || W == 0) return 0;
   MI_REQUIRE(src && hout && (cfa || plain), "%s: temporal: null frame list", who);
@@ -1101,51 +1058,21 @@ static int temporal_raw_impl(const void* const* src, const float* const* hin, fl
     MI_REQUIRE(plain || cfa[i], "%s: temporal: frame %d has a null CFA", who, i);
     MI_REQUIRE(plain || src[i] != cfa[i], "%s: temporal: frame %d: the CFA must not overwrite its source", who, i);
   }
-  MI_REQUIRE(!plain || !shading, "%s: temporal: the plain f32 output takes no shading grid", who);
-  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
-  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: temporal: packed frames must be even size, got %dx%d", who, H, W);
-  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: temporal: the IDS layout is a packed-12 layout", who);
+  if (int rc = raw_source_rules(H, W, kind, ids_format, shading, plain, kTemporal, who)) return rc;
   const size_t px = (size_t)H * (size_t)W;
   const size_t src_bytes = kind == MI_RAW_PACKED12 ? px * 3 / 2 : (kind == MI_RAW_32F ? px * 4 : px * 2);
   if (int rc = temporal_overlaps(src, src_bytes, hin, hout, plain ? nullptr : cfa, px * mi_dtype_size(work_dtype), n, px * 4,
                                  who))
     return rc;
-  a.H = H; a.W = W;
   int src_kind;
-  if (packed) {
-    tile::Params p = {};
-    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
-    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
-    if (int rc = apply_levels(p, levels, bits, who)) return rc;
-    for (int s = 0; s < 4; ++s) {                     // the per-site decode of the shading path (apply_levels_shading)
-      a.black[s] = p.levels ? p.lv_black[s] : 0;
-      a.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
-    }
-    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
-  } else {
-    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
-      MI_REQUIRE(kind == MI_RAW_16U, "%s: temporal: levels apply to u16 codes only (source kind %d)", who, kind);
-      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
-      for (int s = 0; s < 4; ++s) a.k[s] = (float)(levels->white - levels->black[s]);
-      a.levels = 1;
-    }
-    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
-  }
-  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
-  a.mask_w = (W + 31) / 32;
-  for (int i = 0; i < n; ++i)
-    if (defects && defects[i]) {
-      MI_REQUIRE(defects[i]->n >= 0, "%s: temporal: negative defect count %d", who, (int)defects[i]->n);
-      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: temporal: frame %d: defects without a mask", who, i);
-    }
+  if (int rc = raw_source_setup(a, src_kind, H, W, kind, ids_format, levels, shading, defects, n, kTemporal, who))
+    return rc;
   const int out = plain ? tn::OUT_PLAIN : (work_dtype == MI_F16 ? tn::OUT_F16 : tn::OUT_F32);
   for (int i0 = 0; i0 < n; i0 += tn::MAX_FRAMES) {
     a.n_frames = n - i0 < tn::MAX_FRAMES ? n - i0 : tn::MAX_FRAMES;
-    for (int i = 0; i < a.n_frames; ++i) {
-      const mi_isp_defects* m = defects ? defects[i0 + i] : nullptr;
+    for (int i = 0; i < a.n_frames; ++i)
       a.f[i] = {src[i0 + i], plain ? nullptr : cfa[i0 + i], hin ? hin[i0 + i] : nullptr, hout[i0 + i],
-                (m && m->n > 0) ? m->mask_dev : nullptr};
-    }
+                mask_of(defects, i0 + i)};
     if (int rc = tn::launch(a, src_kind, out, (hipStream_t)stream)) return rc;
   }
   return 0;
@@ -1173,7 +1100,7 @@ extern "C" int mi_isp_temporal_cfa(const void* in, const float* hist_in, float* 
   const char* who = "temporal_cfa";
   tn::Args a = {};
   if (int rc = temporal_settings(a, temporal, who)) return rc;
-  if (int rc = temporal_geometry(H, W, dtype, who)) return rc;
+  if (int rc = raw_geometry(H, W, dtype, kTemporal, who)) return rc;
   if (H == 0 || W == 0) return 0;
   MI_REQUIRE(in && out && hist_out, "%s: temporal: null pointer", who);
   MI_REQUIRE(in != out, "%s: temporal: the output must not overwrite the input", who);
@@ -1185,7 +1112,7 @@ extern "C" int mi_isp_temporal_cfa(const void* in, const float* hist_in, float* 
   a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
   a.n_frames = 1;
   a.f[0] = {in, out, hist_in, hist_out, nullptr};
-  return tn::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? tn::OUT_F16 : tn::OUT_F32,
+  return tn::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? tn::OUT_F16 : tn::OUT_F32,
                     (hipStream_t)stream);
 }
 
@@ -1236,13 +1163,6 @@ static int merge_settings(em::Args& a, const mi_isp_exposure_merge* m, const cha
   return 0;
 }
 
-static int merge_geometry(int H, int W, int work_dtype, const char* who) {
-  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad exposure merge shape %dx%d", who, H, W);
-  MI_REQUIRE(H < (1 << 22) && W < (1 << 24), "%s: exposure merge frame %dx%d too large", who, H, W);
-  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: exposure merge work dtype must be f16 or f32", who);
-  return 0;
-}
-
 // n brackets of one geometry (src: n * E pointers, bracket-major): every bracket's pointers (and defect mask) in the kernel
 // arguments, 16 per launch
 static int merge_raw_impl(const void* const* src, void* const* out, int n, int H, int W, int kind, int ids_format,
@@ -1251,17 +1171,13 @@ static int merge_raw_impl(const void* const* src, void* const* out, int n, int H
                           const char* who) {
   em::Args a = {};
   if (int rc = merge_settings(a, m, who)) return rc;
-  if (int rc = merge_geometry(H, W, work_dtype, who)) return rc;
-  MI_REQUIRE(kind >= MI_RAW_PACKED12 && kind <= MI_RAW_16F, "%s: bad exposure merge source kind %d", who, kind);
+  if (int rc = raw_geometry(H, W, work_dtype, kMerge, who)) return rc;
+  if (int rc = raw_kind(kind, kMerge, who)) return rc;
   MI_REQUIRE(n >= 0, "%s: exposure merge with %d brackets", who, n);
   if (n == 0 || H == 0 || W == 0) return 0;
   MI_REQUIRE(src && out, "%s: exposure merge: null bracket list", who);
   const int E = a.E;
-  const bool packed = kind == MI_RAW_PACKED12 || kind == MI_RAW_PACKED16;
-  MI_REQUIRE(!plain || !shading, "%s: exposure merge: the plain f32 output takes no shading grid", who);
-  MI_REQUIRE(!packed || (H % 2 == 0 && W % 2 == 0), "%s: exposure merge: packed frames must be even size, got %dx%d", who, H,
-             W);
-  MI_REQUIRE(!ids_format || kind == MI_RAW_PACKED12, "%s: exposure merge: the IDS layout is a packed-12 layout", who);
+  if (int rc = raw_source_rules(H, W, kind, ids_format, shading, plain, kMerge, who)) return rc;
   const size_t px = (size_t)H * (size_t)W;
   const size_t src_bytes = kind == MI_RAW_PACKED12 ? px * 3 / 2 : (kind == MI_RAW_32F ? px * 4 : px * 2);
   const size_t out_bytes = plain ? px * 4 : px * mi_dtype_size(work_dtype);
@@ -1278,44 +1194,18 @@ static int merge_raw_impl(const void* const* src, void* const* out, int n, int H
       MI_REQUIRE(i == j || !ranges_overlap(out[i], out_bytes, out[j], out_bytes),
                  "%s: exposure merge: the outputs of brackets %d and %d overlap", who, i, j);
     }
-  a.H = H; a.W = W;
   int src_kind;
-  if (packed) {
-    tile::Params p = {};
-    const int bits = kind == MI_RAW_PACKED12 ? 12 : 16;
-    p.k_decode = (float)(1.0 / (bits == 16 ? 65535.0 : 4095.0));
-    if (int rc = apply_levels(p, levels, bits, who)) return rc;
-    for (int s = 0; s < 4; ++s) {                     // the per-site decode of the shading path (apply_levels_shading)
-      a.black[s] = p.levels ? p.lv_black[s] : 0;
-      a.k[s] = p.levels ? p.lv_k[s] : p.k_decode;
-    }
-    src_kind = bits == 16 ? dn::SRC_P16 : (ids_format ? dn::SRC_P12_IDS : dn::SRC_P12);
-  } else {
-    if (levels) {                                     // load_u16_levels_kernel's levels: k[] holds the denominators
-      MI_REQUIRE(kind == MI_RAW_16U, "%s: exposure merge: levels apply to u16 codes only (source kind %d)", who, kind);
-      if (int rc = mi_check_levels(levels, 65535, who, a.black)) return rc;
-      for (int s = 0; s < 4; ++s) a.k[s] = (float)(levels->white - levels->black[s]);
-      a.levels = 1;
-    }
-    src_kind = kind == MI_RAW_16U ? dn::SRC_U16 : (kind == MI_RAW_32F ? dn::SRC_F32 : dn::SRC_U16F);
-  }
-  if (int rc = apply_shading(a, shading, H, W, who)) return rc;
-  a.mask_w = (W + 31) / 32;
-  for (int i = 0; i < n; ++i)
-    if (defects && defects[i]) {
-      MI_REQUIRE(defects[i]->n >= 0, "%s: exposure merge: negative defect count %d", who, (int)defects[i]->n);
-      MI_REQUIRE(defects[i]->n == 0 || defects[i]->mask_dev, "%s: exposure merge: bracket %d: defects without a mask", who, i);
-    }
+  if (int rc = raw_source_setup(a, src_kind, H, W, kind, ids_format, levels, shading, defects, n, kMerge, who))
+    return rc;
   const int o = plain ? em::OUT_PLAIN : (work_dtype == MI_F16 ? em::OUT_F16 : em::OUT_F32);
   for (int i0 = 0; i0 < n; i0 += em::MAX_BRACKETS) {
     a.n_brackets = n - i0 < em::MAX_BRACKETS ? n - i0 : em::MAX_BRACKETS;
     for (int i = 0; i < a.n_brackets; ++i) {
-      const mi_isp_defects* d = defects ? defects[i0 + i] : nullptr;
       em::Bracket& b = a.b[i];
       b = {};
       for (int e = 0; e < E; ++e) b.src[e] = src[(size_t)(i0 + i) * E + e];
       b.dst = out[i0 + i];
-      b.mask = (d && d->n > 0) ? d->mask_dev : nullptr;
+      b.mask = mask_of(defects, i0 + i);
     }
     if (int rc = em::launch(a, src_kind, o, (hipStream_t)stream)) return rc;
   }
@@ -1342,7 +1232,7 @@ extern "C" int mi_isp_merge_cfa(const void* const* in, void* out, int H, int W, 
   const char* who = "merge_cfa";
   em::Args a = {};
   if (int rc = merge_settings(a, merge, who)) return rc;
-  if (int rc = merge_geometry(H, W, dtype, who)) return rc;
+  if (int rc = raw_geometry(H, W, dtype, kMerge, who)) return rc;
   if (H == 0 || W == 0) return 0;
   MI_REQUIRE(in && out, "%s: exposure merge: null pointer", who);
   const size_t bytes = (size_t)H * (size_t)W * mi_dtype_size(dtype);
@@ -1355,7 +1245,7 @@ extern "C" int mi_isp_merge_cfa(const void* const* in, void* out, int H, int W, 
   a.b[0] = {};
   for (int e = 0; e < a.E; ++e) a.b[0].src[e] = in[e];
   a.b[0].dst = out;
-  return em::launch(a, dtype == MI_F16 ? dn::SRC_CFA_F16 : dn::SRC_CFA_F32, dtype == MI_F16 ? em::OUT_F16 : em::OUT_F32,
+  return em::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? em::OUT_F16 : em::OUT_F32,
                     (hipStream_t)stream);
 }
 

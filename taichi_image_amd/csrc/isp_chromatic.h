@@ -5,8 +5,7 @@
 // demosaic and everything after it then run unchanged on that CFA.  One launch takes up to MAX_FRAMES frames of one geometry.
 #pragma once
 #include <cmath>
-#include "isp_common.h"
-#include "isp_denoise.h"
+#include "isp_raw_source.h"
 #include "isp_highlights.h"
 
 namespace ca {
@@ -23,20 +22,9 @@ constexpr double HALO_SLACK = 0.5;          // raw pixels: the f32 rounding of v
 constexpr double MAX_SHIFT = 8.0;           // the largest shift (raw pixels) the host accepts
 constexpr int SHIFT_SAMPLES = 1025;         // radii at which the host evaluates the shift
 
-typedef hl::Frame Frame;                    // {src, dst, mask}
+typedef raw::Frame Frame;                   // {src, dst, mask}; dst the work dtype, or f32 for hl::OUT_PLAIN
 
-struct Args {
-  int H, W;
-  // decode: the members of dn::Args (the sources are dn::Src)
-  int levels;
-  int black[4];
-  float k[4];
-  // lens shading / AWB gain (the members shade_gain reads); shading 0: gain 1
-  int shading;
-  const float* sh_gain;
-  int sh_sites, sh_gh, sh_gw;
-  float sh_sy, sh_sx;
-  int mask_w;
+struct Args : raw::Source {                 // the decode, the gain and the mask: isp_raw_source.h
   // the operator: the centre, 1 / norm_radius^2 and (k0 - 1, k1, k2) of red and of blue, each rounded once from the
   // host's doubles; colour[s] of CFA site s = (row & 1) * 2 + (col & 1) under the demosaic pattern
   float cy, cx, iR2;
@@ -55,7 +43,7 @@ inline int halo_for(double shift) {
   return h < 4 ? 4 : (h > HALO ? HALO : h);
 }
 
-// one launch (a.n_frames frames): src one of dn::Src, out one of hl::Out
+// one launch (a.n_frames frames): src one of raw::Src, out one of hl::Out
 int launch(const Args& a, int src, int out, hipStream_t stream);
 
 }  // namespace ca

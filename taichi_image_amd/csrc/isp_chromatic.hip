@@ -26,49 +26,6 @@
 
 namespace ca {
 
-// x of raw pixels (r, c) and (r, c + 1), c even, row r inside the frame; two: c + 1 is inside the frame (the decode of
-// hl::decode_pair and dn::decode_pair: the loaders' own arithmetic)
-template <int SRC>
-MI_DEV void decode_pair(const Args& a, const void* src, int r, int c, bool two, float& x0, float& x1) {
-  const bool odd = (r & 1) != 0;                     // (selects: a run-time index would put the arrays in scratch)
-  const int b0 = odd ? a.black[2] : a.black[0], b1 = odd ? a.black[3] : a.black[1];
-  const float k0 = odd ? a.k[2] : a.k[0], k1 = odd ? a.k[3] : a.k[1];
-  if constexpr (SRC == dn::SRC_P12 || SRC == dn::SRC_P12_IDS) {
-    const uint8_t* q = static_cast<const uint8_t*>(src) + (size_t)r * ((size_t)a.W * 3 / 2) + (size_t)(c >> 1) * 3;
-    uint32_t p0, p1;
-    tile::unpack_pair(q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16), SRC == dn::SRC_P12_IDS, p0, p1);
-    x0 = tile::level_x(p0, b0, k0);
-    x1 = tile::level_x(p1, b1, k1);
-  } else if constexpr (SRC == dn::SRC_P16) {
-    const uint8_t* q = static_cast<const uint8_t*>(src) + ((size_t)r * a.W + c) * 2;
-    x0 = tile::level_x(q[0] | ((uint32_t)q[1] << 8), b0, k0);
-    x1 = two ? tile::level_x(q[2] | ((uint32_t)q[3] << 8), b1, k1) : 0.f;
-  } else if constexpr (SRC == dn::SRC_U16) {
-    const uint16_t* q = static_cast<const uint16_t*>(src) + (size_t)r * a.W + c;
-    const uint32_t v0 = q[0], v1 = two ? q[1] : 0u;
-    if (a.levels) {                                   // load_u16_levels_kernel's quotient
-      const int d0 = (int)v0 - b0, d1 = (int)v1 - b1;
-      x0 = (float)(d0 > 0 ? d0 : 0) / k0;
-      x1 = (float)(d1 > 0 ? d1 : 0) / k1;
-    } else {                                          // load_convert_kernel's
-      x0 = (float)v0 / 65535.0f;
-      x1 = (float)v1 / 65535.0f;
-    }
-  } else if constexpr (SRC == dn::SRC_U16F) {
-    const uint16_t* q = static_cast<const uint16_t*>(src) + (size_t)r * a.W + c;
-    x0 = (float)q[0];
-    x1 = two ? (float)q[1] : 0.f;
-  } else if constexpr (SRC == dn::SRC_F32 || SRC == dn::SRC_CFA_F32) {
-    const float* q = static_cast<const float*>(src) + (size_t)r * a.W + c;
-    x0 = q[0];
-    x1 = two ? q[1] : 0.f;
-  } else {
-    const half_t* q = static_cast<const half_t*>(src) + (size_t)r * a.W + c;
-    x0 = (float)q[0];
-    x1 = two ? (float)q[1] : 0.f;
-  }
-}
-
 MI_DEV float mix(float u, float v, float omt, float t) { return u * omt + v * t; }
 
 // the renormalised sums over the kept taps: each starts from its first kept term
@@ -109,7 +66,7 @@ __global__ void __launch_bounds__(THREADS) chromatic_kernel(const Args a) {
     float x0 = 0.f, x1 = 0.f;
     if (r >= 0 && r < H && c >= 0 && c < W) {
       const bool two = c + 1 < W;
-      decode_pair<SRC>(a, fr.src, r, c, two, x0, x1);
+      raw::decode_pair<SRC>(a, fr.src, r, c, two, x0, x1);
       if (!two) x1 = 0.f;
       if (fr.mask) {
         const uint32_t m = fr.mask[(size_t)r * a.mask_w + (c >> 5)] >> (c & 31);
@@ -177,9 +134,9 @@ __global__ void __launch_bounds__(THREADS) chromatic_kernel(const Args a) {
     if (__builtin_amdgcn_ballot_w64(masked || listed || listed_g) != 0) {
       if (listed || listed_g) {                       // a listed pixel's own value, decoded again
         float p0, p1;
-        decode_pair<SRC>(a, fr.src, listed ? r : rg, c & ~1, (c | 1) < W, p0, p1);
+        raw::decode_pair<SRC>(a, fr.src, listed ? r : rg, c & ~1, (c | 1) < W, p0, p1);
         if (listed) xp = cp ? p1 : p0;
-        if (listed && listed_g) decode_pair<SRC>(a, fr.src, rg, c & ~1, (c | 1) < W, p0, p1);
+        if (listed && listed_g) raw::decode_pair<SRC>(a, fr.src, rg, c & ~1, (c | 1) < W, p0, p1);
         if (listed_g) xg = cp ? p1 : p0;
       }
       if (masked) {
@@ -217,16 +174,7 @@ static int launch_src(const Args& a, int out, hipStream_t stream) {
 
 int launch(const Args& a, int src, int out, hipStream_t stream) {
   if (a.n_frames <= 0 || a.H <= 0 || a.W <= 0) return 0;
-  switch (src) {
-    case dn::SRC_P12: return launch_src<dn::SRC_P12>(a, out, stream);
-    case dn::SRC_P12_IDS: return launch_src<dn::SRC_P12_IDS>(a, out, stream);
-    case dn::SRC_P16: return launch_src<dn::SRC_P16>(a, out, stream);
-    case dn::SRC_U16: return launch_src<dn::SRC_U16>(a, out, stream);
-    case dn::SRC_U16F: return launch_src<dn::SRC_U16F>(a, out, stream);
-    case dn::SRC_F32: return launch_src<dn::SRC_F32>(a, out, stream);
-    case dn::SRC_CFA_F16: return launch_src<dn::SRC_CFA_F16>(a, out, stream);
-    default: return launch_src<dn::SRC_CFA_F32>(a, out, stream);
-  }
+  return raw::dispatch_src(src, [&](auto s) { return launch_src<decltype(s)::value>(a, out, stream); });
 }
 
 }  // namespace ca

@@ -29,55 +29,12 @@ MI_DEV float in_vgpr(float x) {
   return x;
 }
 
-// x of raw pixels (r, c) and (r, c + 1), c even, row r inside the frame; two: c + 1 is inside the frame
-template <int SRC>
-MI_DEV void decode_pair(const Args& a, const void* src, int r, int c, bool two, float& x0, float& x1) {
-  const bool odd = (r & 1) != 0;                     // (selects: a run-time index would put the arrays in scratch)
-  const int b0 = odd ? a.black[2] : a.black[0], b1 = odd ? a.black[3] : a.black[1];
-  const float k0 = odd ? a.k[2] : a.k[0], k1 = odd ? a.k[3] : a.k[1];
-  if constexpr (SRC == SRC_P12 || SRC == SRC_P12_IDS) {
-    const uint8_t* q = static_cast<const uint8_t*>(src) + (size_t)r * ((size_t)a.W * 3 / 2) + (size_t)(c >> 1) * 3;
-    uint32_t p0, p1;
-    tile::unpack_pair(q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16), SRC == SRC_P12_IDS, p0, p1);
-    x0 = tile::level_x(p0, b0, k0);
-    x1 = tile::level_x(p1, b1, k1);
-  } else if constexpr (SRC == SRC_P16) {
-    const uint8_t* q = static_cast<const uint8_t*>(src) + ((size_t)r * a.W + c) * 2;
-    x0 = tile::level_x(q[0] | ((uint32_t)q[1] << 8), b0, k0);
-    x1 = two ? tile::level_x(q[2] | ((uint32_t)q[3] << 8), b1, k1) : 0.f;
-  } else if constexpr (SRC == SRC_U16) {
-    const uint16_t* q = static_cast<const uint16_t*>(src) + (size_t)r * a.W + c;
-    const uint32_t v0 = q[0], v1 = two ? q[1] : 0u;
-    if (a.levels) {                                   // load_u16_levels_kernel's quotient
-      const int d0 = (int)v0 - b0, d1 = (int)v1 - b1;
-      x0 = (float)(d0 > 0 ? d0 : 0) / k0;
-      x1 = (float)(d1 > 0 ? d1 : 0) / k1;
-    } else {                                          // load_convert_kernel's
-      x0 = (float)v0 / 65535.0f;
-      x1 = (float)v1 / 65535.0f;
-    }
-  } else if constexpr (SRC == SRC_U16F) {
-    const uint16_t* q = static_cast<const uint16_t*>(src) + (size_t)r * a.W + c;
-    x0 = (float)q[0];
-    x1 = two ? (float)q[1] : 0.f;
-  } else if constexpr (SRC == SRC_F32 || SRC == SRC_CFA_F32) {
-    const float* q = static_cast<const float*>(src) + (size_t)r * a.W + c;
-    x0 = q[0];
-    x1 = two ? q[1] : 0.f;
-  } else {
-    const half_t* q = static_cast<const half_t*>(src) + (size_t)r * a.W + c;
-    x0 = (float)q[0];
-    x1 = two ? (float)q[1] : 0.f;
-  }
-}
-
 // grid (ceil(W / TILE_W), ceil(H / TILE_H), n_frames)
 template <int SRC, class TO, int R>
 __global__ void __launch_bounds__(THREADS) denoise_kernel(const Args a) {
   constexpr int HALO = 2 * R;
   constexpr int LW = TILE_W + 2 * HALO;               // LDS row pitch (floats)
   constexpr int LH = TILE_H + 2 * HALO;
-  constexpr int LP = LW / 2;                          // column pairs per LDS row
   constexpr int N = 2 * R + 1;                        // window side
   __shared__ float xs[LH * LW];
 
@@ -85,24 +42,8 @@ __global__ void __launch_bounds__(THREADS) denoise_kernel(const Args a) {
   const int H = a.H, W = a.W;
   const int c0 = blockIdx.x * TILE_W, r0 = blockIdx.y * TILE_H;
 
-  // 1. the tile and its halo, decoded once: x, or -inf for a tap that is outside the frame or a listed defect.  Pairs
-  // start on even frame columns (c0 and HALO are even), so a pair's two sites and its mask bits are those of (c, c + 1).
-  for (int u = threadIdx.x; u < LH * LP; u += THREADS) {
-    const int lr = u / LP, lp = u - lr * LP;
-    const int r = r0 - HALO + lr, c = c0 - HALO + 2 * lp;
-    float x0 = -INFINITY, x1 = -INFINITY;
-    if (r >= 0 && r < H && c >= 0 && c < W) {
-      const bool two = c + 1 < W;
-      decode_pair<SRC>(a, fr.src, r, c, two, x0, x1);
-      if (!two) x1 = -INFINITY;
-      if (fr.mask) {
-        const uint32_t m = fr.mask[(size_t)r * a.mask_w + (c >> 5)] >> (c & 31);
-        if (m & 1u) x0 = -INFINITY;
-        if (m & 2u) x1 = -INFINITY;
-      }
-    }
-    *reinterpret_cast<float2*>(&xs[lr * LW + 2 * lp]) = make_float2(x0, x1);
-  }
+  // 1. the tile and its halo, decoded once: x, or -inf for a tap that is outside the frame or a listed defect
+  raw::stage_tile<SRC, TILE_H, TILE_W, HALO, HALO, THREADS>(a, fr.src, fr.mask, r0, c0, xs);
   __syncthreads();
 
   // 2. the filter: lane = tile column, the wave's rows two apart
@@ -128,11 +69,8 @@ __global__ void __launch_bounds__(THREADS) denoise_kernel(const Args a) {
     const int r = r0 + rb + 2 * k;
     const bool inside = r < H && c < W;
     float xp = win[R][R];
-    if (xp == -INFINITY && inside) {                  // a listed defect is filtered with its own value (rare)
-      float p0, p1;
-      decode_pair<SRC>(a, fr.src, r, c & ~1, (c | 1) < W, p0, p1);
-      xp = (c & 1) ? p1 : p0;
-    }
+    // a listed defect is filtered with its own value (rare)
+    if (xp == -INFINITY && inside) xp = raw::decode_one<SRC>(a, fr.src, r, c);
     const float var = __builtin_fmaf(gain, fmaxf(xp, 0.f), rn2);
     const float nkl = -fminf(c2 * __builtin_amdgcn_rcpf(var), FLT_MAX);   // (var 0: k = FLT_MAX, not inf * 0)
     float num = 0.f, den = 0.f;
@@ -168,23 +106,12 @@ static int launch_r(const Args& a, int radius, hipStream_t stream) {
   return 0;
 }
 
-template <int SRC>
-static int launch_src(const Args& a, int work_dtype, int radius, hipStream_t stream) {
-  return work_dtype == MI_F16 ? launch_r<SRC, half_t>(a, radius, stream) : launch_r<SRC, float>(a, radius, stream);
-}
-
 int launch(const Args& a, int src, int work_dtype, int radius, hipStream_t stream) {
   if (a.n_frames <= 0 || a.H <= 0 || a.W <= 0) return 0;
-  switch (src) {
-    case SRC_P12: return launch_src<SRC_P12>(a, work_dtype, radius, stream);
-    case SRC_P12_IDS: return launch_src<SRC_P12_IDS>(a, work_dtype, radius, stream);
-    case SRC_P16: return launch_src<SRC_P16>(a, work_dtype, radius, stream);
-    case SRC_U16: return launch_src<SRC_U16>(a, work_dtype, radius, stream);
-    case SRC_U16F: return launch_src<SRC_U16F>(a, work_dtype, radius, stream);
-    case SRC_F32: return launch_src<SRC_F32>(a, work_dtype, radius, stream);
-    case SRC_CFA_F16: return launch_src<SRC_CFA_F16>(a, work_dtype, radius, stream);
-    default: return launch_src<SRC_CFA_F32>(a, work_dtype, radius, stream);
-  }
+  return raw::dispatch_src(src, [&](auto s) {
+    constexpr int SRC = decltype(s)::value;
+    return work_dtype == MI_F16 ? launch_r<SRC, half_t>(a, radius, stream) : launch_r<SRC, float>(a, radius, stream);
+  });
 }
 
 }  // namespace dn

@@ -5,8 +5,7 @@
 // f32 values x_e each loader computes before shading and the cast.  The kernel writes the gained, cast CFA of the work
 // dtype, or the plain f32 y for the next raw stage.  One launch takes up to MAX_BRACKETS brackets of one geometry.
 #pragma once
-#include "isp_common.h"
-#include "isp_denoise.h"
+#include "isp_raw_source.h"
 
 namespace em {
 
@@ -26,18 +25,7 @@ struct Bracket {
   const uint32_t* mask;                     // defect mask (H rows x mask_w words, bit c & 31 of word c >> 5), or NULL
 };
 
-struct Args {
-  int H, W;
-  // decode: the members of dn::Args (the sources are dn::Src)
-  int levels;
-  int black[4];
-  float k[4];
-  // lens shading / AWB gain (the members shade_gain reads); shading 0: gain 1
-  int shading;
-  const float* sh_gain;
-  int sh_sites, sh_gh, sh_gw;
-  float sh_sy, sh_sx;
-  int mask_w;
+struct Args : raw::Source {                 // the decode, the gain and the mask: isp_raw_source.h
   // the operator: inv[e] = f32(1 / ratio_e), i2[e] = f32(1 / ratio_e^2), rn2 = read_noise^2,
   // c = threshold^2, rf = 1 / (saturation * knee), rcp_n[n] = f32(1 / n) for n = 1 .. 9 (rcp_n[0] is not used)
   int E;
@@ -48,7 +36,7 @@ struct Args {
   Bracket b[MAX_BRACKETS];
 };
 
-// one launch (a.n_brackets brackets): src one of dn::Src, out one of Out
+// one launch (a.n_brackets brackets): src one of raw::Src, out one of Out
 int launch(const Args& a, int src, int out, hipStream_t stream);
 
 }  // namespace em

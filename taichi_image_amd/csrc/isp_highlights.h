@@ -4,8 +4,7 @@
 // kernel writes the gained, cast CFA of the work dtype (or the plain f32 y for raw noise reduction to filter); the demosaic
 // and everything after it then run unchanged on that CFA.  One launch takes up to MAX_FRAMES frames of one geometry.
 #pragma once
-#include "isp_common.h"
-#include "isp_denoise.h"
+#include "isp_raw_source.h"
 
 namespace hl {
 
@@ -20,24 +19,9 @@ constexpr int HALO_C = 2;                   // ... and the decode takes pairs th
 enum Mode { MODE_REBUILD = 0, MODE_CLIP = 1 };
 enum Out { OUT_F16 = 0, OUT_F32 = 1, OUT_PLAIN = 2 };   // work-dtype CFA with gain and cast, or the plain f32 y
 
-struct Frame {
-  const void* src;
-  void* dst;                                // H x W CFA: the work dtype, or f32 for OUT_PLAIN
-  const uint32_t* mask;                     // defect mask (H rows x mask_w words, bit c & 31 of word c >> 5), or NULL
-};
+typedef raw::Frame Frame;                   // {src, dst, mask}; dst the work dtype, or f32 for OUT_PLAIN
 
-struct Args {
-  int H, W;
-  // decode: the members of dn::Args (the sources are dn::Src)
-  int levels;
-  int black[4];
-  float k[4];
-  // lens shading / AWB gain (the members shade_gain reads); shading 0: gain 1
-  int shading;
-  const float* sh_gain;
-  int sh_sites, sh_gh, sh_gw;
-  float sh_sy, sh_sx;
-  int mask_w;
+struct Args : raw::Source {                 // the decode, the gain and the mask: isp_raw_source.h
   // the operator: t = f32(clip); the balance gains of R, G, B (wb_dev, when not NULL, overrides wb: 3 f32 on the device,
   // read by the kernel); colour[s] of CFA site s = (row & 1) * 2 + (col & 1) under the demosaic pattern
   int mode;
@@ -49,7 +33,7 @@ struct Args {
   Frame f[MAX_FRAMES];
 };
 
-// one launch (a.n_frames frames): src one of dn::Src, out one of Out
+// one launch (a.n_frames frames): src one of raw::Src, out one of Out
 int launch(const Args& a, int src, int out, hipStream_t stream);
 
 }  // namespace hl

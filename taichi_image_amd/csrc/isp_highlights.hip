@@ -11,7 +11,7 @@
 // Every operation is one f32 rounding (no contraction, IEEE divisions): the output is the contract's bit for bit.
 //
 // One 256-thread block per 64 x 64 output tile of one frame (grid.z): the tile plus a halo of one row and two columns (the
-// decode takes the pairs of isp_denoise.hip, which start on even columns) is decoded ONCE into LDS as f32 x, excluded taps
+// decode takes the pairs of isp_raw_source.h, which start on even columns) is decoded ONCE into LDS as f32 x, excluded taps
 // (outside the frame, or listed defects) as -inf.  Lane l of wave w then takes column l of rows 16 w .. 16 w + 15.  Almost
 // every wave of a real frame holds no clipped pixel, so the neighbour arithmetic sits behind a wave-uniform branch (a
 // ballot of x >= t): the common case is decode, gain, cast and store.
@@ -21,49 +21,6 @@
 #pragma clang fp contract(off)
 
 namespace hl {
-
-// x of raw pixels (r, c) and (r, c + 1), c even, row r inside the frame; two: c + 1 is inside the frame (the decode of
-// dn::decode_pair: the loaders' own arithmetic)
-template <int SRC>
-MI_DEV void decode_pair(const Args& a, const void* src, int r, int c, bool two, float& x0, float& x1) {
-  const bool odd = (r & 1) != 0;                     // (selects: a run-time index would put the arrays in scratch)
-  const int b0 = odd ? a.black[2] : a.black[0], b1 = odd ? a.black[3] : a.black[1];
-  const float k0 = odd ? a.k[2] : a.k[0], k1 = odd ? a.k[3] : a.k[1];
-  if constexpr (SRC == dn::SRC_P12 || SRC == dn::SRC_P12_IDS) {
-    const uint8_t* q = static_cast<const uint8_t*>(src) + (size_t)r * ((size_t)a.W * 3 / 2) + (size_t)(c >> 1) * 3;
-    uint32_t p0, p1;
-    tile::unpack_pair(q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16), SRC == dn::SRC_P12_IDS, p0, p1);
-    x0 = tile::level_x(p0, b0, k0);
-    x1 = tile::level_x(p1, b1, k1);
-  } else if constexpr (SRC == dn::SRC_P16) {
-    const uint8_t* q = static_cast<const uint8_t*>(src) + ((size_t)r * a.W + c) * 2;
-    x0 = tile::level_x(q[0] | ((uint32_t)q[1] << 8), b0, k0);
-    x1 = two ? tile::level_x(q[2] | ((uint32_t)q[3] << 8), b1, k1) : 0.f;
-  } else if constexpr (SRC == dn::SRC_U16) {
-    const uint16_t* q = static_cast<const uint16_t*>(src) + (size_t)r * a.W + c;
-    const uint32_t v0 = q[0], v1 = two ? q[1] : 0u;
-    if (a.levels) {                                   // load_u16_levels_kernel's quotient
-      const int d0 = (int)v0 - b0, d1 = (int)v1 - b1;
-      x0 = (float)(d0 > 0 ? d0 : 0) / k0;
-      x1 = (float)(d1 > 0 ? d1 : 0) / k1;
-    } else {                                          // load_convert_kernel's
-      x0 = (float)v0 / 65535.0f;
-      x1 = (float)v1 / 65535.0f;
-    }
-  } else if constexpr (SRC == dn::SRC_U16F) {
-    const uint16_t* q = static_cast<const uint16_t*>(src) + (size_t)r * a.W + c;
-    x0 = (float)q[0];
-    x1 = two ? (float)q[1] : 0.f;
-  } else if constexpr (SRC == dn::SRC_F32 || SRC == dn::SRC_CFA_F32) {
-    const float* q = static_cast<const float*>(src) + (size_t)r * a.W + c;
-    x0 = q[0];
-    x1 = two ? q[1] : 0.f;
-  } else {
-    const half_t* q = static_cast<const half_t*>(src) + (size_t)r * a.W + c;
-    x0 = (float)q[0];
-    x1 = two ? (float)q[1] : 0.f;
-  }
-}
 
 // one tap group: the f32 sum of the kept taps' balanced values in the order given, starting from the first kept tap
 struct Group { float S; int n; };
@@ -84,31 +41,14 @@ __global__ void __launch_bounds__(THREADS) highlights_kernel(const Args a) {
   typedef typename OutType<OUT>::type TO;
   constexpr int LW = TILE_W + 2 * HALO_C;             // LDS row pitch (floats)
   constexpr int LH = TILE_H + 2 * HALO_R;
-  constexpr int LP = LW / 2;                          // column pairs per LDS row
   __shared__ float xs[LH * LW];
 
   const Frame& fr = a.f[blockIdx.z];                  // (a wave-uniform index: scalar loads)
   const int H = a.H, W = a.W;
   const int c0 = blockIdx.x * TILE_W, r0 = blockIdx.y * TILE_H;
 
-  // 1. the tile and its halo, decoded once: x, or -inf for a tap that is outside the frame or a listed defect.  Pairs
-  // start on even frame columns (c0 and HALO_C are even), so a pair's two sites and its mask bits are those of (c, c + 1).
-  for (int u = threadIdx.x; u < LH * LP; u += THREADS) {
-    const int lr = u / LP, lp = u - lr * LP;
-    const int r = r0 - HALO_R + lr, c = c0 - HALO_C + 2 * lp;
-    float x0 = -INFINITY, x1 = -INFINITY;
-    if (r >= 0 && r < H && c >= 0 && c < W) {
-      const bool two = c + 1 < W;
-      decode_pair<SRC>(a, fr.src, r, c, two, x0, x1);
-      if (!two) x1 = -INFINITY;
-      if (fr.mask) {
-        const uint32_t m = fr.mask[(size_t)r * a.mask_w + (c >> 5)] >> (c & 31);
-        if (m & 1u) x0 = -INFINITY;
-        if (m & 2u) x1 = -INFINITY;
-      }
-    }
-    *reinterpret_cast<float2*>(&xs[lr * LW + 2 * lp]) = make_float2(x0, x1);
-  }
+  // 1. the tile and its halo, decoded once: x, or -inf for a tap that is outside the frame or a listed defect
+  raw::stage_tile<SRC, TILE_H, TILE_W, HALO_R, HALO_C, THREADS>(a, fr.src, fr.mask, r0, c0, xs);
   __syncthreads();
 
   // 2. lane = tile column; the balance gains of the lane's own sites (ws) and of the other column parity (wo), per row parity
@@ -142,11 +82,7 @@ __global__ void __launch_bounds__(THREADS) highlights_kernel(const Args a) {
       const float* row = &xs[(tr + HALO_R) * LW + lane + HALO_C];
       float xp = row[0];
       const bool listed = xp == -INFINITY && inside;
-      if (listed) {                                   // a listed defect keeps its own value (rare)
-        float p0, p1;
-        decode_pair<SRC>(a, fr.src, r, c & ~1, (c | 1) < W, p0, p1);
-        xp = cp ? p1 : p0;
-      }
+      if (listed) xp = raw::decode_one<SRC>(a, fr.src, r, c);      // a listed defect keeps its own value (rare)
       float y = xp;
       if (clip_mode) {
         y = (xp > lim[par] && !listed) ? lim[par] : xp;
@@ -200,16 +136,7 @@ static int launch_src(const Args& a, int out, hipStream_t stream) {
 
 int launch(const Args& a, int src, int out, hipStream_t stream) {
   if (a.n_frames <= 0 || a.H <= 0 || a.W <= 0) return 0;
-  switch (src) {
-    case dn::SRC_P12: return launch_src<dn::SRC_P12>(a, out, stream);
-    case dn::SRC_P12_IDS: return launch_src<dn::SRC_P12_IDS>(a, out, stream);
-    case dn::SRC_P16: return launch_src<dn::SRC_P16>(a, out, stream);
-    case dn::SRC_U16: return launch_src<dn::SRC_U16>(a, out, stream);
-    case dn::SRC_U16F: return launch_src<dn::SRC_U16F>(a, out, stream);
-    case dn::SRC_F32: return launch_src<dn::SRC_F32>(a, out, stream);
-    case dn::SRC_CFA_F16: return launch_src<dn::SRC_CFA_F16>(a, out, stream);
-    default: return launch_src<dn::SRC_CFA_F32>(a, out, stream);
-  }
+  return raw::dispatch_src(src, [&](auto s) { return launch_src<decltype(s)::value>(a, out, stream); });
 }
 
 }  // namespace hl

@@ -5,8 +5,7 @@
 // and the gained, cast CFA of the work dtype; with the plain output the history plane is the only write, and the next raw
 // stage reads it.  One launch takes up to MAX_FRAMES frames of one geometry, each with its own two history planes.
 #pragma once
-#include "isp_common.h"
-#include "isp_denoise.h"
+#include "isp_raw_source.h"
 
 namespace tn {
 
@@ -27,18 +26,7 @@ struct Frame {
   const uint32_t* mask;                     // defect mask (H rows x mask_w words, bit c & 31 of word c >> 5), or NULL
 };
 
-struct Args {
-  int H, W;
-  // decode: the members of dn::Args (the sources are dn::Src)
-  int levels;
-  int black[4];
-  float k[4];
-  // lens shading / AWB gain (the members shade_gain reads); shading 0: gain 1
-  int shading;
-  const float* sh_gain;
-  int sh_sites, sh_gh, sh_gw;
-  float sh_sy, sh_sx;
-  int mask_w;
+struct Args : raw::Source {                 // the decode, the gain and the mask: isp_raw_source.h
   // the operator: var = gain * max(h, 0) + rn2; qv = (m * m) / (c * var); w = wmax * max(1 - qv, 0);
   // m = D * rcp_n[n], rcp_n[n] = f32(1 / n) for n = 1 .. 9 (rcp_n[0] is not used)
   float gain, rn2, c, wmax;
@@ -47,7 +35,7 @@ struct Args {
   Frame f[MAX_FRAMES];
 };
 
-// one launch (a.n_frames frames): src one of dn::Src, out one of Out
+// one launch (a.n_frames frames): src one of raw::Src, out one of Out
 int launch(const Args& a, int src, int out, hipStream_t stream);
 
 }  // namespace tn

@@ -16,8 +16,9 @@ isp_denoise.hip), instance by instance against their NumPy references, and the h
    temporal_cfa, denoise_cfa), which the feature tests cover with OUT of the same dtype; <CFA_F16, OUT_F32>,
    <CFA_F32, OUT_F16> and <CFA_*, OUT_PLAIN> are instantiated, but no entry point dispatches to them.  dn::denoise_kernel
    has no plain output.
-2. Every position a stage takes in ISP._corrected that the feature tests leave out, through the loaders of Camera16 and
-   Camera32 at 66 x 70 (CHAINS below): the references composed in _corrected's order; every intermediate a chain exposes
+2. Every position a stage takes in ISP._raw_chain that the feature tests leave out, and the chains H, D and HD of one or
+   two stages (every loader with a raw stage on takes that one route), through the loaders of Camera16 and
+   Camera32 at 66 x 70 (CHAINS below): the references composed in _raw_chain's order; every intermediate a chain exposes
    (the plain f32 output of each stage that is not the last, read from the tensors the wrapped entry point wrote, and the
    temporal history) bit for bit, the final CFA bit for bit - or, behind raw noise reduction, within its bound - and one
    launch per stage and load.
@@ -73,7 +74,8 @@ UNIT = {k: 1000.0 if k == "16f" else 1.0 for k in KINDS}  # load_16f's x is the 
 SEAMS = (66, 70)
 
 # the chains of section 2 -> the kind that runs them besides p12
-CHAINS = {"MH": "ids", "MC": "16f", "MD": "p16", "CT": "32f", "HT": "16u", "TD": "ids", "MCT": "p16", "HTD": "32f"}
+CHAINS = {"MH": "ids", "MC": "16f", "MD": "p16", "CT": "32f", "HT": "16u", "TD": "ids", "MCT": "p16", "HTD": "32f",
+          "H": "p16", "D": "16f", "HD": "16u"}
 CHAIN_CASES = [(c, k) for c, other in CHAINS.items() for k in ("p12", other)]
 ENTRY = {"M": ("mi_isp_merge_raw_batch", 1), "H": ("mi_isp_highlights_raw_batch", 1), "C": ("mi_isp_chromatic_raw_batch", 1),
          "T": ("mi_isp_temporal_raw_batch", 2), "D": ("mi_isp_denoise_raw_batch", 1)}     # entry point, its output list
@@ -227,10 +229,10 @@ def test_the_matrix_is_the_full_cross_product():
 
 
 def test_the_chains_and_their_kinds():
-    assert list(CHAINS) == ["MH", "MC", "MD", "CT", "HT", "TD", "MCT", "HTD"]
+    assert list(CHAINS) == ["MH", "MC", "MD", "CT", "HT", "TD", "MCT", "HTD", "H", "D", "HD"]
     assert {"ids", "p16", "16f", "32f"} <= set(CHAINS.values()) and "p12" not in CHAINS.values()
-    assert CHAIN_CASES == [(c, k) for c in CHAINS for k in ("p12", CHAINS[c])] and len(set(CHAIN_CASES)) == 16
-    for chain in CHAINS:                                   # _corrected's order, every stage at most once
+    assert CHAIN_CASES == [(c, k) for c in CHAINS for k in ("p12", CHAINS[c])] and len(set(CHAIN_CASES)) == 22
+    for chain in CHAINS:                                   # _raw_chain's order, every stage at most once
         assert [s for s in "MHCTD" if s in chain] == list(chain)
     marks = {m.args[0]: m.args[1] for m in test_chain_positions.pytestmark if m.name == "parametrize"}
     assert marks["chain,kind"] is CHAIN_CASES and marks["cam,work"] is CAMS
@@ -399,7 +401,7 @@ def test_denoise_instance(ti, dev, kind, work, radius):
                               f"denoise <{kind}, {work}, R={radius}> {H}x{W} map={mapped}", where=~listed)
 
 
-# ---- 2. every position of a stage in _corrected -------------------------------------------------------------------------
+# ---- 2. every position of a stage in _raw_chain -------------------------------------------------------------------------
 def chain_settings(chain, kind):
     H, W = SEAMS
     names = {"M": "merge", "H": "highlights", "C": "chromatic", "T": "temporal", "D": "denoise"}
@@ -409,7 +411,7 @@ def chain_settings(chain, kind):
 @functools.lru_cache(maxsize=None)
 def chain_case(chain, kind):
     """The loads of a chain (two through one history when it has the temporal stage) and the references composed in
-    _corrected's order: dict(steps=[dict(srcs, xs, inputs={stage: what it reads}, ys={stage: its y})], ...)."""
+    _raw_chain's order: dict(steps=[dict(srcs, xs, inputs={stage: what it reads}, ys={stage: its y})], ...)."""
     H, W = SEAMS
     rng = _rng(50, list(CHAINS).index(chain), KINDS.index(kind))
     pattern = O.GRBG
