@@ -439,7 +439,41 @@ int mi_isp_highlights_raw_batch(const void* const* src_host, void* const* cfa_ho
                                 const mi_isp_highlights* highlights_host, int out_f32_plain, void* stream);
 int mi_isp_highlights_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, int pattern,
                           const mi_isp_highlights* highlights_host, void* stream);
-/* ---- chromatic aberration ("Chromatic aberration") ------------------------------------------------------
+/* ---- directional demosaic ("Directional demosaic") --------------------------------------------------------
+ * A direction-adaptive alternative to mi_isp_demosaic's 13-tap filter, in f32 with one rounding per operation, in the
+ * order written, never contracted: the output is the contract's bit for bit.  X(r, c) is the f32 value of the H x W CFA
+ * in the work dtype (H, W even and >= 2), extended over the plane by the mirror that does not repeat the edge sample:
+ * index i folds with period 2 (n - 1), -1 -> 1, n -> n - 2, repeatedly for small n, which keeps the Bayer phase.  Every
+ * quantity is defined on that plane.
+ *   1. eh = (X(r,c-1) + X(r,c+1)) * 0.5 + ((X(r,c) + X(r,c)) - (X(r,c-2) + X(r,c+2))) * 0.25; ev the same along the column.
+ *      Red or blue site: GH = eh, GV = ev, CH = X - eh, CV = X - ev.  Green site: CH = eh - X, CV = ev - X.
+ *   2. DH(r,c) = |CH(r,c) - CH(r,c+2)|, DV(r,c) = |CV(r,c) - CV(r+2,c)|.  dH(r,c) = DH(r-2,c) + DH(r-2,c+2) + DH(r-1,c+1)
+ *      + 3 * DH(r,c) + 3 * DH(r,c+2) + DH(r+1,c+1) + DH(r+2,c) + DH(r+2,c+2), accumulated in that order; dV is its
+ *      transpose (weights, window and order).  A site is horizontal when dV >= dH.
+ *   3. Red or blue site: G = GH when horizontal, else GV.
+ *   4. Green site, K the chroma of its row neighbours: K = X + ((K(r,c-1) - G(r,c-1)) + (K(r,c+1) - G(r,c+1))) * 0.5; the
+ *      other chroma the same from the neighbours above and below.
+ *   5. Red or blue site: d = (RB(r,c-1) + RB(r,c+1)) * 0.5 when horizontal, else the same along the column, RB = R - B of
+ *      the green site from step 4.  Blue site: R = X + d.  Red site: B = X - d.
+ *   6. mi_isp_demosaic's epilogue: the optional matrix as (m0 * r + m1 * g) + m2 * b, clamp01, * scale(out), the cast.
+ * An output pixel reads X over rows r - 4 .. r + 8 and columns c - 4 .. c + 8.
+ *  - mi_isp_demosaic_directional_cfa: a normalised CFA of in_dtype MI_F16 / MI_F32; out_dtype any of MI_U8 .. MI_F32.
+ *  - mi_isp_demosaic_directional_raw_batch: n raw frames of one geometry (source kinds, ids_format, levels and grids as
+ *    mi_isp_denoise_raw_batch; levels_host and shading_host may each be NULL); X is the loaders' CFA cast_work(x * g), the
+ *    output is in the work dtype.  One launch per 32 frames.
+ *  - mi_isp_raw_cfa_batch: the decode alone: that CFA, H x W of the work dtype, written to cfa_host[i].
+ * Host-side checks before any launch (error text names "demosaic_directional"): NULL pointers, odd or non-positive sizes,
+ * dtypes, the pattern, the kind, n < 0, levels and grids.  n == 0 is a successful no-op. */
+int mi_isp_demosaic_directional_cfa(const void* cfa_dev, void* rgb_dev, int H, int W, int in_dtype, int out_dtype,
+                                    int pattern, const float* ccm9_host, void* stream);
+int mi_isp_demosaic_directional_raw_batch(const void* const* srcs_host, void* const* rgbs_host, int n, int H, int W,
+                                          int src_kind, int ids_format, int work_dtype, int pattern,
+                                          const mi_isp_levels* levels_host, const mi_isp_shading* shading_host,
+                                          const float* ccm9_host, void* stream);
+int mi_isp_raw_cfa_batch(const void* const* srcs_host, void* const* cfas_host, int n, int H, int W, int src_kind,
+                         int ids_format, int work_dtype, const mi_isp_levels* levels_host,
+                         const mi_isp_shading* shading_host, void* stream);
+/* ---- chromatic aberration("Chromatic aberration") ------------------------------------------------------
  * Lateral chromatic aberration corrected on the CFA: the red and the blue site planes are resampled radially about the
  * optical centre, green is left alone; in f32 with one rounding per operation, left to right, never contracted: the
  * output is the contract's bit for bit.  x(p) is the value raw noise reduction filters (above); s(p) = (row & 1) * 2 +

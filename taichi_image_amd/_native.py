@@ -211,6 +211,11 @@ SIGNATURES = {
                                             POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Highlights), c_int,
                                             _P]),
     "mi_isp_highlights_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Highlights), _P]),
+    "mi_isp_demosaic_directional_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
+    "mi_isp_demosaic_directional_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
+                                                      c_int, POINTER(Levels), POINTER(Shading), POINTER(c_float), _P]),
+    "mi_isp_raw_cfa_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Levels),
+                                     POINTER(Shading), _P]),
     "mi_isp_chromatic_raw": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading),
                                      POINTER(Defects), POINTER(Chromatic), c_int, _P]),
     "mi_isp_chromatic_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -33,6 +33,7 @@ from . import luma_denoise as _ydn
 from . import color_lut as _clut
 from . import local_contrast as _lc
 from . import local_tonemap as _ltm
+from . import demosaic as _dm
 from . import white_balance as _wb
 from . import distributed as _dist
 
@@ -298,7 +299,8 @@ def camera_isp(name: str, dtype=types.f32):
                      temporal_denoise=None,
                      exposure_merge=None,
                      local_tonemap=None,
-                     luma_denoise=None):
+                     luma_denoise=None,
+                     demosaic=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -325,6 +327,7 @@ def camera_isp(name: str, dtype=types.f32):
             chroma_denoise = _cdn.check_chroma_denoise(chroma_denoise)
             luma_denoise = _ydn.check_luma_denoise(luma_denoise)
             color_lut = _clut.check_color_lut(color_lut)
+            demosaic = _dm.check_demosaic(demosaic)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -407,6 +410,9 @@ def camera_isp(name: str, dtype=types.f32):
             self._color_lut = color_lut
             if color_lut is not None:
                 color_lut._device_table(self.device)         # (uploaded now: a captured step finds it on the device)
+            # the demosaic (an extension): the Demosaic every loader demosaics with, or None (the 13-tap filter: the loaders
+            # run exactly as without it).  DESIGN.md 3, "Directional demosaic".
+            self._demosaic = demosaic
 
         @property
         def _demosaic_pattern(self):
@@ -421,7 +427,7 @@ def camera_isp(name: str, dtype=types.f32):
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
                 highlights=None, chromatic_aberration=None, temporal_denoise=None, exposure_merge=None,
-                local_tonemap=None, luma_denoise=None):
+                local_tonemap=None, luma_denoise=None, demosaic=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -442,7 +448,8 @@ def camera_isp(name: str, dtype=types.f32):
             histories are the caller's: reset() them when the new settings should not meet old frames).
             exposure_merge (the extension): None leaves it, False turns it off, an ExposureMerge replaces it.
             local_tonemap (the extension): None leaves it, False turns it off, a LocalTonemap replaces it.
-            luma_denoise (the extension): None leaves it, False turns it off, a LumaDenoise replaces it."""
+            luma_denoise (the extension): None leaves it, False turns it off, a LumaDenoise replaces it.
+            demosaic (the extension): None leaves it, False turns it off, a Demosaic replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -468,6 +475,7 @@ def camera_isp(name: str, dtype=types.f32):
             new_ydn = (None if luma_denoise is None or luma_denoise is False
                        else _ydn.check_luma_denoise(luma_denoise))
             new_clut = None if color_lut is None or color_lut is False else _clut.check_color_lut(color_lut)
+            new_dm = None if demosaic is None or demosaic is False else _dm.check_demosaic(demosaic)
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -553,6 +561,10 @@ def camera_isp(name: str, dtype=types.f32):
             elif new_clut is not None:
                 self._color_lut = new_clut
                 new_clut._device_table(self.device)
+            if demosaic is False:
+                self._demosaic = None
+            elif new_dm is not None:
+                self._demosaic = new_dm
             if auto_white_balance is not None:
                 if awb is None:
                     self._awb_off()
@@ -758,6 +770,15 @@ def camera_isp(name: str, dtype=types.f32):
                 if a is not None:
                     _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, a, stream))
             return cfas
+
+        @property
+        def demosaic(self) -> Optional[_dm.Demosaic]:
+            """The Demosaic the loaders demosaic with, or None (the 13-tap filter)."""
+            return self._demosaic
+
+        def _directional(self):
+            """True when the loaders take the directional demosaic (Demosaic("malvar") is as without the option)."""
+            return self._demosaic is not None and self._demosaic.is_directional
 
         @property
         def local_tonemap(self) -> Optional[_ltm.LocalTonemap]:
@@ -1000,6 +1021,8 @@ def camera_isp(name: str, dtype=types.f32):
                 kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
                 cfas = self._raw_chain(srcs, h, w, kind, ids_format, lv, maps, hists)
                 rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
+            elif self._directional():
+                rgbs = self._load_directional(srcs, h, w, bits, ids_format, lv, maps, lenses)
             elif lenses.count(None) < len(lenses):       # (some frame has a lens)
                 # lens distortion: the frames without a lens as the call without lenses, the others loaded at full
                 # resolution in one launch and remapped
@@ -1015,6 +1038,37 @@ def camera_isp(name: str, dtype=types.f32):
                 rgbs = self._load_frames(srcs, h, w, bits, ids_format, lv, maps, batch)
             self._awb_stats_packed(srcs, h, w, bits, ids_format, lv)     # auto white balance: the statistics of the sources
             return self._tone_mapped(rgbs)
+
+        def _load_directional(self, srcs, h, w, bits, ids_format, lv, maps, lenses):
+            """The packed loaders' route with the directional demosaic and no raw stage on: the frames without a defect map
+            go from packed bytes to the full-resolution image in ONE launch (mi_isp_demosaic_directional_raw_batch: the
+            CFA exists in LDS only); a frame with a map is decoded to its CFA (one launch for all of them), fixed in place
+            and demosaiced from there.  Then each image is resized, or remapped through its lens, as _process_image does:
+            the fused resize and the fused metering subsample are not used.  DESIGN.md 3, "Directional demosaic"."""
+            L = _native.lib()
+            stream = _native.stream_ptr(self.device)
+            kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
+            ids = int(bool(ids_format))
+            sh = _native.shading_arg(self._applied_shading())
+            plain = [i for i, m in enumerate(maps) if m is None]
+            mapped = [i for i, m in enumerate(maps) if m is not None]
+            out = {}
+            if plain:
+                full = [torch.empty((h, w, 3), dtype=torch_dtype, device=self.device) for _ in plain]
+                _native.check(L.mi_isp_demosaic_directional_raw_batch(
+                    _native.ptr_array([srcs[i] for i in plain]), _native.ptr_array(full), len(plain), h, w, kind, ids,
+                    dtype.code, self._demosaic_pattern.value, lv, sh, _native.ccm_arg(self.color_correct_matrix), stream))
+                for i, rgb in zip(plain, full):
+                    out[i] = self.resize_image(rgb) if lenses[i] is None else self._undistort([rgb], [lenses[i]], h, w)[0]
+            if mapped:
+                cfas = [torch.empty((h, w), dtype=torch_dtype, device=self.device) for _ in mapped]
+                _native.check(L.mi_isp_raw_cfa_batch(_native.ptr_array([srcs[i] for i in mapped]), _native.ptr_array(cfas),
+                                                     len(mapped), h, w, kind, ids, dtype.code, lv, sh, stream))
+                for i, cfa in zip(mapped, cfas):
+                    _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, maps[i]._arg(self.device),
+                                                           stream))
+                    out[i] = self._process_image(cfa, lenses[i])
+            return [out[i] for i in range(len(srcs))]
 
         def _load_frames(self, srcs, h, w, bits, ids_format, lv, maps, batch, full=False):
             """The load itself: the checked h x w packed frames srcs (on the device; maps: a DefectMap or None each) to
@@ -1218,7 +1272,8 @@ def camera_isp(name: str, dtype=types.f32):
 
         def _process_image(self, cfa, lens=None):
             """camera_isp.py:371-373; with a lens the full-resolution image is remapped at the resize geometry."""
-            rgb = bayer.bayer_to_rgb(cfa, pattern=self._demosaic_pattern, correct_colors=self.color_correct_matrix)
+            demosaic = _dm.directional if self._directional() else bayer.bayer_to_rgb
+            rgb = demosaic(cfa, pattern=self._demosaic_pattern, correct_colors=self.color_correct_matrix)
             if lens is not None:
                 return self._undistort([rgb], [lens], *cfa.shape)[0]
             return self.resize_image(rgb)
@@ -1408,7 +1463,8 @@ def camera_isp(name: str, dtype=types.f32):
                      and self._chromatic is None              # (chromatic aberration: the two calls below)
                      and self._temporal is None               # (temporal noise reduction: the two calls below)
                      and self._ltm is None                    # (local tone mapping: the two calls below)
-                     and history is None                      # (a history without it: the load below rejects it)
+                     and not self._directional()              # (the directional demosaic: the two calls below)
+                     and history is None                     # (a history without it: the load below rejects it)
                      and defects is None                      # (defective pixels: the two calls below)
                      and undistort is None                    # (lens distortion: the two calls below)
                      and self.transform == interpolate.ImageTransform.none and self.metering_stride == 8

@@ -16,6 +16,7 @@
 #include "isp_awb.h"
 #include "isp_denoise.h"
 #include "isp_highlights.h"
+#include "isp_demosaic_dir.h"
 #include "isp_chromatic.h"
 #include "isp_temporal.h"
 #include "isp_exposure_merge.h"
@@ -883,6 +884,83 @@ extern "C" int mi_isp_highlights_cfa(const void* in, void* out, int H, int W, in
   a.f[0] = {in, out, nullptr};
   return hl::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
                     (hipStream_t)stream);
+}
+
+// ---- directional demosaic (isp_demosaic_dir.h; DESIGN.md 3, "Directional demosaic") ---------------------------------
+static const RawStage kDirectional = {"demosaic_directional", "demosaic_directional: ", "frame"};
+
+// the shape, the pattern and the colour matrix, checked on the host; fills the operator members of a
+static int directional_settings(dd::Args& a, int H, int W, int pattern, const float* ccm9, int out_dtype, const char* who) {
+  MI_REQUIRE(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "%s: demosaic_directional: the frame must be of even size >= 2, got %dx%d",
+             who, H, W);
+  MI_REQUIRE(H <= dd::TILE_H * 65535 && W < (1 << 24), "%s: demosaic_directional: frame %dx%d too large", who, H, W);
+  MI_REQUIRE(pattern >= MI_RGGB && pattern <= MI_BGGR, "%s: demosaic_directional: bad pattern %d", who, pattern);
+  a.green_par = (pattern == MI_RGGB || pattern == MI_BGGR) ? 1 : 0;
+  a.red_par = (pattern == MI_RGGB || pattern == MI_GRBG) ? 0 : 1;
+  a.has_ccm = ccm9 != nullptr;
+  for (int i = 0; i < 9; ++i) a.ccm[i] = ccm9 ? ccm9[i] : (i % 4 == 0 ? 1.f : 0.f);
+  a.out_scale = mi_scale_factor(out_dtype);
+  return 0;
+}
+
+extern "C" int mi_isp_demosaic_directional_cfa(const void* cfa, void* rgb, int H, int W, int in_dtype, int out_dtype,
+                                               int pattern, const float* ccm9, void* stream) {
+  const char* who = "demosaic_directional_cfa";
+  MI_REQUIRE(cfa && rgb, "%s: demosaic_directional: null pointer", who);
+  MI_REQUIRE(in_dtype == MI_F16 || in_dtype == MI_F32, "%s: demosaic_directional: the CFA must be f16 or f32 (dtype %d)", who,
+             in_dtype);
+  MI_REQUIRE(mi_valid_dtype(out_dtype), "%s: demosaic_directional: bad output dtype %d", who, out_dtype);
+  dd::Args a = {};
+  if (int rc = directional_settings(a, H, W, pattern, ccm9, out_dtype, who)) return rc;
+  a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
+  a.n_frames = 1;
+  a.f[0] = {cfa, rgb};
+  return dd::launch(a, in_dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, in_dtype, out_dtype, (hipStream_t)stream);
+}
+
+// n raw frames of one geometry through the demosaic (rgb) or the decode alone (!rgb): MAX_FRAMES frames per launch
+static int directional_raw_impl(const void* const* src, void* const* dst, int n, int H, int W, int kind, int ids_format,
+                                int work_dtype, int pattern, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                const float* ccm9, bool rgb, void* stream, const char* who) {
+  dd::Args a = {};
+  MI_REQUIRE(work_dtype == MI_F16 || work_dtype == MI_F32, "%s: demosaic_directional: work dtype must be f16 or f32 (dtype %d)",
+             who, work_dtype);
+  if (int rc = directional_settings(a, H, W, rgb ? pattern : MI_RGGB, ccm9, work_dtype, who)) return rc;
+  if (int rc = raw_kind(kind, kDirectional, who)) return rc;
+  MI_REQUIRE(n >= 0, "%s: demosaic_directional with %d frames", who, n);
+  if (int rc = raw_source_rules(H, W, kind, ids_format, shading, 0, kDirectional, who)) return rc;
+  int src_kind;
+  if (int rc = raw_source_setup(a, src_kind, H, W, kind, ids_format, levels, shading, nullptr, 0, kDirectional, who))
+    return rc;
+  if (n == 0) return 0;
+  MI_REQUIRE(src && dst, "%s: demosaic_directional: null frame list", who);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && dst[i], "%s: demosaic_directional: frame %d has a null pointer", who, i);
+    MI_REQUIRE(src[i] != dst[i], "%s: demosaic_directional: frame %d: the output must not overwrite its source", who, i);
+  }
+  for (int i0 = 0; i0 < n; i0 += dd::MAX_FRAMES) {
+    a.n_frames = n - i0 < dd::MAX_FRAMES ? n - i0 : dd::MAX_FRAMES;
+    for (int i = 0; i < a.n_frames; ++i) a.f[i] = {src[i0 + i], dst[i0 + i]};
+    if (int rc = rgb ? dd::launch(a, src_kind, work_dtype, work_dtype, (hipStream_t)stream)
+                     : dd::launch_cfa(a, src_kind, work_dtype, (hipStream_t)stream))
+      return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_demosaic_directional_raw_batch(const void* const* src, void* const* rgb, int n, int H, int W, int kind,
+                                                     int ids_format, int work_dtype, int pattern,
+                                                     const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                                     const float* ccm9, void* stream) {
+  return directional_raw_impl(src, rgb, n, H, W, kind, ids_format, work_dtype, pattern, levels, shading, ccm9, true, stream,
+                              "demosaic_directional_raw_batch");
+}
+
+extern "C" int mi_isp_raw_cfa_batch(const void* const* src, void* const* cfa, int n, int H, int W, int kind, int ids_format,
+                                    int work_dtype, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                    void* stream) {
+  return directional_raw_impl(src, cfa, n, H, W, kind, ids_format, work_dtype, MI_RGGB, levels, shading, nullptr, false, stream,
+                              "raw_cfa_batch");
 }
 
 // ---- chromatic aberration (isp_chromatic.h; DESIGN.md 3, "Chromatic aberration") --------------------------------------

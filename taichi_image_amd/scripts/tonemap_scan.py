@@ -203,6 +203,9 @@ def build_parser() -> argparse.ArgumentParser:
     # limited to the balanced clip level ("clip"); T the clip level in units of the white level (default 0.98)
     tone.add_argument("--highlights", dest="highlights", choices=("rebuild", "clip"), default=None)
     tone.add_argument("--highlights-clip", dest="highlights_clip", type=float, metavar="T", default=None)
+    # the demosaic (an extension): "directional" interpolates along edges instead of across them; "malvar" (the default)
+    # is the 13-tap filter
+    tone.add_argument("--demosaic", dest="demosaic", choices=("malvar", "directional"), default=None)
     # chromatic aberration (an extension): (k0, k1, k2) of the red and of the blue channel's radial scale, the optical
     # centre (default: the middle of the frame) and the normalisation radius (default: the half diagonal), in raw pixels
     tone.add_argument("--chromatic-aberration", dest="chromatic_aberration", type=float, nargs=6,
@@ -264,6 +267,7 @@ def main(argv=None) -> int:
     from ..lens import LensDistortion
     from ..denoise import RawDenoise
     from ..highlights import Highlights
+    from ..demosaic import Demosaic
     from ..chromatic import ChromaticAberration
     from ..temporal import TemporalDenoise, TemporalHistory
     from ..local_tonemap import LocalTonemap
@@ -358,7 +362,8 @@ def main(argv=None) -> int:
                               auto_white_balance=args.auto_white_balance, raw_denoise=denoise, sharpen=sharpen,
                               local_contrast=local_contrast, chroma_denoise=chroma_denoise, color_lut=color_lut,
                               highlights=highlights, chromatic_aberration=chromatic, temporal_denoise=temporal,
-                              local_tonemap=local_tonemap, luma_denoise=luma_denoise)
+                              local_tonemap=local_tonemap, luma_denoise=luma_denoise,
+                              demosaic=None if args.demosaic is None else Demosaic(args.demosaic))
     # temporal noise reduction: the state of each camera folder, for the whole scan
     histories = [TemporalHistory() if temporal is not None else None for _ in index.cameras]
     row_bytes = args.width * 3 // 2
