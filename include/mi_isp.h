@@ -617,6 +617,47 @@ int mi_isp_local_tonemap_batch(void* const* images_host, int n, int H, int W, in
                                const mi_isp_local_tonemap* settings_host, void* ws_dev, void* stream);
 int mi_isp_local_tonemap_grids(const void* image_dev, int H, int W, int dtype, const mi_isp_local_tonemap* settings_host,
                                uint32_t* cnt_dev, uint32_t* sum_dev, float* nb_dev, float* sb_dev, void* stream);
+/* ---- antialiased resize ("Antialiased resize") ---------------------------------------------------------
+ * A separable, table-driven resize of work-dtype RGB images (H x W x 3 interleaved, MI_F16 or MI_F32 in, MI_F16 or MI_F32
+ * out): one table per axis, built on the host; the kernel evaluates the tables and decides nothing itself.
+ * The table of an axis with S source and D output samples at scale s (output / source), every operation one IEEE double
+ * operation in the order written; filter MI_RESAMPLE_AREA / _TRIANGLE / _LANCZOS3:
+ *   widen = s < 1 ? 1 / s : 1;  c = d / s                                         (the geometry of mi_isp_resize_bilinear)
+ *   radius R = widen / 2 + 0.5 (area), widen (triangle), 3 * widen (lanczos3); candidates k = floor(c - R) .. ceil(c + R)
+ *   area, s < 1:    w = min(k + 0.5, c + widen / 2) - max(k - 0.5, c - widen / 2)
+ *   triangle, and area at s >= 1:  w = 1 - |k - c| / widen
+ *   lanczos3:       x = (k - c) / widen;  w = |x| < 3 ? sinc(x) * sinc(x / 3) : 0;  sinc(0) = 1, sinc of another integer
+ *                   is 0, else sinc(x) = sin(pi * x) / (pi * x) with pi * x one product
+ *   a candidate is a tap when w > 0 (area, triangle) or w != 0 (lanczos3); first / last: the lowest / highest tap index
+ *   T = min(max over d of (last - first + 1), S);  start[d] = min(max(first, 0), S - T)
+ *   row d: T doubles, zero; for the taps in increasing k: row[min(max(k, 0), S - 1) - start[d]] += w    (replicate border)
+ *   sum = ((row[0] + row[1]) + ...) + row[T - 1];  weight[d][j] = f32(row[j] / sum)
+ * so at s >= 1 area and triangle hold the bilinear weights (1 - frac, frac), and at s == 1 every filter is one tap of
+ * weight 1.  T <= 32, or the filter does not take the scale.
+ * The image, f32 with one rounding per operation and no contraction, per channel:
+ *   h[y][x] = (..((wx[x][0] * f32(src[y][sx[x]])) + wx[x][1] * f32(src[y][sx[x] + 1])) + ..) over the Tx taps in order
+ *   o[r][x] = the same over h[sy[r] + j][x] with wy[r][j], j = 0 .. Ty - 1;  dst[r][x] = cast(o[r][x])
+ * h is never rounded to f16, a zero weight still multiplies its (padded) tap, and nothing is clamped.
+ *  - mi_isp_resample_taps: T of the axis (host only, nothing is launched), or -1 with the error set (a bad filter, S or D
+ *    not positive, a scale that is not finite and > 0, T > 32: the text names the filter and the smallest scale it takes).
+ *  - mi_isp_resample_table: the table of the axis into start_host (D int32) and weight_host (D x T f32); host only.
+ *  - mi_isp_resample_batch: n images of one geometry in ONE launch per 32 images, both passes in it (the horizontally
+ *    filtered rows exist in LDS only).  rows / cols: the tables of the vertical (S = Hs, D = Hd) and the horizontal axis on
+ *    the device, 0 <= start[d] <= S - taps (the kernel clamps a start into that range, so no table makes it read
+ *    outside the image; starts that do not rise with d are evaluated all the same, tap by tap from memory).  srcs_host / dsts_host: n device pointers each, read on the host, each
+ *    aligned to its element; an output must not overlap a source.
+ * Host-side checks before any launch (error text names "resample"): NULL pointers, n < 0, sizes that are not positive
+ * (Hd or Wd == 0 and n == 0 are successful no-ops that launch nothing), taps outside 1 .. min(32, S), the dtypes. */
+#define MI_RESAMPLE_AREA 1
+#define MI_RESAMPLE_TRIANGLE 2
+#define MI_RESAMPLE_LANCZOS3 3
+#define MI_RESAMPLE_MAX_TAPS 32
+typedef struct { int32_t taps; const int32_t* start_dev; const float* weight_dev; } mi_isp_resample_axis;
+int mi_isp_resample_taps(int filter, int S, int D, double scale);
+int mi_isp_resample_table(int filter, int S, int D, double scale, int32_t* start_host, float* weight_host);
+int mi_isp_resample_batch(const void* const* srcs_host, void* const* dsts_host, int n, int Hs, int Ws, int Hd, int Wd,
+                          int in_dtype, int out_dtype, const mi_isp_resample_axis* rows_host,
+                          const mi_isp_resample_axis* cols_host, void* stream);
 /* ---- output sharpening ("Output sharpening") ----------------------------------------------------------
  * An unsharp mask on the luma of a u8 image, in integer arithmetic: the output is the contract's bit for bit.  All values
  * signed 32-bit, >> arithmetic, coordinates outside the image clamped to the edge; b = (1, 2, 1) for radius 1 and

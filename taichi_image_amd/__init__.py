@@ -6,9 +6,10 @@ mirror the modules of uc-vision/taichi_image; every op dispatches through ctypes
 libmi355_isp.so (hand-written HIP for gfx950).  There is no CPU fallback.
 """
 from . import types  # noqa: F401
-from . import packed, bayer, interpolate, tonemap, camera_isp, pipeline, distributed, color, ingest, defects, lens, white_balance, denoise, sharpen, local_contrast, chroma_denoise, luma_denoise, color_lut, highlights, chromatic, temporal, exposure_merge, local_tonemap, demosaic  # noqa: F401
+from . import packed, bayer, interpolate, tonemap, camera_isp, pipeline, distributed, color, ingest, defects, lens, white_balance, denoise, sharpen, local_contrast, chroma_denoise, luma_denoise, color_lut, highlights, chromatic, temporal, exposure_merge, local_tonemap, demosaic, resample  # noqa: F401
 from .bayer import BayerPattern  # noqa: F401
 from .demosaic import Demosaic  # noqa: F401
+from .resample import Resample, check_resample  # noqa: F401
 from .interpolate import ImageTransform  # noqa: F401
 from .camera_isp import Camera16, Camera32  # noqa: F401
 from .defects import DefectMap, find_defects  # noqa: F401

@@ -110,6 +110,12 @@ class LumaDenoise(ctypes.Structure):
     _fields_ = [("radius", c_int32), ("threshold", c_int32), ("threshold_bright", c_int32), ("strength_q6", c_int32)]
 
 
+class ResampleAxis(ctypes.Structure):
+    """mi_isp_resample_axis: the table of one axis of the antialiased resize: its taps, and the starts (D int32) and the
+    weights (D x taps f32) on the device."""
+    _fields_ = [("taps", c_int32), ("start_dev", c_void_p), ("weight_dev", c_void_p)]
+
+
 class ColorLut(ctypes.Structure):
     """mi_isp_color_lut: the table's points per axis (2 .. 65) and the strength times 64 (0 .. 64)."""
     _fields_ = [("n_points", c_int32), ("strength_q6", c_int32)]
@@ -243,6 +249,10 @@ SIGNATURES = {
     "mi_isp_local_tonemap_workspace_bytes": (c_size_t, [c_int, c_int, c_int, POINTER(LocalTonemap)]),
     "mi_isp_local_tonemap_batch": (c_int, [POINTER(_P), c_int, c_int, c_int, c_int, POINTER(LocalTonemap), _P, _P]),
     "mi_isp_local_tonemap_grids": (c_int, [_P, c_int, c_int, c_int, POINTER(LocalTonemap), _P, _P, _P, _P, _P]),
+    "mi_isp_resample_taps": (c_int, [c_int, c_int, c_int, c_double]),
+    "mi_isp_resample_table": (c_int, [c_int, c_int, c_int, c_double, _P, _P]),
+    "mi_isp_resample_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      POINTER(ResampleAxis), POINTER(ResampleAxis), _P]),
     "mi_isp_chroma_denoise_rgb_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise), _P]),
     "mi_isp_chroma_denoise_yuv420_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, POINTER(ChromaDenoise),
                                                    _P]),

@@ -34,6 +34,7 @@ from . import color_lut as _clut
 from . import local_contrast as _lc
 from . import local_tonemap as _ltm
 from . import demosaic as _dm
+from . import resample as _rs
 from . import white_balance as _wb
 from . import distributed as _dist
 
@@ -300,7 +301,8 @@ def camera_isp(name: str, dtype=types.f32):
                      exposure_merge=None,
                      local_tonemap=None,
                      luma_denoise=None,
-                     demosaic=None):
+                     demosaic=None,
+                     resample=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -328,6 +330,7 @@ def camera_isp(name: str, dtype=types.f32):
             luma_denoise = _ydn.check_luma_denoise(luma_denoise)
             color_lut = _clut.check_color_lut(color_lut)
             demosaic = _dm.check_demosaic(demosaic)
+            resample = _rs.check_resample(resample)
 
             self.bayer_pattern = bayer_pattern
             # reference_quirks=True: demosaic as the reference does - ISP._process_image calls bayer_to_rgb WITHOUT its
@@ -413,6 +416,9 @@ def camera_isp(name: str, dtype=types.f32):
             # the demosaic (an extension): the Demosaic every loader demosaics with, or None (the 13-tap filter: the loaders
             # run exactly as without it).  DESIGN.md 3, "Directional demosaic".
             self._demosaic = demosaic
+            # the resize (an extension): the Resample every loader resizes with, or None (the bilinear resize: the loaders
+            # run exactly as without it).  DESIGN.md 3, "Antialiased resize".
+            self._resample = resample
 
         @property
         def _demosaic_pattern(self):
@@ -427,7 +433,7 @@ def camera_isp(name: str, dtype=types.f32):
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
                 highlights=None, chromatic_aberration=None, temporal_denoise=None, exposure_merge=None,
-                local_tonemap=None, luma_denoise=None, demosaic=None):
+                local_tonemap=None, luma_denoise=None, demosaic=None, resample=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -449,7 +455,8 @@ def camera_isp(name: str, dtype=types.f32):
             exposure_merge (the extension): None leaves it, False turns it off, an ExposureMerge replaces it.
             local_tonemap (the extension): None leaves it, False turns it off, a LocalTonemap replaces it.
             luma_denoise (the extension): None leaves it, False turns it off, a LumaDenoise replaces it.
-            demosaic (the extension): None leaves it, False turns it off, a Demosaic replaces it."""
+            demosaic (the extension): None leaves it, False turns it off, a Demosaic replaces it.
+            resample (the extension): None leaves it, False turns it off, a Resample replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -476,6 +483,7 @@ def camera_isp(name: str, dtype=types.f32):
                        else _ydn.check_luma_denoise(luma_denoise))
             new_clut = None if color_lut is None or color_lut is False else _clut.check_color_lut(color_lut)
             new_dm = None if demosaic is None or demosaic is False else _dm.check_demosaic(demosaic)
+            new_rs = None if resample is None or resample is False else _rs.check_resample(resample)
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -565,6 +573,10 @@ def camera_isp(name: str, dtype=types.f32):
                 self._demosaic = None
             elif new_dm is not None:
                 self._demosaic = new_dm
+            if resample is False:
+                self._resample = None
+            elif new_rs is not None:
+                self._resample = new_rs
             if auto_white_balance is not None:
                 if awb is None:
                     self._awb_off()
@@ -781,6 +793,35 @@ def camera_isp(name: str, dtype=types.f32):
             return self._demosaic is not None and self._demosaic.is_directional
 
         @property
+        def resample(self) -> Optional[_rs.Resample]:
+            """The Resample the loaders resize with, or None (the bilinear resize)."""
+            return self._resample
+
+        def _antialiased(self):
+            """True when the loaders' resize is the antialiased one: a filter other than "bilinear" and a resize set
+            (Resample("bilinear"), or no resize, is as without the option)."""
+            return (self._resample is not None and not self._resample.is_bilinear
+                    and (self.resize_width > 0 or self.scale is not None))
+
+        def _resampled(self, rgbs):
+            """The full-resolution work-dtype images rgbs of one shape resized to the ISP's resize geometry by the
+            antialiased resize, in ONE launch.  DESIGN.md 3, "Antialiased resize"."""
+            if not rgbs:
+                return rgbs
+            h, w = rgbs[0].shape[:2]
+            hd, wd, scale = self._geometry(h, w)
+            outs = [torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device) for _ in rgbs]
+            _rs.apply(rgbs, outs, self._resample.filter, h, w, hd, wd, scale, scale, dtype.code, dtype.code, self.device)
+            return outs
+
+        def _check_resample_fits(self, shape):
+            """ValueError when the antialiased resize does not take the ISP's scale on a frame of `shape` (before
+            anything is uploaded or launched)."""
+            if self._antialiased():
+                hd, wd, scale = self._geometry(*shape)
+                _rs.check_geometry(self._resample.filter, shape[0], shape[1], hd, wd, scale, scale)
+
+        @property
         def local_tonemap(self) -> Optional[_ltm.LocalTonemap]:
             """The LocalTonemap the loaders apply to the images they return, or None."""
             return self._ltm
@@ -879,6 +920,8 @@ def camera_isp(name: str, dtype=types.f32):
             if self.resize_width <= 0 and self.scale is None:
                 return image
             hd, wd, scale = self._geometry(*image.shape[:2])
+            if self._antialiased():
+                return interpolate.resample(image, (wd, hd), scale, self._resample.filter)
             return interpolate.resize_bilinear(image, (wd, hd), scale)
 
         def _convert(self, image, mode, src_dtype, defects=None, undistort=None, history=None):
@@ -897,6 +940,7 @@ def camera_isp(name: str, dtype=types.f32):
             if self._chromatic is not None:
                 self._chromatic.check_shape((h, w))      # (before anything is uploaded or launched)
             hists = _tn.check_histories(self._temporal, None if history is None else [history], 1, (h, w), self.device)
+            self._check_resample_fits((h, w))
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             src = image.to(self.device).contiguous()
@@ -932,17 +976,27 @@ def camera_isp(name: str, dtype=types.f32):
             output shape than the loader's."""
             if undistort is None:
                 return None
+            if self._antialiased():
+                # the remap runs at the frame's own size and scale 1, and the antialiased resize follows
+                if undistort.is_table and tuple(undistort.table_shape) != tuple(shape):
+                    raise ValueError(f"with resample={self._resample.filter!r} the lens remap runs at the frame's own "
+                                     f"size before the resize: a lens table must have the frame's shape {tuple(shape)}, "
+                                     f"got {tuple(undistort.table_shape)}")
+                return _lens.check_lens(undistort, shape, tuple(shape))
             return _lens.check_lens(undistort, shape, self._geometry(*shape)[:2])
 
-        def _undistort(self, rgbs, lenses, h, w):
+        def _undistort(self, rgbs, lenses, h, w, full=False):
             """The full-resolution work-dtype images rgbs remapped through lenses (one each, none None) into new images
-            at the ISP's resize geometry, at scale 1 without a resize (one launch for the analytic lenses)."""
-            hd, wd, scale = self._geometry(h, w)
+            at the ISP's resize geometry, at scale 1 without a resize (one launch for the analytic lenses).  With the
+            antialiased resize the remap runs at the frame's own size and scale 1 and the resize follows; full: the
+            caller resizes (all images of its call in one launch)."""
+            hd, wd, scale = (h, w, 0.0) if self._antialiased() else self._geometry(h, w)
             scale = scale or 1.0                         # (no resize: the remap at scale 1)
             outs = [torch.empty((hd, wd, 3), dtype=torch_dtype, device=self.device) for _ in rgbs]
             if hd * wd:
                 _lens.apply(lenses, rgbs, outs, h, w, hd, wd, scale, scale, dtype.code, dtype.code, self.device)
-            return outs
+            # (the antialiased resize: the remap above ran at the frame's own size and scale 1, the resize follows)
+            return self._resampled(outs) if self._antialiased() and not full else outs
 
         def _fix_defects(self, srcs, rgbs, subs, maps, h, w, bits, ids_format, hd, wd, scale, lv, sh):
             """The sparse fix-up after a packed load on the same stream: every output pixel of rgbs[i] (and its metering
@@ -1014,15 +1068,26 @@ def camera_isp(name: str, dtype=types.f32):
                 raise ValueError(f"history must be None or a list with one TemporalHistory per frame, got "
                                  f"{type(history).__name__}")
             hists = _tn.check_histories(self._temporal, history, len(frames), (h, w), self.device)
+            self._check_resample_fits((h, w))
             srcs = [d.to(self.device).contiguous() for d in frames]
+            aa = self._antialiased()                     # (every route below then stays at full resolution)
             if self._raw_stage_on():
                 # the raw stages - highlight reconstruction, chromatic aberration, temporal noise reduction, raw noise
                 # reduction - that are on: one launch each, then per frame
                 kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
                 cfas = self._raw_chain(srcs, h, w, kind, ids_format, lv, maps, hists)
-                rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
+                rgbs = [(self._process_full if aa else self._process_image)(c, m) for c, m in zip(cfas, lenses)]
             elif self._directional():
-                rgbs = self._load_directional(srcs, h, w, bits, ids_format, lv, maps, lenses)
+                rgbs = self._load_directional(srcs, h, w, bits, ids_format, lv, maps, lenses, keep_size=aa)
+            elif aa:
+                # the antialiased resize: the frames loaded at full resolution in one launch, without the fused resize and
+                # the fused metering subsample, the defect fix-up on those images, then each lens remap at the frame's size
+                rgbs = self._load_frames(srcs, h, w, bits, ids_format, lv, maps, True, full=True)
+                rest = [i for i, m in enumerate(lenses) if m is not None]
+                if rest:
+                    for i, out in zip(rest, self._undistort([rgbs[i] for i in rest], [lenses[i] for i in rest], h, w,
+                                                            full=True)):
+                        rgbs[i] = out
             elif lenses.count(None) < len(lenses):       # (some frame has a lens)
                 # lens distortion: the frames without a lens as the call without lenses, the others loaded at full
                 # resolution in one launch and remapped
@@ -1036,10 +1101,12 @@ def camera_isp(name: str, dtype=types.f32):
                 rgbs = [out[i] for i in range(len(srcs))]
             else:
                 rgbs = self._load_frames(srcs, h, w, bits, ids_format, lv, maps, batch)
+            if aa:
+                rgbs = self._resampled(rgbs)             # (all images of the call in ONE launch)
             self._awb_stats_packed(srcs, h, w, bits, ids_format, lv)     # auto white balance: the statistics of the sources
             return self._tone_mapped(rgbs)
 
-        def _load_directional(self, srcs, h, w, bits, ids_format, lv, maps, lenses):
+        def _load_directional(self, srcs, h, w, bits, ids_format, lv, maps, lenses, keep_size=False):
             """The packed loaders' route with the directional demosaic and no raw stage on: the frames without a defect map
             go from packed bytes to the full-resolution image in ONE launch (mi_isp_demosaic_directional_raw_batch: the
             CFA exists in LDS only); a frame with a map is decoded to its CFA (one launch for all of them), fixed in place
@@ -1059,7 +1126,10 @@ def camera_isp(name: str, dtype=types.f32):
                     _native.ptr_array([srcs[i] for i in plain]), _native.ptr_array(full), len(plain), h, w, kind, ids,
                     dtype.code, self._demosaic_pattern.value, lv, sh, _native.ccm_arg(self.color_correct_matrix), stream))
                 for i, rgb in zip(plain, full):
-                    out[i] = self.resize_image(rgb) if lenses[i] is None else self._undistort([rgb], [lenses[i]], h, w)[0]
+                    if lenses[i] is not None:
+                        out[i] = self._undistort([rgb], [lenses[i]], h, w, full=keep_size)[0]
+                    else:
+                        out[i] = rgb if keep_size else self.resize_image(rgb)
             if mapped:
                 cfas = [torch.empty((h, w), dtype=torch_dtype, device=self.device) for _ in mapped]
                 _native.check(L.mi_isp_raw_cfa_batch(_native.ptr_array([srcs[i] for i in mapped]), _native.ptr_array(cfas),
@@ -1067,7 +1137,7 @@ def camera_isp(name: str, dtype=types.f32):
                 for i, cfa in zip(mapped, cfas):
                     _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, maps[i]._arg(self.device),
                                                            stream))
-                    out[i] = self._process_image(cfa, lenses[i])
+                    out[i] = (self._process_full if keep_size else self._process_image)(cfa, lenses[i])
             return [out[i] for i in range(len(srcs))]
 
         def _load_frames(self, srcs, h, w, bits, ids_format, lv, maps, batch, full=False):
@@ -1223,11 +1293,15 @@ def camera_isp(name: str, dtype=types.f32):
             if self._chromatic is not None:
                 self._chromatic.check_shape((h, w))
             hists = _tn.check_histories(self._temporal, history, n, (h, w), self.device)
+            self._check_resample_fits((h, w))
             srcs = [[f.to(self.device).contiguous() for f in b] for b in brackets]
             first = [b[0] for b in srcs]
             kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
             cfas = self._raw_chain(first, h, w, kind, ids_format, lv, maps, hists, brackets=srcs)
-            rgbs = [self._process_image(c, m) for c, m in zip(cfas, lenses)]
+            aa = self._antialiased()                     # (the images stay at full resolution, one resize launch for all)
+            rgbs = [(self._process_full if aa else self._process_image)(c, m) for c, m in zip(cfas, lenses)]
+            if aa:
+                rgbs = self._resampled(rgbs)
             self._awb_stats_packed(first, h, w, bits, ids_format, lv)    # auto white balance: each bracket's frame 0
             return self._tone_mapped(rgbs)
 
@@ -1270,13 +1344,22 @@ def camera_isp(name: str, dtype=types.f32):
                 return cc
             return None
 
+        def _demosaiced(self, cfa):
+            demosaic = _dm.directional if self._directional() else bayer.bayer_to_rgb
+            return demosaic(cfa, pattern=self._demosaic_pattern, correct_colors=self.color_correct_matrix)
+
         def _process_image(self, cfa, lens=None):
             """camera_isp.py:371-373; with a lens the full-resolution image is remapped at the resize geometry."""
-            demosaic = _dm.directional if self._directional() else bayer.bayer_to_rgb
-            rgb = demosaic(cfa, pattern=self._demosaic_pattern, correct_colors=self.color_correct_matrix)
+            rgb = self._demosaiced(cfa)
             if lens is not None:
                 return self._undistort([rgb], [lens], *cfa.shape)[0]
             return self.resize_image(rgb)
+
+        def _process_full(self, cfa, lens=None):
+            """_process_image without the resize (the antialiased resize: the caller resizes all images of its call in one
+            launch); a lens remaps at the frame's own size."""
+            rgb = self._demosaiced(cfa)
+            return rgb if lens is None else self._undistort([rgb], [lens], *cfa.shape, full=True)[0]
 
         def _metering_images(self, images, t, prev, stride=None):
             """camera_isp.py:168-175: statistics of the stride-subsampled images, blended into a

@@ -26,6 +26,7 @@
 #include "isp_color_lut.h"
 #include "isp_local_contrast.h"
 #include "isp_local_tonemap.h"
+#include "isp_resample.h"
 #include <mutex>
 #include <atomic>
 
@@ -1435,6 +1436,57 @@ extern "C" int mi_isp_local_tonemap_grids(const void* image, int H, int W, int d
   a.cnt = cnt; a.sum = sum; a.nb = nb; a.sb = sb;
   a.im[0] = const_cast<void*>(image);
   return ltm::launch(a, dtype, 0, 1, (hipStream_t)stream);
+}
+
+// ---- antialiased resize (isp_resample.h; DESIGN.md 3, "Antialiased resize") -----------------------------------------
+extern "C" int mi_isp_resample_taps(int filter, int S, int D, double scale) {
+  return rs::taps(filter, S, D, scale, "resample_taps");
+}
+
+extern "C" int mi_isp_resample_table(int filter, int S, int D, double scale, int32_t* start, float* weight) {
+  return rs::table(filter, S, D, scale, start, weight, "resample_table");
+}
+
+static int resample_axis(const mi_isp_resample_axis* t, int S, const char* what, const char* who) {
+  MI_REQUIRE(t, "%s: null resample %s table", who, what);
+  MI_REQUIRE(t->taps >= 1 && t->taps <= rs::MAX_TAPS && t->taps <= S, "%s: resample %s table with %d taps outside "
+             "1 .. min(%d, %d source samples)", who, what, (int)t->taps, rs::MAX_TAPS, S);
+  MI_REQUIRE(t->start_dev && t->weight_dev, "%s: resample %s table without starts or weights", who, what);
+  MI_REQUIRE(mi_aligned(t->start_dev, 4) && mi_aligned(t->weight_dev, 4), "%s: resample %s table not 4-byte aligned", who,
+             what);
+  return 0;
+}
+
+// n images of one geometry: every image's pointers in the kernel arguments, 32 per launch
+extern "C" int mi_isp_resample_batch(const void* const* srcs, void* const* dsts, int n, int Hs, int Ws, int Hd, int Wd,
+                                     int in_dtype, int out_dtype, const mi_isp_resample_axis* rows,
+                                     const mi_isp_resample_axis* cols, void* stream) {
+  const char* who = "resample_batch";
+  MI_REQUIRE(n >= 0, "%s: resample with %d images", who, n);
+  MI_REQUIRE(Hs > 0 && Ws > 0 && Hs <= 32768 && Ws <= 32768, "%s: resample source %d x %d outside 1 .. 32768", who, Hs, Ws);
+  MI_REQUIRE(Hd >= 0 && Wd >= 0 && Hd <= 32768 && Wd <= 32768, "%s: resample output %d x %d outside 0 .. 32768", who, Hd, Wd);
+  MI_REQUIRE((in_dtype == MI_F16 || in_dtype == MI_F32) && (out_dtype == MI_F16 || out_dtype == MI_F32),
+             "%s: resample takes MI_F16 / MI_F32 images, got dtypes %d -> %d", who, in_dtype, out_dtype);
+  if (int rc = resample_axis(rows, Hs, "row", who)) return rc;
+  if (int rc = resample_axis(cols, Ws, "column", who)) return rc;
+  if (n == 0 || (size_t)Hd * (size_t)Wd == 0) return 0;
+  MI_REQUIRE(srcs && dsts, "%s: null resample image list", who);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(srcs[i] && dsts[i], "%s: resample image %d has a null pointer", who, i);
+    MI_REQUIRE(mi_aligned(srcs[i], mi_dtype_size(in_dtype)) && mi_aligned(dsts[i], mi_dtype_size(out_dtype)),
+               "%s: resample image %d not aligned to its element", who, i);
+    MI_REQUIRE(srcs[i] != dsts[i], "%s: resample image %d: the filter cannot run in place", who, i);
+  }
+  rs::Args a = {};
+  a.Hs = Hs; a.Ws = Ws; a.Hd = Hd; a.Wd = Wd;
+  a.rows = {rows->taps, rows->start_dev, rows->weight_dev};
+  a.cols = {cols->taps, cols->start_dev, cols->weight_dev};
+  for (int i0 = 0; i0 < n; i0 += rs::MAX_IMAGES) {
+    a.n_images = n - i0 < rs::MAX_IMAGES ? n - i0 : rs::MAX_IMAGES;
+    for (int i = 0; i < a.n_images; ++i) a.im[i] = {srcs[i0 + i], dsts[i0 + i]};
+    if (int rc = rs::launch(a, in_dtype, out_dtype, (hipStream_t)stream)) return rc;
+  }
+  return 0;
 }
 
 // ---- output sharpening (isp_sharpen.h; DESIGN.md 3, "Output sharpening") ---------------------------------------------

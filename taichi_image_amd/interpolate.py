@@ -82,6 +82,34 @@ def resize_bilinear(src, size, scale=None, dtype=None):
     return types.from_device(dst, src)
 
 
+def resample(src, size, scale=None, filter="area", dtype=None):
+    """The antialiased resize of an (H, W, 3) f16 or f32 image (an extension; DESIGN.md 3, "Antialiased resize"): the
+    separable, table-driven resize of `resample.py` with filter "area", "triangle" or "lanczos3" ("bilinear": exactly
+    resize_bilinear at that size and scale).  size = (w, h); scale: a scalar or (row_scale, col_scale), None for
+    (h / H, w / W) - geometrically correct, as undistort, not resize_bilinear's crossed axes.  The geometry is
+    resize_bilinear's (output index d is centred on source coordinate d / scale), the container rule and the dtype
+    handling too; integer images and a scale the filter does not take raise ValueError.  Nothing is clamped."""
+    from . import resample as _rs
+    _rs.check_filter(filter)
+    in_dtype = _rs.float_dtype(src, "resample")
+    out_dtype = _rs.out_float_dtype(dtype, in_dtype, "resample")
+    assert src.ndim == 3 and src.shape[2] == 3, "image must be (H, W, 3)"
+    Hs, Ws = src.shape[:2]
+    Wd, Hd = int(size[0]), int(size[1])
+    if Wd < 0 or Hd < 0:
+        raise ValueError(f"size {tuple(size)} must not be negative")
+    if Hs <= 0 or Ws <= 0:
+        raise ValueError(f"resample of an empty {Hs} x {Ws} image")
+    s0, s1 = (Hd / Hs, Wd / Ws) if scale is None else _scale2(scale)
+    if filter == "bilinear":
+        return resize_bilinear(src, (Wd, Hd), (s0, s1), dtype)
+    _rs.check_geometry(filter, Hs, Ws, Hd, Wd, s0, s1)
+    dev = types.to_device(src)
+    dst = torch.empty((Hd, Wd, 3), dtype=out_dtype.torch, device=dev.device)
+    _rs.apply([dev], [dst], filter, Hs, Ws, Hd, Wd, s0, s1, in_dtype.code, out_dtype.code, dev.device)
+    return types.from_device(dst, src)
+
+
 def resize_width(src, width: int, dtype=None):
     """interpolate.py:141-145 (height truncated with int())."""
     h, w = src.shape[:2]

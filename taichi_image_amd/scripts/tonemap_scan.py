@@ -206,6 +206,9 @@ def build_parser() -> argparse.ArgumentParser:
     # the demosaic (an extension): "directional" interpolates along edges instead of across them; "malvar" (the default)
     # is the 13-tap filter
     tone.add_argument("--demosaic", dest="demosaic", choices=("malvar", "directional"), default=None)
+    # the resize of --resize-width (an extension): "area", "triangle" and "lanczos3" widen with the downscale, so the
+    # resized images do not alias; "bilinear" (the default) is the point-sampled resize
+    tone.add_argument("--resample", dest="resample", choices=("bilinear", "area", "triangle", "lanczos3"), default=None)
     # chromatic aberration (an extension): (k0, k1, k2) of the red and of the blue channel's radial scale, the optical
     # centre (default: the middle of the frame) and the normalisation radius (default: the half diagonal), in raw pixels
     tone.add_argument("--chromatic-aberration", dest="chromatic_aberration", type=float, nargs=6,
@@ -268,6 +271,7 @@ def main(argv=None) -> int:
     from ..denoise import RawDenoise
     from ..highlights import Highlights
     from ..demosaic import Demosaic
+    from ..resample import Resample
     from ..chromatic import ChromaticAberration
     from ..temporal import TemporalDenoise, TemporalHistory
     from ..local_tonemap import LocalTonemap
@@ -363,7 +367,8 @@ def main(argv=None) -> int:
                               local_contrast=local_contrast, chroma_denoise=chroma_denoise, color_lut=color_lut,
                               highlights=highlights, chromatic_aberration=chromatic, temporal_denoise=temporal,
                               local_tonemap=local_tonemap, luma_denoise=luma_denoise,
-                              demosaic=None if args.demosaic is None else Demosaic(args.demosaic))
+                              demosaic=None if args.demosaic is None else Demosaic(args.demosaic),
+                              resample=None if args.resample is None else Resample(args.resample))
     # temporal noise reduction: the state of each camera folder, for the whole scan
     histories = [TemporalHistory() if temporal is not None else None for _ in index.cameras]
     row_bytes = args.width * 3 // 2
