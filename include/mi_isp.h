@@ -463,7 +463,9 @@ int mi_isp_highlights_cfa(const void* in_dev, void* out_dev, int H, int W, int d
  *    output is in the work dtype.  One launch per 32 frames.
  *  - mi_isp_raw_cfa_batch: the decode alone: that CFA, H x W of the work dtype, written to cfa_host[i].
  * Host-side checks before any launch (error text names "demosaic_directional"): NULL pointers, odd or non-positive sizes,
- * dtypes, the pattern, the kind, n < 0, levels and grids.  n == 0 is a successful no-op. */
+ * dtypes, the pattern, the kind, n < 0, levels and grids, and an output, a CFA or a typed source (MI_RAW_16U, MI_RAW_16F,
+ * MI_RAW_32F) that is not aligned to its element (packed bytes stand anywhere).  An output that is aligned to its element
+ * only is stored element by element.  n == 0 is a successful no-op. */
 int mi_isp_demosaic_directional_cfa(const void* cfa_dev, void* rgb_dev, int H, int W, int in_dtype, int out_dtype,
                                     int pattern, const float* ccm9_host, void* stream);
 int mi_isp_demosaic_directional_raw_batch(const void* const* srcs_host, void* const* rgbs_host, int n, int H, int W,

@@ -911,6 +911,8 @@ extern "C" int mi_isp_demosaic_directional_cfa(const void* cfa, void* rgb, int H
   MI_REQUIRE(in_dtype == MI_F16 || in_dtype == MI_F32, "%s: demosaic_directional: the CFA must be f16 or f32 (dtype %d)", who,
              in_dtype);
   MI_REQUIRE(mi_valid_dtype(out_dtype), "%s: demosaic_directional: bad output dtype %d", who, out_dtype);
+  MI_REQUIRE(mi_aligned(cfa, mi_dtype_size(in_dtype)) && mi_aligned(rgb, mi_dtype_size(out_dtype)),
+             "%s: demosaic_directional: the CFA or the image not aligned to its element", who);
   dd::Args a = {};
   if (int rc = directional_settings(a, H, W, pattern, ccm9, out_dtype, who)) return rc;
   a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
@@ -935,8 +937,12 @@ static int directional_raw_impl(const void* const* src, void* const* dst, int n,
     return rc;
   if (n == 0) return 0;
   MI_REQUIRE(src && dst, "%s: demosaic_directional: null frame list", who);
+  // a typed source (16U, 16F: 2 bytes; 32F: 4) and the output stand on their element; packed bytes stand anywhere
+  const size_t src_align = kind == MI_RAW_32F ? 4 : (kind == MI_RAW_16U || kind == MI_RAW_16F ? 2 : 1);
   for (int i = 0; i < n; ++i) {
     MI_REQUIRE(src[i] && dst[i], "%s: demosaic_directional: frame %d has a null pointer", who, i);
+    MI_REQUIRE(mi_aligned(src[i], src_align) && mi_aligned(dst[i], mi_dtype_size(work_dtype)),
+               "%s: demosaic_directional: frame %d not aligned to its element", who, i);
     MI_REQUIRE(src[i] != dst[i], "%s: demosaic_directional: frame %d: the output must not overwrite its source", who, i);
   }
   for (int i0 = 0; i0 < n; i0 += dd::MAX_FRAMES) {

@@ -265,6 +265,20 @@ def test_c_entry_points_reject_bad_arguments_before_any_launch():
         # n == 0 is a successful no-op, whatever the lists
         assert fn(n=0) == 0 and fn(n=0, srcs=None, dsts=None) == 0
     rejected(raw(pattern=7), "bad pattern 7")
+    # a pointer that is not aligned to its element (made-up addresses inside a and b: nothing is launched)
+    off = lambda p, n: ctypes.c_void_p(p.value + n)  # noqa: E731
+    U16 = _native.MI_U16
+    for o, n in ((F32, 1), (F32, 2), (F16, 1), (U16, 1), (F16, 3)):
+        rejected(cfa(dst=off(pb, n), o=o), "the CFA or the image not aligned to its element")
+    for i, n in ((F32, 2), (F16, 1)):
+        rejected(cfa(src=off(pa, n), i=i), "the CFA or the image not aligned to its element")
+    for fn in (raw, dec):
+        for work, n in ((F32, 2), (F32, 1), (F16, 1)):
+            rejected(fn(dsts=(ctypes.c_void_p * 1)(off(pb, n)), work=work), "frame 0 not aligned to its element")
+        for kind, n in ((_native.MI_RAW_32F, 2), (_native.MI_RAW_16U, 1), (_native.MI_RAW_16F, 1)):
+            rejected(fn(srcs=(ctypes.c_void_p * 1)(off(pa, n)), kind=kind), "frame 0 not aligned to its element")
+        two = (ctypes.c_void_p * 2)(pa, off(pa, 34))
+        rejected(fn(srcs=two, dsts=(ctypes.c_void_p * 2)(pb, off(pb, 32)), n=2), "frame 1 not aligned to its element")
     assert L.mi_isp_version() == 1900
 
 
