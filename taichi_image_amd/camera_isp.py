@@ -38,6 +38,23 @@ from . import resample as _rs
 from . import white_balance as _wb
 from . import distributed as _dist
 
+# the optional stages of Camera16 / Camera32: (constructor / set() argument, attribute, checker), in the order set() checks them
+_OPTIONAL_STAGES = (
+    ("raw_denoise", "_raw_denoise", _dn.check_raw_denoise),
+    ("highlights", "_highlights", _hl.check_highlights),
+    ("chromatic_aberration", "_chromatic", _ca.check_chromatic_aberration),
+    ("temporal_denoise", "_temporal", _tn.check_temporal_denoise),
+    ("exposure_merge", "_merge", _em.check_exposure_merge),
+    ("local_tonemap", "_ltm", _ltm.check_local_tonemap),
+    ("sharpen", "_sharpen", _shp.check_sharpen),
+    ("local_contrast", "_local_contrast", _lc.check_local_contrast),
+    ("chroma_denoise", "_chroma_denoise", _cdn.check_chroma_denoise),
+    ("luma_denoise", "_luma_denoise", _ydn.check_luma_denoise),
+    ("color_lut", "_color_lut", _clut.check_color_lut),
+    ("demosaic", "_demosaic", _dm.check_demosaic),
+    ("resample", "_resample", _rs.check_resample),
+)
+
 default_cc = np.array([      # camera_isp.py:230-234
     [1.75, -0.25, -0.30],
     [-0.10, 1.40, -0.30],
@@ -464,26 +481,14 @@ def camera_isp(name: str, dtype=types.f32):
             awb = self._awb if auto_white_balance is None else _wb.check_auto_white_balance(auto_white_balance)
             if awb is not None and (auto_white_balance is not None or white_balance is not None):
                 _wb.check_seed(self.white_balance if white_balance is None else white_balance)
-            denoise = None if raw_denoise is None or raw_denoise is False else _dn.check_raw_denoise(raw_denoise)
-            new_hl = None if highlights is None or highlights is False else _hl.check_highlights(highlights)
-            new_ca = (None if chromatic_aberration is None or chromatic_aberration is False
-                      else _ca.check_chromatic_aberration(chromatic_aberration))
-            new_tn = (None if temporal_denoise is None or temporal_denoise is False
-                      else _tn.check_temporal_denoise(temporal_denoise))
-            new_em = (None if exposure_merge is None or exposure_merge is False
-                      else _em.check_exposure_merge(exposure_merge))
-            new_ltm = (None if local_tonemap is None or local_tonemap is False
-                       else _ltm.check_local_tonemap(local_tonemap))
-            new_sharpen = None if sharpen is None or sharpen is False else _shp.check_sharpen(sharpen)
-            new_lc = (None if local_contrast is None or local_contrast is False
-                      else _lc.check_local_contrast(local_contrast))
-            new_cdn = (None if chroma_denoise is None or chroma_denoise is False
-                       else _cdn.check_chroma_denoise(chroma_denoise))
-            new_ydn = (None if luma_denoise is None or luma_denoise is False
-                       else _ydn.check_luma_denoise(luma_denoise))
-            new_clut = None if color_lut is None or color_lut is False else _clut.check_color_lut(color_lut)
-            new_dm = None if demosaic is None or demosaic is False else _dm.check_demosaic(demosaic)
-            new_rs = None if resample is None or resample is False else _rs.check_resample(resample)
+            # the optional stages: None leaves one, False turns it off, a value replaces it - every value checked here, before
+            # anything is assigned
+            given = dict(raw_denoise=raw_denoise, highlights=highlights, chromatic_aberration=chromatic_aberration,
+                         temporal_denoise=temporal_denoise, exposure_merge=exposure_merge, local_tonemap=local_tonemap,
+                         sharpen=sharpen, local_contrast=local_contrast, chroma_denoise=chroma_denoise,
+                         luma_denoise=luma_denoise, color_lut=color_lut, demosaic=demosaic, resample=resample)
+            replaced = {name: check(given[name]) for name, _, check in _OPTIONAL_STAGES
+                        if given[name] is not None and given[name] is not False}
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
             _typecheck("resize_width", resize_width, int, optional=True)
             _typecheck("scale", scale, float, optional=True)
@@ -524,59 +529,13 @@ def camera_isp(name: str, dtype=types.f32):
                     if self._shading is not None:
                         self._shading_retired.append(self._shading)
                     self._shading = new.to(self.device)
-            if raw_denoise is False:
-                self._raw_denoise = None
-            elif denoise is not None:
-                self._raw_denoise = denoise
-            if highlights is False:
-                self._highlights = None
-            elif new_hl is not None:
-                self._highlights = new_hl
-            if chromatic_aberration is False:
-                self._chromatic = None
-            elif new_ca is not None:
-                self._chromatic = new_ca
-            if temporal_denoise is False:
-                self._temporal = None
-            elif new_tn is not None:
-                self._temporal = new_tn
-            if exposure_merge is False:
-                self._merge = None
-            elif new_em is not None:
-                self._merge = new_em
-            if local_tonemap is False:
-                self._ltm = None
-            elif new_ltm is not None:
-                self._ltm = new_ltm
-            if sharpen is False:
-                self._sharpen = None
-            elif new_sharpen is not None:
-                self._sharpen = new_sharpen
-            if local_contrast is False:
-                self._local_contrast = None
-            elif new_lc is not None:
-                self._local_contrast = new_lc
-            if chroma_denoise is False:
-                self._chroma_denoise = None
-            elif new_cdn is not None:
-                self._chroma_denoise = new_cdn
-            if luma_denoise is False:
-                self._luma_denoise = None
-            elif new_ydn is not None:
-                self._luma_denoise = new_ydn
-            if color_lut is False:
-                self._color_lut = None
-            elif new_clut is not None:
-                self._color_lut = new_clut
-                new_clut._device_table(self.device)
-            if demosaic is False:
-                self._demosaic = None
-            elif new_dm is not None:
-                self._demosaic = new_dm
-            if resample is False:
-                self._resample = None
-            elif new_rs is not None:
-                self._resample = new_rs
+            for name, attr, _ in _OPTIONAL_STAGES:
+                if given[name] is False:
+                    setattr(self, attr, None)
+                elif replaced.get(name) is not None:
+                    setattr(self, attr, replaced[name])
+            if replaced.get("color_lut") is not None:
+                replaced["color_lut"]._device_table(self.device)  # (uploaded now: a captured step finds it on the device)
             if auto_white_balance is not None:
                 if awb is None:
                     self._awb_off()

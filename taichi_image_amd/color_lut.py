@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from . import _native, types
+from . import _native, _u8_stage as _u8, types
 
 MIN_POINTS, MAX_POINTS = 2, 65
 
@@ -49,13 +49,9 @@ class ColorLut:
             raise ValueError(f"ColorLut.table must be u8 or float, got {table.dtype}")
         t = np.ascontiguousarray(t)
         t.setflags(write=False)
-        s = strength
-        if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)):
-            raise ValueError(f"ColorLut.strength must be a number, got {s!r}")
-        if not math.isfinite(float(s)) or not 0 <= float(s) <= 1:
-            raise ValueError(f"ColorLut.strength must be finite and within [0, 1], got {s!r}")
+        _u8.number("ColorLut", "strength", strength, 0, 1)
         self._table = t
-        self._strength = float(s)
+        self._strength = float(strength)
         self._device_tables = {}
 
     @property
@@ -75,7 +71,7 @@ class ColorLut:
     @property
     def strength_q6(self) -> int:
         """S = floor(strength * 64 + 0.5): the weight the operator multiplies with, 0 .. 64."""
-        return int(math.floor(self._strength * 64 + 0.5))
+        return _u8.q6(self._strength)
 
     def __eq__(self, other):
         return (isinstance(other, ColorLut) and self._strength == other._strength
@@ -184,24 +180,16 @@ class ColorLut:
 
 def check_color_lut(value):
     """The ColorLut of a constructor / set() argument, None for None; ValueError otherwise."""
-    if value is None or isinstance(value, ColorLut):
-        return value
-    raise ValueError(f"color_lut must be None or a ColorLut, got {type(value).__name__}")
+    return _u8.check_setting(value, ColorLut, "color_lut")
 
 
 def apply(images, lut: ColorLut, inplace=False):
     """The operator on the u8 device tensors `images` ((H, W, 3), one shape, contiguous, one device).  inplace=True
     overwrites and returns `images` (the operator is pointwise), else new tensors come back.  One launch per 32 images on
     the device's current stream, no host synchronisation."""
-    first = images[0]
-    H, W = first.shape[:2]
-    outs = images if inplace else [torch.empty_like(im) for im in images]
-    if H * W:
-        table = lut._device_table(first.device)
-        _native.check(_native.lib().mi_isp_color_lut_rgb_batch(
-            _native.ptr_array(images), _native.ptr_array(outs), len(images), H, W, table.data_ptr(), lut._arg(),
-            _native.stream_ptr(first.device)))
-    return outs
+    H, W = images[0].shape[:2]
+    table = lut._device_table(images[0].device).data_ptr() if H * W else None
+    return _u8.apply_batch(images, "mi_isp_color_lut_rgb_batch", None, table, inplace=inplace, extra=(lut._arg(),))
 
 
 def apply_lut(image, lut: ColorLut):

@@ -1495,9 +1495,93 @@ extern "C" int mi_isp_resample_batch(const void* const* srcs, void* const* dsts,
   return 0;
 }
 
+// ---- the filters on the u8 outputs (isp_u8_stage.h): one front end ----------------------------------------------------------
+// n u8 images of one geometry (rgb: H x W x 3; else planar YUV 4:2:0 with an H x W Y plane, whose untouched rows are copied):
+// every image's pointers in the kernel arguments, 32 per launch.  Where the five stages' rules differ, they differ here: the
+// texts name the stage by its noun, and the order of an entry point's checks is the order of its calls.  So whether the
+// empty return (u8_nothing) comes before or after the list check is no field here: it is where the entry point puts that
+// line, because local contrast's tile and workspace checks sit between the two and a flag could not say that.
+struct U8Stage {
+  const char* noun;
+  bool one_image;                 // n == 0 is an error (else: nothing to do)
+  bool even_width;                // the Y plane of the YUV form must have an even width as well as an even height
+  bool in_place;                  // src[i] == dst[i] is allowed
+  bool disjoint;                  // a written image must overlap no read image and no other written image
+};
+static const U8Stage kSharpen = {"sharpen", true, false, false, false},
+                     kLocalContrast = {"local_contrast", false, true, true, false},
+                     kChromaDenoise = {"chroma_denoise", false, true, false, false},
+                     kLumaDenoise = {"luma_denoise", false, true, false, true},
+                     kColorLut = {"color_lut", false, false, true, false};    // (RGB only: no evenness rule applies)
+
+// one 256-thread block per 128 x 64 pixels: the launch's work-items per image must stay below 2^32
+static_assert(2 * cdn::TILE_CW == u8::TILE_W && 2 * cdn::TILE_CH == u8::TILE_H, "the chroma_denoise tile in pixels");
+static bool u8_tiles_fit(int H, int W) {
+  return H < (1 << 22) && W < (1 << 24) &&
+         (uint64_t)((W + u8::TILE_W - 1) / u8::TILE_W) * (uint64_t)((H + u8::TILE_H - 1) / u8::TILE_H) < (1u << 24);
+}
+
+static bool u8_nothing(int n, int H, int W) { return n == 0 || (size_t)H * (size_t)W == 0; }
+
+// the count, the shape, the stage's size limit (fits) and the evenness of the YUV form
+static int u8_shape(int n, int H, int W, bool rgb, bool fits, const U8Stage& st, const char* who) {
+  if (st.one_image) MI_REQUIRE(n >= 1, "%s: %s needs at least one image, got %d", who, st.noun, n);
+  else MI_REQUIRE(n >= 0, "%s: %s with %d images", who, st.noun, n);
+  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad %s shape %dx%d", who, st.noun, H, W);
+  MI_REQUIRE(fits, "%s: %s image %dx%d too large", who, st.noun, H, W);
+  if (st.even_width)
+    MI_REQUIRE(rgb || (H % 2 == 0 && W % 2 == 0), "%s: the Y plane of a %s YUV 4:2:0 image must have even sides, got %dx%d",
+               who, st.noun, H, W);
+  MI_REQUIRE(rgb || H % 2 == 0, "%s: the Y plane of a %s YUV 4:2:0 image must have an even height, got %d", who, st.noun, H);
+  return 0;
+}
+
+static int u8_list(const uint8_t* const* src, uint8_t* const* dst, const U8Stage& st, const char* who) {
+  MI_REQUIRE(src && dst, "%s: null %s image list", who, st.noun);
+  return 0;
+}
+
+// the n images' pointers; bytes: of one image
+static int u8_images(const uint8_t* const* src, uint8_t* const* dst, int n, size_t bytes, const U8Stage& st, const char* who) {
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && dst[i], "%s: %s image %d has a null pointer", who, st.noun, i);
+    MI_REQUIRE(st.in_place || src[i] != dst[i], "%s: %s image %d: the filter cannot run in place", who, st.noun, i);
+  }
+  for (int i = 0; st.disjoint && i < n; ++i) {
+    const uintptr_t d = (uintptr_t)dst[i];
+    for (int j = 0; j < n; ++j) {
+      const uintptr_t sj = (uintptr_t)src[j], dj = (uintptr_t)dst[j];
+      MI_REQUIRE(d + bytes <= sj || sj + bytes <= d, "%s: %s output %d overlaps input %d", who, st.noun, i, j);
+      MI_REQUIRE(i == j || d + bytes <= dj || dj + bytes <= d, "%s: %s outputs %d and %d overlap", who, st.noun, i, j);
+    }
+  }
+  return 0;
+}
+
+// The launches: a.im and a.n_images filled 32 images at a time, launch(i0) for the group that starts at image i0, then, for
+// the YUV form, bytes [first, first + count) of the group's images that are not filtered in place copied as they are
+// (count 0: the RGB form, no copy).
+struct U8Plane { size_t first, count; };
+static U8Plane u8_chroma_rows(bool rgb, int H, int W) { return {(size_t)H * W, rgb ? 0 : (size_t)H * W / 2}; }
+
+template <class Args, class Launch>
+static int for_each_group(const uint8_t* const* src, uint8_t* const* dst, int n, Args& a, U8Plane plane, void* stream,
+                          Launch launch) {
+  for (int i0 = 0; i0 < n; i0 += u8::MAX_IMAGES) {
+    a.n_images = n - i0 < u8::MAX_IMAGES ? n - i0 : u8::MAX_IMAGES;
+    u8::Image moved[u8::MAX_IMAGES];
+    int n_moved = 0;
+    for (int i = 0; i < a.n_images; ++i) {
+      a.im[i] = {src[i0 + i], dst[i0 + i]};
+      if (plane.count && src[i0 + i] != dst[i0 + i]) moved[n_moved++] = a.im[i];
+    }
+    if (int rc = launch(i0)) return rc;
+    if (int rc = u8::launch_copy(moved, n_moved, plane.first, plane.count, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
 // ---- output sharpening (isp_sharpen.h; DESIGN.md 3, "Output sharpening") ---------------------------------------------
-// n u8 images of one geometry (rgb: H x W x 3; else planar YUV 4:2:0 with an H x W Y plane, whose chroma rows are copied):
-// every image's pointers in the kernel arguments, 32 per launch
 static int sharpen_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W, const mi_isp_sharpen* s,
                         bool rgb, void* stream, const char* who) {
   MI_REQUIRE(s, "%s: null sharpen settings", who);
@@ -1508,30 +1592,15 @@ static int sharpen_impl(const uint8_t* const* src, uint8_t* const* dst, int n, i
              (int)s->threshold);
   MI_REQUIRE(s->overshoot >= -1 && s->overshoot <= 255, "%s: sharpen overshoot %d outside 0 .. 255 (-1: none)", who,
              (int)s->overshoot);
-  MI_REQUIRE(n >= 1, "%s: sharpen needs at least one image, got %d", who, n);
-  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad sharpen shape %dx%d", who, H, W);
-  // (one 256-thread block per tile: the launch's work-items per image must stay below 2^32)
-  MI_REQUIRE(H < (1 << 22) && W < (1 << 24) &&
-                 (uint64_t)((W + shp::TILE_W - 1) / shp::TILE_W) * (uint64_t)((H + shp::TILE_H - 1) / shp::TILE_H) < (1u << 24),
-             "%s: sharpen image %dx%d too large", who, H, W);
-  MI_REQUIRE(rgb || H % 2 == 0, "%s: the Y plane of a sharpen YUV 4:2:0 image must have an even height, got %d", who, H);
-  MI_REQUIRE(src && dst, "%s: null sharpen image list", who);
-  if ((size_t)H * (size_t)W == 0) return 0;
-  for (int i = 0; i < n; ++i) {
-    MI_REQUIRE(src[i] && dst[i], "%s: sharpen image %d has a null pointer", who, i);
-    MI_REQUIRE(src[i] != dst[i], "%s: sharpen image %d: the filter cannot run in place", who, i);
-  }
+  if (int rc = u8_shape(n, H, W, rgb, u8_tiles_fit(H, W), kSharpen, who)) return rc;
+  if (int rc = u8_list(src, dst, kSharpen, who)) return rc;
+  if (u8_nothing(n, H, W)) return 0;
+  if (int rc = u8_images(src, dst, n, 0, kSharpen, who)) return rc;
   shp::Args a = {};
   a.H = H; a.W = W;
   a.amount_q6 = s->amount_q6; a.threshold = s->threshold; a.overshoot = s->overshoot;
-  for (int i0 = 0; i0 < n; i0 += shp::MAX_IMAGES) {
-    a.n_images = n - i0 < shp::MAX_IMAGES ? n - i0 : shp::MAX_IMAGES;
-    for (int i = 0; i < a.n_images; ++i) a.im[i] = {src[i0 + i], dst[i0 + i]};
-    if (int rc = shp::launch(a, rgb, s->radius, (hipStream_t)stream)) return rc;
-    if (!rgb)
-      if (int rc = shp::launch_copy(a, (size_t)H * W, (size_t)H * W / 2, (hipStream_t)stream)) return rc;
-  }
-  return 0;
+  return for_each_group(src, dst, n, a, u8_chroma_rows(rgb, H, W), stream,
+                        [&](int) { return shp::launch(a, rgb, s->radius, (hipStream_t)stream); });
 }
 
 extern "C" int mi_isp_sharpen_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
@@ -1561,41 +1630,30 @@ extern "C" size_t mi_isp_local_contrast_workspace_bytes(int n, const mi_isp_loca
   return lc::hist_bytes(n, s->tiles_y, s->tiles_x) + lc::lut_bytes(n, s->tiles_y, s->tiles_x);
 }
 
-// n u8 images of one geometry (rgb: H x W x 3; else planar YUV 4:2:0 with an H x W Y plane, whose chroma rows are copied
-// when the image is not filtered in place): every image's pointers in the kernel arguments, 32 per launch
+// (nothing to do returns before the tile fit, the list and the workspace are looked at; the chroma rows are copied for the
+// images not filtered in place)
 static int local_contrast_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
                                const mi_isp_local_contrast* s, void* ws, bool rgb, void* stream, const char* who) {
   if (int rc = local_contrast_settings(s, who)) return rc;
-  MI_REQUIRE(n >= 0, "%s: local_contrast with %d images", who, n);
-  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad local_contrast shape %dx%d", who, H, W);
-  MI_REQUIRE(rgb || (H % 2 == 0 && W % 2 == 0),
-             "%s: the Y plane of a local_contrast YUV 4:2:0 image must have even sides, got %dx%d", who, H, W);
-  if (n == 0 || (size_t)H * (size_t)W == 0) return 0;
+  if (int rc = u8_shape(n, H, W, rgb, true, kLocalContrast, who)) return rc;
+  if (u8_nothing(n, H, W)) return 0;
   MI_REQUIRE(H >= s->tiles_y && W >= s->tiles_x, "%s: local_contrast image %dx%d smaller than its %d x %d tiles", who, H, W,
              (int)s->tiles_y, (int)s->tiles_x);
   MI_REQUIRE(H <= lc::MAX_SIDE && W <= lc::MAX_SIDE, "%s: local_contrast image %dx%d larger than %d", who, H, W, lc::MAX_SIDE);
-  MI_REQUIRE(src && dst, "%s: null local_contrast image list", who);
+  if (int rc = u8_list(src, dst, kLocalContrast, who)) return rc;
   MI_REQUIRE(ws && mi_aligned(ws, 16), "%s: local_contrast workspace null or not 16-byte aligned", who);
-  for (int i = 0; i < n; ++i) MI_REQUIRE(src[i] && dst[i], "%s: local_contrast image %d has a null pointer", who, i);
+  if (int rc = u8_images(src, dst, n, 0, kLocalContrast, who)) return rc;
   const size_t per_image = (size_t)s->tiles_y * s->tiles_x * 256;
   uint32_t* hist = static_cast<uint32_t*>(ws);
   uint8_t* lut = static_cast<uint8_t*>(ws) + lc::hist_bytes(n, s->tiles_y, s->tiles_x);
   lc::Args a = {};
   a.H = H; a.W = W; a.Ty = s->tiles_y; a.Tx = s->tiles_x;
   a.clip_q8 = s->clip_q8; a.strength_q6 = s->strength_q6;
-  for (int i0 = 0; i0 < n; i0 += lc::MAX_IMAGES) {
-    a.n_images = n - i0 < lc::MAX_IMAGES ? n - i0 : lc::MAX_IMAGES;
+  return for_each_group(src, dst, n, a, u8_chroma_rows(rgb, H, W), stream, [&](int i0) {
     a.hist = hist + i0 * per_image;
     a.lut = lut + i0 * per_image;
-    shp::Args chroma = {};                            // the chroma rows of the images not filtered in place
-    for (int i = 0; i < a.n_images; ++i) {
-      a.im[i] = {src[i0 + i], dst[i0 + i]};
-      if (!rgb && src[i0 + i] != dst[i0 + i]) chroma.im[chroma.n_images++] = {src[i0 + i], dst[i0 + i]};
-    }
-    if (int rc = lc::launch(a, rgb, (hipStream_t)stream)) return rc;
-    if (int rc = shp::launch_copy(chroma, (size_t)H * W, (size_t)H * W / 2, (hipStream_t)stream)) return rc;
-  }
-  return 0;
+    return lc::launch(a, rgb, (hipStream_t)stream);
+  });
 }
 
 extern "C" int mi_isp_local_contrast_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
@@ -1609,8 +1667,7 @@ extern "C" int mi_isp_local_contrast_yuv420_batch(const uint8_t* const* src, uin
 }
 
 // ---- chroma noise reduction (isp_chroma_denoise.h; DESIGN.md 3, "Chroma noise reduction") -----------------------------
-// n u8 images of one geometry (rgb: H x W x 3; else planar YUV 4:2:0 with an H x W Y plane, whose Y rows are copied): every
-// image's pointers in the kernel arguments, 32 per launch
+// (the planar form writes U and V: the Y rows are copied)
 static int chroma_denoise_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
                                const mi_isp_chroma_denoise* s, bool rgb, void* stream, const char* who) {
   MI_REQUIRE(s, "%s: null chroma_denoise settings", who);
@@ -1621,36 +1678,15 @@ static int chroma_denoise_impl(const uint8_t* const* src, uint8_t* const* dst, i
              who, (int)s->chroma_threshold);
   MI_REQUIRE(s->strength_q6 >= 0 && s->strength_q6 <= 64, "%s: chroma_denoise strength_q6 %d outside 0 .. 64", who,
              (int)s->strength_q6);
-  MI_REQUIRE(n >= 0, "%s: chroma_denoise with %d images", who, n);
-  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad chroma_denoise shape %dx%d", who, H, W);
-  // (one 256-thread block per tile: the launch's work-items per image must stay below 2^32)
-  MI_REQUIRE(H < (1 << 22) && W < (1 << 24) &&
-                 (uint64_t)((W + 2 * cdn::TILE_CW - 1) / (2 * cdn::TILE_CW)) *
-                         (uint64_t)((H + 2 * cdn::TILE_CH - 1) / (2 * cdn::TILE_CH)) < (1u << 24),
-             "%s: chroma_denoise image %dx%d too large", who, H, W);
-  MI_REQUIRE(rgb || (H % 2 == 0 && W % 2 == 0),
-             "%s: the Y plane of a chroma_denoise YUV 4:2:0 image must have even sides, got %dx%d", who, H, W);
-  MI_REQUIRE(src && dst, "%s: null chroma_denoise image list", who);
-  if (n == 0 || (size_t)H * (size_t)W == 0) return 0;
-  for (int i = 0; i < n; ++i) {
-    MI_REQUIRE(src[i] && dst[i], "%s: chroma_denoise image %d has a null pointer", who, i);
-    MI_REQUIRE(src[i] != dst[i], "%s: chroma_denoise image %d: the filter cannot run in place", who, i);
-  }
+  if (int rc = u8_shape(n, H, W, rgb, u8_tiles_fit(H, W), kChromaDenoise, who)) return rc;
+  if (int rc = u8_list(src, dst, kChromaDenoise, who)) return rc;
+  if (u8_nothing(n, H, W)) return 0;
+  if (int rc = u8_images(src, dst, n, 0, kChromaDenoise, who)) return rc;
   cdn::Args a = {};
   a.H = H; a.W = W;
   a.tl4 = 4 * s->luma_threshold; a.tc4 = 4 * s->chroma_threshold; a.strength_q6 = s->strength_q6;
-  for (int i0 = 0; i0 < n; i0 += cdn::MAX_IMAGES) {
-    a.n_images = n - i0 < cdn::MAX_IMAGES ? n - i0 : cdn::MAX_IMAGES;
-    for (int i = 0; i < a.n_images; ++i) a.im[i] = {src[i0 + i], dst[i0 + i]};
-    if (int rc = cdn::launch(a, rgb, s->radius, (hipStream_t)stream)) return rc;
-    if (!rgb) {
-      shp::Args y = {};                               // the Y rows
-      y.n_images = a.n_images;
-      for (int i = 0; i < a.n_images; ++i) y.im[i] = a.im[i];
-      if (int rc = shp::launch_copy(y, 0, (size_t)H * W, (hipStream_t)stream)) return rc;
-    }
-  }
-  return 0;
+  return for_each_group(src, dst, n, a, U8Plane{0, rgb ? 0 : (size_t)H * W}, stream,
+                        [&](int) { return cdn::launch(a, rgb, s->radius, (hipStream_t)stream); });
 }
 
 extern "C" int mi_isp_chroma_denoise_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
@@ -1664,8 +1700,6 @@ extern "C" int mi_isp_chroma_denoise_yuv420_batch(const uint8_t* const* src, uin
 }
 
 // ---- luma noise reduction (isp_luma_denoise.h; DESIGN.md 3, "Luma noise reduction") -----------------------------------
-// n u8 images of one geometry (rgb: H x W x 3; else planar YUV 4:2:0 with an H x W Y plane, whose chroma rows are copied):
-// every image's pointers in the kernel arguments, 32 per launch
 static int luma_denoise_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
                              const mi_isp_luma_denoise* s, bool rgb, void* stream, const char* who) {
   MI_REQUIRE(s, "%s: null luma_denoise settings", who);
@@ -1676,45 +1710,15 @@ static int luma_denoise_impl(const uint8_t* const* src, uint8_t* const* dst, int
              who, (int)s->threshold_bright);
   MI_REQUIRE(s->strength_q6 >= 0 && s->strength_q6 <= 64, "%s: luma_denoise strength_q6 %d outside 0 .. 64", who,
              (int)s->strength_q6);
-  MI_REQUIRE(n >= 0, "%s: luma_denoise with %d images", who, n);
-  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad luma_denoise shape %dx%d", who, H, W);
-  // (one 256-thread block per tile: the launch's work-items per image must stay below 2^32)
-  MI_REQUIRE(H < (1 << 22) && W < (1 << 24) &&
-                 (uint64_t)((W + ydn::TILE_W - 1) / ydn::TILE_W) * (uint64_t)((H + ydn::TILE_H - 1) / ydn::TILE_H) < (1u << 24),
-             "%s: luma_denoise image %dx%d too large", who, H, W);
-  MI_REQUIRE(rgb || (H % 2 == 0 && W % 2 == 0),
-             "%s: the Y plane of a luma_denoise YUV 4:2:0 image must have even sides, got %dx%d", who, H, W);
-  MI_REQUIRE(src && dst, "%s: null luma_denoise image list", who);
-  if (n == 0 || (size_t)H * (size_t)W == 0) return 0;
-  const size_t bytes = rgb ? (size_t)H * W * 3 : (size_t)H * W * 3 / 2;
-  for (int i = 0; i < n; ++i) {
-    MI_REQUIRE(src[i] && dst[i], "%s: luma_denoise image %d has a null pointer", who, i);
-    MI_REQUIRE(src[i] != dst[i], "%s: luma_denoise image %d: the filter cannot run in place", who, i);
-  }
-  // a written image overlaps no read image and no other written image
-  for (int i = 0; i < n; ++i) {
-    const uintptr_t d = (uintptr_t)dst[i];
-    for (int j = 0; j < n; ++j) {
-      const uintptr_t sj = (uintptr_t)src[j], dj = (uintptr_t)dst[j];
-      MI_REQUIRE(d + bytes <= sj || sj + bytes <= d, "%s: luma_denoise output %d overlaps input %d", who, i, j);
-      MI_REQUIRE(i == j || d + bytes <= dj || dj + bytes <= d, "%s: luma_denoise outputs %d and %d overlap", who, i, j);
-    }
-  }
+  if (int rc = u8_shape(n, H, W, rgb, u8_tiles_fit(H, W), kLumaDenoise, who)) return rc;
+  if (int rc = u8_list(src, dst, kLumaDenoise, who)) return rc;
+  if (u8_nothing(n, H, W)) return 0;
+  if (int rc = u8_images(src, dst, n, rgb ? (size_t)H * W * 3 : (size_t)H * W * 3 / 2, kLumaDenoise, who)) return rc;
   ydn::Args a = {};
   a.H = H; a.W = W;
   a.t0 = s->threshold; a.t1 = s->threshold_bright; a.strength_q6 = s->strength_q6;
-  for (int i0 = 0; i0 < n; i0 += ydn::MAX_IMAGES) {
-    a.n_images = n - i0 < ydn::MAX_IMAGES ? n - i0 : ydn::MAX_IMAGES;
-    for (int i = 0; i < a.n_images; ++i) a.im[i] = {src[i0 + i], dst[i0 + i]};
-    if (int rc = ydn::launch(a, rgb, s->radius, (hipStream_t)stream)) return rc;
-    if (!rgb) {
-      shp::Args uv = {};                              // the chroma rows
-      uv.n_images = a.n_images;
-      for (int i = 0; i < a.n_images; ++i) uv.im[i] = a.im[i];
-      if (int rc = shp::launch_copy(uv, (size_t)H * W, (size_t)H * W / 2, (hipStream_t)stream)) return rc;
-    }
-  }
-  return 0;
+  return for_each_group(src, dst, n, a, u8_chroma_rows(rgb, H, W), stream,
+                        [&](int) { return ydn::launch(a, rgb, s->radius, (hipStream_t)stream); });
 }
 
 extern "C" int mi_isp_luma_denoise_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,
@@ -1728,8 +1732,7 @@ extern "C" int mi_isp_luma_denoise_yuv420_batch(const uint8_t* const* src, uint8
 }
 
 // ---- 3D colour LUT (isp_color_lut.h; DESIGN.md 3, "Colour LUT") ------------------------------------------------------------
-// n interleaved u8 RGB images of one geometry through one table: every image's pointers in the kernel arguments, 32 per
-// launch; path: clut::Path (the dispatcher's choice, or one path forced)
+// n interleaved u8 RGB images of one geometry through one table; path: clut::Path (the dispatcher's choice, or one path forced)
 static int color_lut_impl(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W, const uint32_t* table,
                           const mi_isp_color_lut* s, int path, void* stream, const char* who) {
   MI_REQUIRE(s, "%s: null color_lut settings", who);
@@ -1739,13 +1742,11 @@ static int color_lut_impl(const uint8_t* const* src, uint8_t* const* dst, int n,
              (int)s->strength_q6);
   MI_REQUIRE(path == clut::PATH_AUTO || path == clut::PATH_GLOBAL || (path == clut::PATH_LDS && s->n_points <= clut::LDS_POINTS),
              "%s: color_lut path %d (0: the dispatcher's, 1: LDS, n_points <= %d, 2: global)", who, path, clut::LDS_POINTS);
-  MI_REQUIRE(n >= 0, "%s: color_lut with %d images", who, n);
-  MI_REQUIRE(H >= 0 && W >= 0, "%s: bad color_lut shape %dx%d", who, H, W);
-  MI_REQUIRE((uint64_t)H * (uint64_t)W < (1ull << 31), "%s: color_lut image %dx%d too large", who, H, W);
+  if (int rc = u8_shape(n, H, W, true, (uint64_t)H * (uint64_t)W < (1ull << 31), kColorLut, who)) return rc;
   MI_REQUIRE(table, "%s: null color_lut table", who);
-  MI_REQUIRE(src && dst, "%s: null color_lut image list", who);
-  if (n == 0 || (size_t)H * (size_t)W == 0) return 0;
-  for (int i = 0; i < n; ++i) MI_REQUIRE(src[i] && dst[i], "%s: color_lut image %d has a null pointer", who, i);
+  if (int rc = u8_list(src, dst, kColorLut, who)) return rc;
+  if (u8_nothing(n, H, W)) return 0;
+  if (int rc = u8_images(src, dst, n, 0, kColorLut, who)) return rc;
   int dev = 0;
   MI_HIP(hipGetDevice(&dev));
   clut::Args a = {};
@@ -1753,12 +1754,8 @@ static int color_lut_impl(const uint8_t* const* src, uint8_t* const* dst, int n,
   a.dword_rows = W % 4 == 0;
   a.n_points = s->n_points; a.strength_q6 = s->strength_q6;
   a.table = table;
-  for (int i0 = 0; i0 < n; i0 += clut::MAX_IMAGES) {
-    a.n_images = n - i0 < clut::MAX_IMAGES ? n - i0 : clut::MAX_IMAGES;
-    for (int i = 0; i < a.n_images; ++i) a.im[i] = {src[i0 + i], dst[i0 + i]};
-    if (int rc = clut::launch(a, (clut::Path)path, ew::device_cus(dev), (hipStream_t)stream)) return rc;
-  }
-  return 0;
+  return for_each_group(src, dst, n, a, U8Plane{0, 0}, stream,
+                        [&](int) { return clut::launch(a, (clut::Path)path, ew::device_cus(dev), (hipStream_t)stream); });
 }
 
 extern "C" int mi_isp_color_lut_rgb_batch(const uint8_t* const* src, uint8_t* const* dst, int n, int H, int W,

@@ -1,7 +1,7 @@
 // Chroma noise reduction (mi_isp_chroma_denoise; DESIGN.md 3, "Chroma noise reduction"): a luma-guided mean of the chroma
 // on the grid of 2 x 2 pixel cells of a u8 image, interleaved RGB (H x W x 3) or planar YUV 4:2:0 (the U and V planes are
 // that grid).  The filter is stated in integer arithmetic, so the kernel's output is the contract's bit for bit.  One
-// launch takes up to MAX_IMAGES images of one geometry, their pointers in the kernel arguments.
+// launch takes up to u8::MAX_IMAGES images of one geometry, their pointers in the kernel arguments.
 #pragma once
 #include <stdint.h>
 
@@ -34,11 +34,10 @@ CDN_HD int green_delta(int dr, int db) { return ((-(77 * dr + 29 * db)) * 437 + 
 }  // namespace cdn
 
 #if defined(__HIPCC__)
-#include "isp_sharpen.h"
+#include "isp_u8_stage.h"
 
 namespace cdn {
 
-constexpr int MAX_IMAGES = 32;              // images per launch (grid.z)
 constexpr int THREADS = 256;                // 4 waves
 constexpr int TILE_CW = 64;                 // tile, in cells: 32 pairs of cells (one pair = 4 pixels per lane of a half wave) ...
 constexpr int TILE_CH = 32;                 // ... by 8 strips of ROWS cell rows: 128 x 64 pixels
@@ -49,8 +48,9 @@ struct Args {
   int tl4, tc4;                             // 4 luma_threshold, 4 chroma_threshold
   int strength_q6;                          // S = floor(strength * 64 + 0.5), 0 .. 64
   int n_images;
-  shp::Image im[MAX_IMAGES];
+  u8::Image im[u8::MAX_IMAGES];
 };
+static_assert(sizeof(Args) == 536 && offsetof(Args, im) == 24, "the kernel arguments' layout");
 
 // one launch (a.n_images images): rgb (interleaved, 3 bytes per pixel) or planar YUV 4:2:0 (only U and V are written: the Y
 // rows are the caller's to copy), radius 1, 2 or 3

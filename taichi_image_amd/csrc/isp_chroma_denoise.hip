@@ -17,13 +17,13 @@
 // tested against both cells (three v_sad_u32, a v_max3, a shift, two v_mad_u32_u24 and an add per tap).  A cell outside
 // the grid is no tap: a block whose staged cells all lie inside the grid runs without the test, the others give such a
 // cell a luma no threshold accepts.  3. The pair's pixels, read as three dwords per row before its windows were walked,
-// take the deltas as packed 16-bit adds with a saturating pack (isp_sharpen.h); byte by byte on the other path.
+// take the deltas as packed 16-bit adds with a saturating pack (isp_u8_stage.h); byte by byte on the other path.
 #include "isp_chroma_denoise.h"
 
 namespace cdn {
 
-using shp::clampi;
-using shp::dot4;
+using u8::clampi;
+using u8::dot4;
 
 constexpr uint32_t BIAS = 1020;                       // SB, SR in -1020 .. 1020
 
@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(THREADS) chroma_denoise_kernel(const Args a) {
   constexpr int N = 2 * R + 1;                        // window side
   __shared__ uint32_t cells[LH * LW];
 
-  const shp::Image im = a.im[blockIdx.z];             // (a wave-uniform index: scalar loads)
+  const u8::Image im = a.im[blockIdx.z];             // (a wave-uniform index: scalar loads)
   const int H = a.H, W = a.W, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
   const int cb0 = blockIdx.x * TILE_CW, ca0 = blockIdx.y * TILE_CH;
   const size_t pitch = (size_t)W * CH;
@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(THREADS) chroma_denoise_kernel(const Args a) {
       if constexpr (RGB) {
         // a row's four pixels: bytes R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3; cell 0 holds pixels 0 and 1, cell 1 pixels 2 and 3
         const uint32_t* d = q[it];
-        const uint32_t la = shp::luma4(d[0], d[1], d[2]), lb = shp::luma4(d[3], d[4], d[5]);
+        const uint32_t la = u8::luma4(d[0], d[1], d[2]), lb = u8::luma4(d[3], d[4], d[5]);
         const uint32_t sl0 = dot4(la, 0x00000101u, dot4(lb, 0x00000101u, 0u));
         const uint32_t sl1 = dot4(la, 0x01010000u, dot4(lb, 0x01010000u, 0u));
         const uint32_t r0 = dot4(d[0], 0x01000001u, dot4(d[3], 0x01000001u, BIAS));
@@ -218,8 +218,8 @@ __global__ void __launch_bounds__(THREADS) chroma_denoise_kernel(const Args a) {
     }
     if constexpr (RGB) {
       if (fast) {
-        using shp::add_sat4;
-        using shp::pair;
+        using u8::add_sat4;
+        using u8::pair;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int r = 2 * ck + i;

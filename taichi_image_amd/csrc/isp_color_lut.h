@@ -1,7 +1,7 @@
 // 3D colour LUT (mi_isp_color_lut; DESIGN.md 3, "Colour LUT"): tetrahedral interpolation in an N x N x N table of packed RGB
 // dwords on an interleaved u8 RGB image (H x W x 3), stated in integer arithmetic, so the kernel's output is the contract's
-// bit for bit.  The operator is pointwise: src == dst is allowed.  One launch takes up to MAX_IMAGES images of one geometry,
-// their pointers in the kernel arguments.
+// bit for bit.  The operator is pointwise: src == dst is allowed.  One launch takes up to u8::MAX_IMAGES images of one
+// geometry, their pointers in the kernel arguments.
 //
 // Per pixel, v_c the input codes (c = R, G, B), T the table (entry (r * N + g) * N + b = R | G << 8 | B << 16), S = strength_q6:
 //   p_c = v_c (N - 1);  i_c = p_c // 255;  f_c = p_c - 255 i_c;  j_c = min(i_c + 1, N - 1)
@@ -13,7 +13,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
-#include "isp_sharpen.h"
+#include "isp_u8_stage.h"
 #define CLUT_HD __host__ __device__ inline
 #else
 #define CLUT_HD inline
@@ -56,8 +56,6 @@ CLUT_HD bool lds_wins(int n_points) { return n_points <= LDS_POINTS; }
 #if defined(__HIPCC__)
 namespace clut {
 
-constexpr int MAX_IMAGES = 32;                      // images per launch
-
 struct Args {
   uint32_t pixels;                                  // H * W of one image (< 2^31)
   int dword_rows;                                   // W * 3 % 4 == 0: with 4-byte aligned images, the dword path
@@ -65,8 +63,9 @@ struct Args {
   int strength_q6;                                  // S = floor(strength * 64 + 0.5), 0 .. 64
   int n_images;
   const uint32_t* table;                            // N^3 dwords on the device
-  shp::Image im[MAX_IMAGES];
+  u8::Image im[u8::MAX_IMAGES];
 };
+static_assert(sizeof(Args) == 544 && offsetof(Args, im) == 32, "the kernel arguments' layout");
 
 // one launch (a.n_images images) on `path` (PATH_LDS needs N <= LDS_POINTS); n_cus: the device's CU count
 int launch(const Args& a, Path path, int n_cus, hipStream_t stream);

@@ -17,7 +17,7 @@
 
 namespace clut {
 
-using shp::byte_of;
+using u8::byte_of;
 
 // one compare-exchange of the sort by descending fraction: the index step travels with its fraction
 MI_DEV void order(uint32_t& fa, uint32_t& sa, uint32_t& fb, uint32_t& sb) {
@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(THREADS) color_lut_kernel(const Args a) {
 
   for (uint32_t chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
     const uint32_t k = chunk / per_image;             // (block-uniform: scalar loads of the image's pointers)
-    const shp::Image im = a.im[k];
+    const u8::Image im = a.im[k];
     const uint32_t p0 = (chunk - k * per_image) * CHUNK + threadIdx.x * PIXELS_PER_THREAD;
     if (p0 >= P) continue;                            // (no barrier inside the loop)
     const bool fast = a.dword_rows && ((reinterpret_cast<uintptr_t>(im.src) | reinterpret_cast<uintptr_t>(im.dst)) & 3) == 0;

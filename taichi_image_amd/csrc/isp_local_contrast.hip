@@ -18,15 +18,13 @@
 //    rows and 128 columns come from one exact 32-bit integer division each.  Integer adds in 1. make the histograms
 //    independent of the arrival order; no block waits for another.
 #include "isp_local_contrast.h"
-#include "isp_sharpen.h"
 
 namespace lc {
 
-using shp::add_sat4;
-using shp::byte_of;
-using shp::clampi;
-using shp::luma4;
-using shp::pair;
+using u8::byte_of;
+using u8::clampi;
+using u8::Image;
+using u8::luma4;
 
 constexpr int HIST_COPIES = THREADS / 64;          // one histogram per wave (the decision: DESIGN.md 5.7)
 
@@ -205,7 +203,7 @@ __global__ void __launch_bounds__(THREADS) apply_kernel(const Args a) {
   const int c0 = blockIdx.x * BLOCK_W, r0 = blockIdx.y * BLOCK_H;
   const size_t pitch = (size_t)W * CH;
   const uint8_t* lut = a.lut + (size_t)blockIdx.z * Ty * Tx * 256;
-  const bool fast = (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(im.src) | reinterpret_cast<uintptr_t>(im.dst)) & 3) == 0;
+  const bool fast = u8::rows_are_dwords(im, W);
 
   if (threadIdx.x < BLOCK_H) qrow[threadIdx.x] = axis_q(min(r0 + (int)threadIdx.x, H - 1), H, Ty);
   else if (threadIdx.x < BLOCK_H + BLOCK_W) qcol[threadIdx.x - BLOCK_H] = axis_q(min(c0 + (int)threadIdx.x - BLOCK_H, W - 1), W, Tx);
@@ -294,14 +292,7 @@ __global__ void __launch_bounds__(THREADS) apply_kernel(const Args a) {
       delta[j] = ((E - L) * S + 32) >> 6;             // floor: an arithmetic shift
     }
     if (fast) {
-      uint32_t* dp = reinterpret_cast<uint32_t*>(im.dst + off);
-      if constexpr (RGB) {
-        dp[0] = add_sat4(px[k][0], pair(delta[0], delta[0]), pair(delta[0], delta[1]));     // R0 G0 B0 R1
-        dp[1] = add_sat4(px[k][1], pair(delta[1], delta[1]), pair(delta[2], delta[2]));     // G1 B1 R2 G2
-        dp[2] = add_sat4(px[k][2], pair(delta[2], delta[3]), pair(delta[3], delta[3]));     // B2 R3 G3 B3
-      } else {
-        dp[0] = add_sat4(px[k][0], pair(delta[0], delta[1]), pair(delta[2], delta[3]));
-      }
+      u8::store_delta4<RGB>(im.dst + off, px[k], delta);
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j)

@@ -1,7 +1,7 @@
 // Luma noise reduction (mi_isp_luma_denoise; DESIGN.md 3, "Luma noise reduction"): an edge-preserving mean of the luma over
 // a (2r + 1)^2 window of a u8 image, interleaved RGB (H x W x 3; the same delta is added to R, G and B) or the Y plane of a
 // planar YUV 4:2:0 image.  The filter is stated in integer arithmetic, so the kernel's output is the contract's bit for bit.
-// One launch takes up to MAX_IMAGES images of one geometry, their pointers in the kernel arguments.
+// One launch takes up to u8::MAX_IMAGES images of one geometry, their pointers in the kernel arguments.
 #pragma once
 #include <stdint.h>
 
@@ -38,24 +38,20 @@ YDN_HD int threshold_at(int t0, int t1, int L0) { return t0 + (((t1 - t0) * L0 +
 }  // namespace ydn
 
 #if defined(__HIPCC__)
-#include "isp_sharpen.h"
+#include "isp_u8_stage.h"
 
 namespace ydn {
 
-constexpr int MAX_IMAGES = 32;              // images per launch (grid.z)
-constexpr int THREADS = 256;                // 4 waves
-constexpr int TILE_W = shp::TILE_W;         // output tile: 32 groups of 4 columns (one group per lane of a half wave) ...
-constexpr int TILE_H = shp::TILE_H;         // ... by 8 strips of ROWS rows: 128 x 64 pixels
-constexpr int ROWS = 8;                     // output rows per thread, one below the other
-constexpr int LG = shp::LG;                 // 4-pixel groups per staged luma row: the tile's and one on either side (r <= 4)
+constexpr int ROWS = 8;                     // output rows per thread, one below the other: 8 strips to a u8::TILE_H tile
 
 struct Args {
   int H, W;                                 // of the RGB image, or of the Y plane
   int t0, t1;                               // threshold, threshold_bright: luma codes 0 .. 255
   int strength_q6;                          // S = floor(strength * 64 + 0.5), 0 .. 64
   int n_images;
-  shp::Image im[MAX_IMAGES];
+  u8::Image im[u8::MAX_IMAGES];
 };
+static_assert(sizeof(Args) == 536 && offsetof(Args, im) == 24, "the kernel arguments' layout");
 
 // one launch (a.n_images images): rgb (interleaved, 3 bytes per pixel) or a plane (1 byte per pixel), radius 1, 2 or 3
 int launch(const Args& a, bool rgb, int radius, hipStream_t stream);

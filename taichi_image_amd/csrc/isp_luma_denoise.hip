@@ -7,7 +7,7 @@
 //   m = floor((2 s + n) / (2 n));  delta = (S (m - L(p)) + 32) >> 6;  out_c = clamp(I_c + delta, 0, 255)
 //
 // One 256-thread block per 128 x 64 output tile of one image (grid.z).  1. The luma of the tile and of four columns and r
-// rows around it is staged ONCE into LDS, four pixels to a dword, as the sharpening kernel stages it (isp_sharpen.hip):
+// rows around it is staged ONCE into LDS, four pixels to a dword, as the sharpening kernel stages it (u8::stage_luma):
 // three dwords per four pixels and six byte dot products where the rows allow (W % 4 == 0 and 4-byte aligned images),
 // every load of the thread issued before the first is used; byte by byte otherwise.  A pixel outside the image is staged
 // from a clamped address and never used as a tap.  2. Lane g of a half wave owns columns 4g .. 4g + 3, the block's 8
@@ -20,14 +20,13 @@
 // 255 fits 16 bits) and v_pk_add_u16 the counts: five instructions for two taps.  No branch looks at a tap.  A block whose
 // windows all stay inside the image runs without the inside test; the others give a pixel outside the image the value
 // 0x7fff, which no threshold accepts (one v_or3_b32 per pair).  3. The four pixels, read as three dwords (one for a plane)
-// before the window is walked, take the deltas as packed 16-bit adds with a saturating pack (isp_sharpen.h); byte by byte
+// before the window is walked, take the deltas as packed 16-bit adds with a saturating pack (u8::store_delta4); byte by byte
 // on the other path.
 #include "isp_luma_denoise.h"
 
 namespace ydn {
 
-using shp::clampi;
-using shp::Image;
+using namespace u8;                                   // the images, the tile, the byte helpers, the staging and the write-back
 
 constexpr uint32_t OUTSIDE = 0x7fffu;                 // a pixel outside the image, as a 16-bit luma: 0x7fff - lo > 2 T always
 
@@ -67,30 +66,12 @@ __global__ void __launch_bounds__(THREADS) luma_denoise_kernel(const Args a) {
   const int H = a.H, W = a.W;
   const int c0 = blockIdx.x * TILE_W, r0 = blockIdx.y * TILE_H;
   const size_t pitch = (size_t)W * CH;
-  // the dword path: every 4-pixel group is then wholly inside the image or wholly outside, and its bytes are aligned
-  const bool fast = (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(im.src) | reinterpret_cast<uintptr_t>(im.dst)) & 3) == 0;
+  const bool fast = rows_are_dwords(im, W);
 
   // 1. the luma of the tile and its surround.  A pixel outside the image is never a tap: its load is clamped into the
   // image and what it gives is not used.
   if (fast) {
-    constexpr int ITER = (LH * LG + THREADS - 1) / THREADS;
-    uint32_t q[ITER][CH];
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-      const int u = threadIdx.x + it * THREADS, lr = u / LG, lg = u - lr * LG;
-      const int r = clampi(r0 - R + lr, 0, H - 1), c = clampi(c0 - 4 + 4 * lg, 0, W - 4);
-      const uint32_t* p = reinterpret_cast<const uint32_t*>(im.src + (size_t)r * pitch + (size_t)c * CH);
-#pragma unroll
-      for (int ch = 0; ch < CH; ++ch) q[it][ch] = p[ch];
-    }
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-      const int u = threadIdx.x + it * THREADS;
-      uint32_t l4;
-      if constexpr (RGB) l4 = shp::luma4(q[it][0], q[it][1], q[it][2]);
-      else l4 = q[it][0];
-      if (u < LH * LG) lum[u] = l4;
-    }
+    stage_luma<RGB, R, false>(lum, im, H, W, r0, c0);
   } else {
     for (int u = threadIdx.x; u < LH * LG; u += THREADS) {
       const int lr = u / LG, lg = u - lr * LG;
@@ -153,7 +134,7 @@ __global__ void __launch_bounds__(THREADS) luma_denoise_kernel(const Args a) {
         int T[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          L0[v][2 * h + e] = shp::byte_of(ctr, 2 * h + e);
+          L0[v][2 * h + e] = byte_of(ctr, 2 * h + e);
           T[e] = threshold_at(t0, t1, L0[v][2 * h + e]);
         }
         lo[v][h] = (uint32_t)((L0[v][2 * h] - T[0]) & 0xffff) | (uint32_t)(L0[v][2 * h + 1] - T[1]) << 16;
@@ -209,16 +190,7 @@ __global__ void __launch_bounds__(THREADS) luma_denoise_kernel(const Args a) {
       // 3. the pixels
       const size_t o = v ? off + pitch : off;
       if (fast) {
-        using shp::add_sat4;
-        using shp::pair;
-        uint32_t* dp = reinterpret_cast<uint32_t*>(im.dst + o);
-        if constexpr (RGB) {
-          dp[0] = add_sat4(px[v][0], pair(delta[0], delta[0]), pair(delta[0], delta[1]));          // R0 G0 B0 R1
-          dp[1] = add_sat4(px[v][1], pair(delta[1], delta[1]), pair(delta[2], delta[2]));          // G1 B1 R2 G2
-          dp[2] = add_sat4(px[v][2], pair(delta[2], delta[3]), pair(delta[3], delta[3]));          // B2 R3 G3 B3
-        } else {
-          dp[0] = add_sat4(px[v][0], pair(delta[0], delta[1]), pair(delta[2], delta[3]));
-        }
+        store_delta4<RGB>(im.dst + o, px[v], delta);
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)

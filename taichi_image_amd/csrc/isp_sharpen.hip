@@ -21,6 +21,8 @@
 
 namespace shp {
 
+using namespace u8;                                   // the images, the tile, the byte helpers, the staging and the write-back
+
 // what one staged row gives a thread's four columns: their lumas (packed), the horizontal blur and the horizontal 3-wide
 // min / max of each
 struct RowV {
@@ -42,34 +44,11 @@ __global__ void __launch_bounds__(THREADS) sharpen_kernel(const Args a) {
   const int H = a.H, W = a.W;
   const int c0 = blockIdx.x * TILE_W, r0 = blockIdx.y * TILE_H;
   const size_t pitch = (size_t)W * CH;
-  // the dword path: every 4-pixel group is then wholly inside the image or wholly outside, and its bytes are aligned
-  const bool fast = (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(im.src) | reinterpret_cast<uintptr_t>(im.dst)) & 3) == 0;
+  const bool fast = rows_are_dwords(im, W);
 
   // 1. the luma of the tile and its surround, coordinates clamped into the image
   if (fast) {
-    // every load of the thread is issued before the first is used (the staging waits for memory, not for arithmetic): a
-    // group outside the image loads the edge group of its row and repeats that group's edge pixel
-    constexpr int ITER = (LH * LG + THREADS - 1) / THREADS;
-    uint32_t q[ITER][CH];
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-      const int u = threadIdx.x + it * THREADS, lr = u / LG, lg = u - lr * LG;
-      const int r = clampi(r0 - R + lr, 0, H - 1), c = clampi(c0 - 4 + 4 * lg, 0, W - 4);
-      const uint32_t* p = reinterpret_cast<const uint32_t*>(im.src + (size_t)r * pitch + (size_t)c * CH);
-#pragma unroll
-      for (int ch = 0; ch < CH; ++ch) q[it][ch] = p[ch];
-    }
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-      const int u = threadIdx.x + it * THREADS, lr = u / LG, lg = u - lr * LG;
-      const int c = c0 - 4 + 4 * lg;
-      uint32_t l4;
-      if constexpr (RGB) l4 = luma4(q[it][0], q[it][1], q[it][2]);
-      else l4 = q[it][0];
-      if (c < 0) l4 = (l4 & 0xffu) * 0x01010101u;
-      else if (c >= W) l4 = (l4 >> 24) * 0x01010101u;
-      if (u < LH * LG) lum[u] = l4;
-    }
+    stage_luma<RGB, R, true>(lum, im, H, W, r0, c0);
   } else {
     for (int u = threadIdx.x; u < LH * LG; u += THREADS) {
       const int lr = u / LG, lg = u - lr * LG;
@@ -166,15 +145,7 @@ __global__ void __launch_bounds__(THREADS) sharpen_kernel(const Args a) {
     if (r < H) {
       const size_t off = (size_t)r * pitch + (size_t)c * CH;
       if (fast) {
-        uint32_t* dp = reinterpret_cast<uint32_t*>(im.dst + off);
-        if constexpr (RGB) {
-          const uint32_t s0 = px[k][0], s1 = px[k][1], s2 = px[k][2];
-          dp[0] = add_sat4(s0, pair(delta[0], delta[0]), pair(delta[0], delta[1]));     // R0 G0 B0 R1
-          dp[1] = add_sat4(s1, pair(delta[1], delta[1]), pair(delta[2], delta[2]));     // G1 B1 R2 G2
-          dp[2] = add_sat4(s2, pair(delta[2], delta[3]), pair(delta[3], delta[3]));     // B2 R3 G3 B3
-        } else {
-          dp[0] = add_sat4(px[k][0], pair(delta[0], delta[1]), pair(delta[2], delta[3]));
-        }
+        store_delta4<RGB>(im.dst + off, px[k], delta);
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -198,19 +169,6 @@ __global__ void __launch_bounds__(THREADS) sharpen_kernel(const Args a) {
   }
 }
 
-// bytes [first, first + count) of every image, as they are (the chroma rows of a planar YUV 4:2:0 image); grid (blocks, n)
-__global__ void __launch_bounds__(THREADS) copy_bytes_kernel(const Args a, size_t first, size_t count) {
-  const Image im = a.im[blockIdx.y];
-  const uint8_t* s = im.src + first;
-  uint8_t* d = im.dst + first;
-  const size_t i0 = (size_t)blockIdx.x * THREADS + threadIdx.x, step = (size_t)gridDim.x * THREADS;
-  if (((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d) | count) & 15) == 0) {
-    for (size_t i = i0; i < count / 16; i += step) reinterpret_cast<uint4*>(d)[i] = reinterpret_cast<const uint4*>(s)[i];
-  } else {
-    for (size_t i = i0; i < count; i += step) d[i] = s[i];
-  }
-}
-
 template <bool RGB>
 static int launch_r(const Args& a, int radius, hipStream_t stream) {
   const dim3 grid((unsigned)((a.W + TILE_W - 1) / TILE_W), (unsigned)((a.H + TILE_H - 1) / TILE_H), (unsigned)a.n_images);
@@ -225,15 +183,6 @@ static int launch_r(const Args& a, int radius, hipStream_t stream) {
 int launch(const Args& a, bool rgb, int radius, hipStream_t stream) {
   if (a.n_images <= 0 || a.H <= 0 || a.W <= 0) return 0;
   return rgb ? launch_r<true>(a, radius, stream) : launch_r<false>(a, radius, stream);
-}
-
-int launch_copy(const Args& a, size_t first, size_t count, hipStream_t stream) {
-  if (a.n_images <= 0 || count == 0) return 0;
-  const size_t blocks = (count / 16 + THREADS - 1) / THREADS;
-  const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks)), (unsigned)a.n_images);
-  hipLaunchKernelGGL(copy_bytes_kernel, grid, dim3(THREADS), 0, stream, a, first, count);
-  MI_LAUNCH_CHECK();
-  return 0;
 }
 
 }  // namespace shp

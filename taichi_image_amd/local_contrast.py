@@ -15,17 +15,10 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _native, types
+from . import _native, _u8_stage as _u8, types
 
 MAX_TILES = 16
 MAX_SIDE = 32768
-
-
-def _number(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"LocalContrast.{name} must be a number, got {v!r}")
-    if not math.isfinite(float(v)) or not lo <= float(v) <= hi:
-        raise ValueError(f"LocalContrast.{name} must be finite and within [{lo}, {hi}], got {v!r}")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -45,8 +38,8 @@ class LocalContrast:
             raise ValueError(f"LocalContrast.tiles must be a pair of integers in 1 .. {MAX_TILES}, got {t!r}")
         object.__setattr__(self, "tiles", (int(t[0]), int(t[1])))
         if self.clip_limit is not None:
-            _number("clip_limit", self.clip_limit, 1, 64)
-        _number("strength", self.strength, 0, 1)
+            _u8.number("LocalContrast", "clip_limit", self.clip_limit, 1, 64)
+        _u8.number("LocalContrast", "strength", self.strength, 0, 1)
 
     @property
     def clip_q8(self) -> int:
@@ -56,7 +49,7 @@ class LocalContrast:
     @property
     def strength_q6(self) -> int:
         """S = floor(strength * 64 + 0.5), 0 .. 64."""
-        return int(math.floor(float(self.strength) * 64 + 0.5))
+        return _u8.q6(self.strength)
 
     def _arg(self) -> "_native.LocalContrast":
         """The mi_isp_local_contrast of these settings."""
@@ -65,9 +58,7 @@ class LocalContrast:
 
 def check_local_contrast(value):
     """The LocalContrast of a constructor / set() argument, None for None; ValueError otherwise."""
-    if value is None or isinstance(value, LocalContrast):
-        return value
-    raise ValueError(f"local_contrast must be None or a LocalContrast, got {type(value).__name__}")
+    return _u8.check_setting(value, LocalContrast, "local_contrast")
 
 
 def check_shape(H, W, lc: LocalContrast):
@@ -82,37 +73,22 @@ def apply(images, lc: LocalContrast, yuv420=False, inplace=False):
     planar (H * 3 / 2, W) ones.  inplace=True overwrites and returns `images` (the apply step is pointwise once the LUTs
     exist), else new tensors come back.  Four launches per 32 images on the device's current stream, no host
     synchronisation; the workspace (1280 bytes per tile and image) comes from torch's allocator."""
-    first = images[0]
-    if yuv420:
-        H, W = first.shape[0] * 2 // 3, first.shape[1]
-        fn = _native.lib().mi_isp_local_contrast_yuv420_batch
-    else:
-        H, W = first.shape[:2]
-        fn = _native.lib().mi_isp_local_contrast_rgb_batch
+    H, W = _u8.geometry(images[0], yuv420)
     check_shape(H, W, lc)
-    outs = images if inplace else [torch.empty_like(im) for im in images]
+    arg = lc._arg()
+    ws = None
     if H * W:
-        arg = lc._arg()
-        ws = torch.empty(int(_native.lib().mi_isp_local_contrast_workspace_bytes(len(images), arg)), dtype=torch.uint8,
-                         device=first.device)
-        _native.check(fn(_native.ptr_array(images), _native.ptr_array(outs), len(images), H, W, arg, ws.data_ptr(),
-                         _native.stream_ptr(first.device)))
-    return outs
-
-
-def _checked(image, lc, what):
-    if not isinstance(lc, LocalContrast):
-        raise ValueError(f"local_contrast must be a LocalContrast, got {type(lc).__name__}")
-    if types.ti_type(image) != types.u8:
-        raise ValueError(f"{what} takes a u8 image, got {types.ti_type(image)}")
-    return types.to_device(image)
+        nbytes = int(_native.lib().mi_isp_local_contrast_workspace_bytes(len(images), arg))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=images[0].device)    # (alive until the launches are queued)
+    return _u8.apply_batch(images, "mi_isp_local_contrast_rgb_batch", "mi_isp_local_contrast_yuv420_batch", arg, yuv420,
+                           inplace, (ws.data_ptr() if ws is not None else 0,))
 
 
 def clahe(image, lc: LocalContrast):
     """The operator on an (H, W, 3) u8 RGB image: the same delta, computed on the luma, is added to R, G and B, so hue is
     kept up to saturation.  numpy in gives numpy out, torch in gives torch out on the same device (always a new array).
     DESIGN.md 3, "Local contrast"."""
-    dev = _checked(image, lc, "clahe")
+    dev = _u8.checked(image, lc, LocalContrast, "clahe", "local_contrast")
     assert dev.ndim == 3 and dev.shape[2] == 3, "image must be (H, W, 3)"
     return types.from_device(apply([dev], lc)[0], image)
 
@@ -121,6 +97,6 @@ def clahe_yuv420(yuv, lc: LocalContrast):
     """The operator on a planar YUV 4:2:0 u8 image (H * 3 / 2, W) as color.rgb_yuv420_image makes it: the Y plane (H, W)
     is the luma, out = clamp(Y + delta, 0, 255), and the chroma rows come back unchanged.  This is NOT the YUV image of the
     RGB result: there the luma is (77, 150, 29) / 256 of RGB and the delta saturates per channel.  Containers as clahe."""
-    dev = _checked(yuv, lc, "clahe_yuv420")
+    dev = _u8.checked(yuv, lc, LocalContrast, "clahe_yuv420", "local_contrast")
     assert dev.ndim == 2 and dev.shape[0] % 3 == 0 and dev.shape[1] % 2 == 0, "yuv must be (H * 3 / 2, W) with H, W even"
     return types.from_device(apply([dev], lc, yuv420=True)[0], yuv)

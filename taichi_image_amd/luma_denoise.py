@@ -9,18 +9,9 @@ noise reduction and before local contrast and sharpening; `luma_denoise` filters
 from __future__ import annotations
 
 import dataclasses
-import math
 from typing import Optional
 
-import numpy as np
-import torch
-
-from . import _native, types
-
-
-def _int_field(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError(f"LumaDenoise.{name} must be an integer in {lo} .. {hi}, got {v!r}")
+from . import _native, _u8_stage as _u8, types
 
 
 @dataclasses.dataclass(frozen=True)
@@ -35,20 +26,16 @@ class LumaDenoise:
     strength: float = 1.0
 
     def __post_init__(self):
-        _int_field("radius", self.radius, 1, 3)
-        _int_field("threshold", self.threshold, 0, 255)
+        _u8.int_field("LumaDenoise", "radius", self.radius, 1, 3)
+        _u8.int_field("LumaDenoise", "threshold", self.threshold, 0, 255)
         if self.threshold_bright is not None:
-            _int_field("threshold_bright", self.threshold_bright, 0, 255)
-        s = self.strength
-        if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)):
-            raise ValueError(f"LumaDenoise.strength must be a number, got {s!r}")
-        if not math.isfinite(float(s)) or not 0 <= float(s) <= 1:
-            raise ValueError(f"LumaDenoise.strength must be finite and within [0, 1], got {s!r}")
+            _u8.int_field("LumaDenoise", "threshold_bright", self.threshold_bright, 0, 255)
+        _u8.number("LumaDenoise", "strength", self.strength, 0, 1)
 
     @property
     def strength_q6(self) -> int:
         """S = floor(strength * 64 + 0.5): the weight the filter multiplies with, 0 .. 64."""
-        return int(math.floor(float(self.strength) * 64 + 0.5))
+        return _u8.q6(self.strength)
 
     def _arg(self) -> "_native.LumaDenoise":
         """The mi_isp_luma_denoise of these settings."""
@@ -58,35 +45,15 @@ class LumaDenoise:
 
 def check_luma_denoise(value):
     """The LumaDenoise of a constructor / set() argument, None for None; ValueError otherwise."""
-    if value is None or isinstance(value, LumaDenoise):
-        return value
-    raise ValueError(f"luma_denoise must be None or a LumaDenoise, got {type(value).__name__}")
+    return _u8.check_setting(value, LumaDenoise, "luma_denoise")
 
 
 def apply(images, settings: LumaDenoise, yuv420=False):
     """New tensors holding the filter of the u8 device tensors `images` (one shape, contiguous, one device): (H, W, 3)
     images, or with yuv420 planar (H * 3 / 2, W) ones; one launch per 32 images (and one copy of the chroma rows for the
     planar form) on the device's current stream, no host synchronisation."""
-    first = images[0]
-    outs = [torch.empty_like(im) for im in images]
-    if yuv420:
-        H, W = first.shape[0] * 2 // 3, first.shape[1]
-        fn = _native.lib().mi_isp_luma_denoise_yuv420_batch
-    else:
-        H, W = first.shape[:2]
-        fn = _native.lib().mi_isp_luma_denoise_rgb_batch
-    if H * W:
-        _native.check(fn(_native.ptr_array(images), _native.ptr_array(outs), len(images), H, W, settings._arg(),
-                         _native.stream_ptr(first.device)))
-    return outs
-
-
-def _checked(image, settings, what):
-    if not isinstance(settings, LumaDenoise):
-        raise ValueError(f"settings must be a LumaDenoise, got {type(settings).__name__}")
-    if types.ti_type(image) != types.u8:
-        raise ValueError(f"{what} takes a u8 image, got {types.ti_type(image)}")
-    return types.to_device(image)
+    return _u8.apply_batch(images, "mi_isp_luma_denoise_rgb_batch", "mi_isp_luma_denoise_yuv420_batch", settings._arg(),
+                           yuv420)
 
 
 def luma_denoise(image, settings: LumaDenoise):
@@ -94,7 +61,7 @@ def luma_denoise(image, settings: LumaDenoise):
     and R, G and B take the same delta, so hue and saturation stay up to the clip.  numpy in gives numpy out, torch in
     gives torch out on the same device (a new tensor: the stencil cannot run in place).  DESIGN.md 3, "Luma noise
     reduction"."""
-    dev = _checked(image, settings, "luma_denoise")
+    dev = _u8.checked(image, settings, LumaDenoise, "luma_denoise")
     assert dev.ndim == 3 and dev.shape[2] == 3, "image must be (H, W, 3)"
     return types.from_device(apply([dev], settings)[0], image)
 
@@ -102,6 +69,6 @@ def luma_denoise(image, settings: LumaDenoise):
 def luma_denoise_yuv420(yuv, settings: LumaDenoise):
     """The filter on a planar YUV 4:2:0 u8 image (H * 3 / 2, W; H and W even) as color.split_yuv_420 reads it: the Y plane
     filtered with L = Y, the chroma rows unchanged.  Containers as luma_denoise."""
-    dev = _checked(yuv, settings, "luma_denoise_yuv420")
+    dev = _u8.checked(yuv, settings, LumaDenoise, "luma_denoise_yuv420")
     assert dev.ndim == 2 and dev.shape[0] % 3 == 0 and dev.shape[1] % 2 == 0, "yuv must be (H * 3 / 2, W) with H, W even"
     return types.from_device(apply([dev], settings, yuv420=True)[0], yuv)

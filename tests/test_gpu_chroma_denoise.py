@@ -14,7 +14,7 @@ from oracle import isp_oracle as O
 from tests import chroma_denoise_ref as C
 from tests import local_contrast_ref as R
 from tests import sharpen_ref as S
-from tests.util import _count_calls, assert_exact, natural_packed12
+from tests.util import _count_calls, assert_exact, natural_packed12, u8_batch_with_sentinels
 
 pytestmark = pytest.mark.gpu
 
@@ -165,6 +165,26 @@ def test_batches(ti, rng, dev, n):
         ref = C.chroma_denoise_yuv420(yuvs[k], 2, 8, 12, 1.0)
         assert not np.array_equal(ref, yuvs[k])
         assert_exact(outs[k].cpu().numpy(), ref, f"yuv image {k} of {n}")
+
+
+@pytest.mark.parametrize("H,W", [(8, 16), (6, 10)])
+def test_the_second_launch_group(ti, rng, dev, H, W):
+    """33 images of distinct contents through the entry points themselves, on the dword path (8 x 16) and on the byte path
+    (6 x 10): image 32 is the second group of 32 and, for the planar form, the second copy of the Y rows.  Sentinel bytes
+    behind every destination."""
+    s, args = ti.ChromaDenoise(2, 8, 12, 1.0), (2, 8, 12, 1.0)
+    imgs = [S.scene_u8(rng, H, W, sigma=0.03 + 0.002 * k) for k in range(33)]
+    refs = [C.chroma_denoise_rgb(i, *args) for i in imgs]
+    assert not np.array_equal(refs[32], imgs[32]) and not np.array_equal(refs[32], refs[0])
+    outs = u8_batch_with_sentinels("mi_isp_chroma_denoise_rgb_batch", imgs, H, W, (s._arg(),), dev)
+    for k in range(33):
+        assert_exact(outs[k], refs[k], f"{H}x{W} image {k}")
+    yuvs = [C.scene_yuv420(rng, H, W) for _ in range(33)]
+    refs = [C.chroma_denoise_yuv420(y, *args) for y in yuvs]
+    assert not np.array_equal(refs[32], yuvs[32])
+    outs = u8_batch_with_sentinels("mi_isp_chroma_denoise_yuv420_batch", yuvs, H, W, (s._arg(),), dev)
+    for k in range(33):
+        assert_exact(outs[k], refs[k], f"{H}x{W} yuv image {k}")
 
 
 # ---- through the ISP ------------------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@ import torch
 from oracle import isp_oracle as O
 from tests import local_contrast_ref as R
 from tests import sharpen_ref as S
-from tests.util import _count_calls, assert_exact, natural_packed12
+from tests.util import _count_calls, assert_exact, natural_packed12, u8_batch_with_sentinels
 
 pytestmark = pytest.mark.gpu
 
@@ -195,6 +195,31 @@ def test_batches(ti, rng, dev, n):
     outs = ti.local_contrast.apply([torch.from_numpy(y).to(dev) for y in yuvs], lc, yuv420=True)
     for k in range(n):
         assert_exact(outs[k].cpu().numpy(), R.clahe_yuv420(yuvs[k], (2, 3), 2.0, 0.75), f"yuv image {k} of {n}")
+
+
+@pytest.mark.parametrize("H,W", [(8, 16), (6, 10)])
+def test_the_second_launch_group(ti, rng, dev, H, W):
+    """33 images of distinct contents through the entry points themselves, on the dword path (8 x 16) and on the byte path
+    (6 x 10), none filtered in place and every second one: image 32 is the second group of 32 - the second part of the
+    workspace - and, for the planar form, the second copy of the chroma rows, which takes only the images not filtered in
+    place.  Sentinel bytes behind every destination."""
+    from taichi_image_amd import _native
+    tiles, clip, strength = (2, 3), 2.0, 0.75
+    arg = ti.LocalContrast(tiles, clip, strength)._arg()
+    ws = torch.empty(int(_native.lib().mi_isp_local_contrast_workspace_bytes(33, arg)), dtype=torch.uint8, device=dev)
+    imgs = [S.scene_u8(rng, H, W, sigma=0.03 + 0.002 * k) for k in range(33)]
+    yuvs = [rng.integers(0, 256, (H * 3 // 2, W)).astype(np.uint8) for _ in range(33)]
+    refs = [R.clahe_rgb(i, tiles, clip, strength) for i in imgs]
+    yuv_refs = [R.clahe_yuv420(y, tiles, clip, strength) for y in yuvs]
+    assert not np.array_equal(refs[32], imgs[32]) and not np.array_equal(refs[32], refs[0])
+    assert not np.array_equal(yuv_refs[32], yuvs[32])
+    for in_place in ((), range(0, 33, 2), range(1, 33, 2)):
+        outs = u8_batch_with_sentinels(ENTRY_POINTS[0], imgs, H, W, (arg, ws.data_ptr()), dev, in_place)
+        for k in range(33):
+            assert_exact(outs[k], refs[k], f"{H}x{W} image {k}, in place: {list(in_place)[:2]}")
+        outs = u8_batch_with_sentinels(ENTRY_POINTS[1], yuvs, H, W, (arg, ws.data_ptr()), dev, in_place)
+        for k in range(33):
+            assert_exact(outs[k], yuv_refs[k], f"{H}x{W} yuv image {k}, in place: {list(in_place)[:2]}")
 
 
 def test_in_place(ti, rng, dev):

@@ -7,7 +7,7 @@ import torch
 
 from oracle import isp_oracle as O
 from tests import sharpen_ref as S
-from tests.util import _count_calls, assert_exact, natural_packed12
+from tests.util import _count_calls, assert_exact, natural_packed12, u8_batch_with_sentinels
 
 pytestmark = pytest.mark.gpu
 
@@ -117,6 +117,27 @@ def test_batches(ti, rng, dev, n):
     outs = ti.sharpen.apply([torch.from_numpy(y).to(dev) for y in yuvs], s, yuv420=True)
     for k in range(n):
         assert_exact(outs[k].cpu().numpy(), S.sharpen_yuv420(yuvs[k], 1.5, 2, 0, 8), f"yuv image {k} of {n}")
+
+
+@pytest.mark.parametrize("H,W", [(8, 16), (6, 10)])
+def test_the_second_launch_group(ti, rng, dev, H, W):
+    """33 images of distinct contents through the entry points themselves, on the dword path (8 x 16) and on the byte path
+    (6 x 10): image 32 is the second group of 32 and, for the planar form, the second copy of the chroma rows.  test_batches
+    has the second group on the dword path through apply(); what this adds is the byte path, the direct call and the
+    sentinel bytes behind every destination."""
+    s, args = ti.Sharpen(1.5, 2, 0, 8), (1.5, 2, 0, 8)
+    imgs = [S.scene_u8(rng, H, W, sigma=0.03 + 0.002 * k) for k in range(33)]
+    refs = [S.sharpen_rgb(i, *args) for i in imgs]
+    assert not np.array_equal(refs[32], imgs[32]) and not np.array_equal(refs[32], refs[0])
+    outs = u8_batch_with_sentinels(ENTRY_POINTS[0], imgs, H, W, (s._arg(),), dev)
+    for k in range(33):
+        assert_exact(outs[k], refs[k], f"{H}x{W} image {k}")
+    yuvs = [rng.integers(0, 256, (H * 3 // 2, W)).astype(np.uint8) for _ in range(33)]
+    refs = [S.sharpen_yuv420(y, *args) for y in yuvs]
+    assert not np.array_equal(refs[32], yuvs[32])
+    outs = u8_batch_with_sentinels(ENTRY_POINTS[1], yuvs, H, W, (s._arg(),), dev)
+    for k in range(33):
+        assert_exact(outs[k], refs[k], f"{H}x{W} yuv image {k}")
 
 
 # ---- the Y-plane form --------------------------------------------------------------------------------------------------

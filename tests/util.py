@@ -203,3 +203,40 @@ def nan_on_grid(img, stride=8, where=((0, 0), (-1, -1)), ch=1):
     for r, c in where:
         out[last_r if r == -1 else r, last_c if c == -1 else c, ch] = np.nan
     return out
+
+
+SENTINEL = 0xA5
+
+
+def u8_batch_with_sentinels(entry, images, H, W, args, dev, in_place=()):
+    """One call of the library's u8 batch entry point `entry` (src, dst, n, H, W, *args, stream) on the numpy u8 images (one
+    shape), every source and every destination a slot of one device buffer with a run of SENTINEL bytes behind it (slots 16
+    bytes aligned, so a W % 4 == 0 image keeps the dword path); the images whose index is in `in_place` are their own
+    destination.  Returns the outputs as numpy arrays after asserting that every sentinel run, every source filtered into
+    another image and every destination slot of an image filtered in place came back as it went in."""
+    import ctypes
+    import torch
+    from taichi_image_amd import _native
+    n, size = len(images), images[0].size
+    stride = (size + 64 + 15) // 16 * 16
+    host = np.full((n, stride), SENTINEL, np.uint8)
+    for k, im in enumerate(images):
+        host[k, :size] = im.ravel()
+    src = torch.from_numpy(host).to(dev)
+    dst = torch.full((n, stride), SENTINEL, dtype=torch.uint8, device=dev)
+    sp = [src[k].data_ptr() for k in range(n)]
+    dp = [sp[k] if k in in_place else dst[k].data_ptr() for k in range(n)]
+    rc = getattr(_native.lib(), entry)((ctypes.c_void_p * n)(*sp), (ctypes.c_void_p * n)(*dp), n, H, W, *args,
+                                       _native.stream_ptr(dev))
+    _native.check(rc)
+    s, d = src.cpu().numpy(), dst.cpu().numpy()
+    outs = []
+    for k in range(n):
+        moved = k not in in_place
+        assert (s[k, size:] == SENTINEL).all() and (d[k, size:] == SENTINEL).all(), f"image {k}: bytes behind it were written"
+        if moved:
+            assert np.array_equal(s[k], host[k]), f"image {k}: its source was written"
+        else:
+            assert (d[k] == SENTINEL).all(), f"image {k}, filtered in place: its unused slot was written"
+        outs.append((d if moved else s)[k, :size].reshape(images[k].shape).copy())
+    return outs
