@@ -439,6 +439,40 @@ int mi_isp_highlights_raw_batch(const void* const* src_host, void* const* cfa_ho
                                 const mi_isp_highlights* highlights_host, int out_f32_plain, void* stream);
 int mi_isp_highlights_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, int pattern,
                           const mi_isp_highlights* highlights_host, void* stream);
+/* ---- dynamic defects ("Dynamic defects") ----------------------------------------------------------------------
+ * Defective-pixel correction without a map, whatever the Bayer pattern.  x(p) is the f32 value a loader computes before
+ * shading and the cast.  The taps of p = (r, c) are its eight same-site neighbours, in this order:
+ *   q0 .. q7 = (r-2,c-2) (r-2,c) (r-2,c+2) (r,c-2) (r,c+2) (r+2,c-2) (r+2,c) (r+2,c+2)
+ * A tap is kept when it is inside the frame, not listed in the frame's defect mask and its x is finite; n counts them.
+ * With k = tolerate (0 or 1), hi / lo the (k+1)-th largest / smallest kept tap and T(v) = threshold + slope max(v, 0)
+ * (every operation one f32 rounding, never contracted):
+ *   p is a candidate when n >= 2k + 1, x(p) is finite and p is not listed
+ *   p is hot  when it is a candidate, hot  != 0 and x(p) - hi > T(hi)
+ *   p is dead when it is a candidate, dead != 0 and lo - x(p) > T(lo)
+ *   of the pairs (q1,q6) (q3,q4) (q0,q7) (q2,q5) with both taps kept, the one of the smallest |a - b| (the earlier on a
+ *   tie) gives m = (a + b) 0.5; a hot pixel gets y = min(m, hi), or hi without such a pair; a dead one y = max(m, lo), or
+ *   lo; every other pixel (a listed one too) keeps y = x(p), the same bits
+ *   cfa = cast_work(y * g(p))      (g the lens shading gain of shading_host, 1 for NULL)
+ * Source kinds, levels, grids, defect maps and outputs as mi_isp_highlights_raw(_batch), out_f32_plain included (the
+ * output is the H x W f32 y itself; shading_host must be NULL).  flags (flags_host: one pointer per frame), when not NULL,
+ * takes H rows of (W + 31) / 32 u32 words on the device in the layout of mi_isp_defects.mask_dev: bit c & 31 of word
+ * c >> 5 is set iff pixel (r, c) was hot or dead; every word is written.
+ *  - mi_isp_dynamic_defects_cfa: a normalised H x W CFA of dtype MI_F16 / MI_F32 (no levels, gain or mask), out of the same dtype.
+ * Host-side checks before any launch (error text names "dynamic defects"): threshold finite > 0, slope finite >= 0,
+ * tolerate 0 or 1, hot or dead set, shapes, dtypes, kinds, levels, grids, NULL pointers.  n == 0 and H * W == 0 are
+ * successful no-ops. */
+typedef struct { float threshold, slope; int32_t tolerate, hot, dead; } mi_isp_dynamic_defects;
+int mi_isp_dynamic_defects_raw(const void* src_dev, void* cfa_dev, int H, int W, int src_kind, int ids_format,
+                               int work_dtype, const mi_isp_levels* levels_host, const mi_isp_shading* shading_host,
+                               const mi_isp_defects* defects_host, const mi_isp_dynamic_defects* dynamic_host,
+                               int out_f32_plain, void* stream, uint32_t* flags_dev);
+int mi_isp_dynamic_defects_raw_batch(const void* const* src_host, void* const* cfa_host, int n, int H, int W, int src_kind,
+                                     int ids_format, int work_dtype, const mi_isp_levels* levels_host,
+                                     const mi_isp_shading* shading_host, const mi_isp_defects* const* defects_host,
+                                     const mi_isp_dynamic_defects* dynamic_host, int out_f32_plain, void* stream,
+                                     uint32_t* const* flags_host);
+int mi_isp_dynamic_defects_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype,
+                               const mi_isp_dynamic_defects* dynamic_host, void* stream, uint32_t* flags_dev);
 /* ---- directional demosaic ("Directional demosaic") --------------------------------------------------------
  * A direction-adaptive alternative to mi_isp_demosaic's 13-tap filter, in f32 with one rounding per operation, in the
  * order written, never contracted: the output is the contract's bit for bit.  X(r, c) is the f32 value of the H x W CFA

@@ -52,6 +52,12 @@ class Denoise(ctypes.Structure):
                 ("radius", c_int32)]
 
 
+class DynamicDefects(ctypes.Structure):
+    """mi_isp_dynamic_defects: the threshold and its slope, how many of a pixel's neighbours may be defective themselves
+    (0 or 1), and whether hot and dead pixels are looked for."""
+    _fields_ = [("threshold", c_float), ("slope", c_float), ("tolerate", c_int32), ("hot", c_int32), ("dead", c_int32)]
+
+
 class Highlights(ctypes.Structure):
     """mi_isp_highlights: the mode (0 rebuild, 1 clip), the clip level, the balance gains of R, G, B and, when not NULL,
     3 f32 on the device that override them."""
@@ -217,6 +223,12 @@ SIGNATURES = {
                                             POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(Highlights), c_int,
                                             _P]),
     "mi_isp_highlights_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Highlights), _P]),
+    "mi_isp_dynamic_defects_raw": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading),
+                                           POINTER(Defects), POINTER(DynamicDefects), c_int, _P, _P]),
+    "mi_isp_dynamic_defects_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
+                                                 POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(DynamicDefects),
+                                                 c_int, _P, POINTER(_P)]),
+    "mi_isp_dynamic_defects_cfa": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(DynamicDefects), _P, _P]),
     "mi_isp_demosaic_directional_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "mi_isp_demosaic_directional_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
                                                       c_int, POINTER(Levels), POINTER(Shading), POINTER(c_float), _P]),

@@ -23,6 +23,7 @@ from . import _native, bayer, interpolate, packed, types
 from . import defects as _defects
 from . import denoise as _dn
 from . import highlights as _hl
+from . import dynamic_defects as _ddp
 from . import chromatic as _ca
 from . import temporal as _tn
 from . import exposure_merge as _em
@@ -42,6 +43,7 @@ from . import distributed as _dist
 _OPTIONAL_STAGES = (
     ("raw_denoise", "_raw_denoise", _dn.check_raw_denoise),
     ("highlights", "_highlights", _hl.check_highlights),
+    ("dynamic_defects", "_dynamic_defects", _ddp.check_dynamic_defects),
     ("chromatic_aberration", "_chromatic", _ca.check_chromatic_aberration),
     ("temporal_denoise", "_temporal", _tn.check_temporal_denoise),
     ("exposure_merge", "_merge", _em.check_exposure_merge),
@@ -319,7 +321,8 @@ def camera_isp(name: str, dtype=types.f32):
                      local_tonemap=None,
                      luma_denoise=None,
                      demosaic=None,
-                     resample=None):
+                     resample=None,
+                     dynamic_defects=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -337,6 +340,7 @@ def camera_isp(name: str, dtype=types.f32):
                 _wb.check_seed(white_balance)
             raw_denoise = _dn.check_raw_denoise(raw_denoise)
             highlights = _hl.check_highlights(highlights)
+            dynamic_defects = _ddp.check_dynamic_defects(dynamic_defects)
             chromatic_aberration = _ca.check_chromatic_aberration(chromatic_aberration)
             temporal_denoise = _tn.check_temporal_denoise(temporal_denoise)
             exposure_merge = _em.check_exposure_merge(exposure_merge)
@@ -396,6 +400,9 @@ def camera_isp(name: str, dtype=types.f32):
             # highlight reconstruction (an extension): the Highlights the loaders apply to clipped raw pixels, or None (the
             # loaders run exactly as without it).  DESIGN.md 3, "Highlight reconstruction".
             self._highlights = highlights
+            # dynamic defects (an extension): the DynamicDefects the loaders detect and replace defective raw pixels with,
+            # without a map, or None (the loaders run exactly as without it).  DESIGN.md 3, "Dynamic defects".
+            self._dynamic_defects = dynamic_defects
             # chromatic aberration (an extension): the ChromaticAberration the loaders correct on the CFA, or None (the
             # loaders run exactly as without it).  DESIGN.md 3, "Chromatic aberration".
             self._chromatic = chromatic_aberration
@@ -450,7 +457,7 @@ def camera_isp(name: str, dtype=types.f32):
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
                 highlights=None, chromatic_aberration=None, temporal_denoise=None, exposure_merge=None,
-                local_tonemap=None, luma_denoise=None, demosaic=None, resample=None):
+                local_tonemap=None, luma_denoise=None, demosaic=None, resample=None, dynamic_defects=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -473,7 +480,8 @@ def camera_isp(name: str, dtype=types.f32):
             local_tonemap (the extension): None leaves it, False turns it off, a LocalTonemap replaces it.
             luma_denoise (the extension): None leaves it, False turns it off, a LumaDenoise replaces it.
             demosaic (the extension): None leaves it, False turns it off, a Demosaic replaces it.
-            resample (the extension): None leaves it, False turns it off, a Resample replaces it."""
+            resample (the extension): None leaves it, False turns it off, a Resample replaces it.
+            dynamic_defects (the extension): None leaves it, False turns it off, a DynamicDefects replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -486,7 +494,8 @@ def camera_isp(name: str, dtype=types.f32):
             given = dict(raw_denoise=raw_denoise, highlights=highlights, chromatic_aberration=chromatic_aberration,
                          temporal_denoise=temporal_denoise, exposure_merge=exposure_merge, local_tonemap=local_tonemap,
                          sharpen=sharpen, local_contrast=local_contrast, chroma_denoise=chroma_denoise,
-                         luma_denoise=luma_denoise, color_lut=color_lut, demosaic=demosaic, resample=resample)
+                         luma_denoise=luma_denoise, color_lut=color_lut, demosaic=demosaic, resample=resample,
+                         dynamic_defects=dynamic_defects)
             replaced = {name: check(given[name]) for name, _, check in _OPTIONAL_STAGES
                         if given[name] is not None and given[name] is not False}
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
@@ -626,7 +635,7 @@ def camera_isp(name: str, dtype=types.f32):
         def _raw_stage_on(self):
             """True when a loader of single frames goes through _raw_chain."""
             return (self._highlights is not None or self._chromatic is not None or self._temporal is not None
-                    or self._raw_denoise is not None)
+                    or self._raw_denoise is not None or self._dynamic_defects is not None)
 
         @property
         def raw_denoise(self) -> Optional[_dn.RawDenoise]:
@@ -637,6 +646,11 @@ def camera_isp(name: str, dtype=types.f32):
         def highlights(self) -> Optional[_hl.Highlights]:
             """The Highlights the loaders apply, or None."""
             return self._highlights
+
+        @property
+        def dynamic_defects(self) -> Optional[_ddp.DynamicDefects]:
+            """The DynamicDefects the loaders apply, or None."""
+            return self._dynamic_defects
 
         def _highlights_arg(self):
             """The mi_isp_highlights of a load: the balance gains are the AWB gains on the device with AWB on, else
@@ -681,15 +695,15 @@ def camera_isp(name: str, dtype=types.f32):
 
         def _raw_chain(self, srcs, h, w, kind, ids_format, lv, maps, hists=None, brackets=None):
             """The raw chain, the one route of every loader with a raw stage on: the raw stages that are on, in the order
-            exposure merge, highlight reconstruction, chromatic aberration, temporal noise reduction, raw noise reduction,
-            one launch each for the raw frames srcs (one shape, source kind `kind`; with exposure merge on brackets holds
+            exposure merge, dynamic defects, highlight reconstruction, chromatic aberration, temporal noise reduction, raw
+            noise reduction, one launch each for the raw frames srcs (one shape, source kind `kind`; with exposure merge on brackets holds
             the E frames of each, and srcs their first), then the defect fix-up of each frame with a map (maps: one
             DefectMap or None per frame).  A stage that is not the last writes the plain f32 y, which the next takes as an
             f32 source without levels; the last applies the grid and the cast; all read the same masks.  The temporal
             stage reads and writes the planes of hists (one checked TemporalHistory per frame), which swap once its launch
             was issued; when it is not the last, its new history planes are the y the next stage reads.  DESIGN.md 3, "Raw
-            noise reduction", "Highlight reconstruction", "Exposure merge", "Chromatic aberration" and "Temporal noise
-            reduction"."""
+            noise reduction", "Highlight reconstruction", "Exposure merge", "Chromatic aberration", "Temporal noise
+            reduction" and "Dynamic defects"."""
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             n = len(srcs)
@@ -703,6 +717,10 @@ def camera_isp(name: str, dtype=types.f32):
                 flat = _native.ptr_array([f for b in brackets for f in b])
                 stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_merge_raw_batch(
                     flat, o, n, h, w, k, f, dtype.code, l, s, p_maps, em_arg, plain, stream))
+            if self._dynamic_defects is not None:        # (no flag plane: the loaders want the pixels only)
+                dd_arg = self._dynamic_defects._arg()
+                stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_dynamic_defects_raw_batch(
+                    i, o, n, h, w, k, f, dtype.code, l, s, p_maps, dd_arg, plain, stream, None))
             if self._highlights is not None:
                 hl_arg = self._highlights_arg()
                 stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_highlights_raw_batch(
@@ -1502,6 +1520,7 @@ def camera_isp(name: str, dtype=types.f32):
                      and self._applied_shading() is None      # (lens shading or AWB: the two calls below)
                      and self._raw_denoise is None            # (raw noise reduction: the two calls below)
                      and self._highlights is None             # (highlight reconstruction: the two calls below)
+                     and self._dynamic_defects is None        # (dynamic defects: the two calls below)
                      and self._chromatic is None              # (chromatic aberration: the two calls below)
                      and self._temporal is None               # (temporal noise reduction: the two calls below)
                      and self._ltm is None                    # (local tone mapping: the two calls below)

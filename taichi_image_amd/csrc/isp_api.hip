@@ -16,6 +16,7 @@
 #include "isp_awb.h"
 #include "isp_denoise.h"
 #include "isp_highlights.h"
+#include "isp_dynamic_defects.h"
 #include "isp_demosaic_dir.h"
 #include "isp_chromatic.h"
 #include "isp_temporal.h"
@@ -885,6 +886,93 @@ extern "C" int mi_isp_highlights_cfa(const void* in, void* out, int H, int W, in
   a.f[0] = {in, out, nullptr};
   return hl::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
                     (hipStream_t)stream);
+}
+
+// ---- dynamic defects (isp_dynamic_defects.h; DESIGN.md 3, "Dynamic defects") -----------------------------------------
+static const RawStage kDynamicDefects = {"dynamic defects", "dynamic defects: ", "frame"};
+
+// the operator's settings, checked on the host; fills the operator members of a
+static int dynamic_defects_settings(ddp::Args& a, const mi_isp_dynamic_defects* d, const char* who) {
+  MI_REQUIRE(d, "%s: null dynamic defects settings", who);
+  MI_REQUIRE(std::isfinite(d->threshold) && d->threshold > 0.f, "%s: dynamic defects threshold %g must be finite and > 0",
+             who, (double)d->threshold);
+  MI_REQUIRE(std::isfinite(d->slope) && d->slope >= 0.f, "%s: dynamic defects slope %g must be finite and >= 0", who,
+             (double)d->slope);
+  MI_REQUIRE(d->tolerate == 0 || d->tolerate == 1, "%s: dynamic defects tolerate %d (0 or 1)", who, (int)d->tolerate);
+  MI_REQUIRE(d->hot || d->dead, "%s: dynamic defects with neither hot nor dead pixels to look for", who);
+  a.t = d->threshold;
+  a.s = d->slope;
+  a.tolerate = d->tolerate;
+  a.hot = d->hot != 0;
+  a.dead = d->dead != 0;
+  return 0;
+}
+
+// n raw frames of one geometry: every frame's pointers (defect mask and flag plane) in the kernel arguments, 32 per launch
+static int dynamic_defects_raw_impl(const void* const* src, void* const* cfa, int n, int H, int W, int kind, int ids_format,
+                                    int work_dtype, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                    const mi_isp_defects* const* defects, const mi_isp_dynamic_defects* d, int plain,
+                                    uint32_t* const* flags, void* stream, const char* who) {
+  ddp::Args a = {};
+  if (int rc = dynamic_defects_settings(a, d, who)) return rc;
+  if (int rc = raw_geometry(H, W, work_dtype, kDynamicDefects, who)) return rc;
+  if (int rc = raw_kind(kind, kDynamicDefects, who)) return rc;
+  MI_REQUIRE(n >= 0, "%s: dynamic defects with %d frames", who, n);
+  if (n == 0 || H == 0 || W == 0) return 0;
+  MI_REQUIRE(src && cfa, "%s: dynamic defects: null frame list", who);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && cfa[i], "%s: dynamic defects: frame %d has a null pointer", who, i);
+    MI_REQUIRE(src[i] != cfa[i], "%s: dynamic defects: frame %d: the CFA must not overwrite its source", who, i);
+    MI_REQUIRE(!flags || (flags[i] != src[i] && flags[i] != cfa[i]),
+               "%s: dynamic defects: frame %d: the flags must not overwrite the source or the CFA", who, i);
+  }
+  if (int rc = raw_source_rules(H, W, kind, ids_format, shading, plain, kDynamicDefects, who)) return rc;
+  int src_kind;
+  if (int rc = raw_source_setup(a, src_kind, H, W, kind, ids_format, levels, shading, defects, n, kDynamicDefects, who))
+    return rc;
+  const int out = plain ? hl::OUT_PLAIN : (work_dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32);
+  for (int i0 = 0; i0 < n; i0 += ddp::MAX_FRAMES) {
+    a.n_frames = n - i0 < ddp::MAX_FRAMES ? n - i0 : ddp::MAX_FRAMES;
+    for (int i = 0; i < a.n_frames; ++i)
+      a.f[i] = {src[i0 + i], cfa[i0 + i], mask_of(defects, i0 + i), flags ? flags[i0 + i] : nullptr};
+    if (int rc = ddp::launch(a, src_kind, out, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_dynamic_defects_raw(const void* src, void* cfa, int H, int W, int kind, int ids_format,
+                                          int work_dtype, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                          const mi_isp_defects* defects, const mi_isp_dynamic_defects* dynamic,
+                                          int out_f32_plain, void* stream, uint32_t* flags) {
+  return dynamic_defects_raw_impl(&src, &cfa, 1, H, W, kind, ids_format, work_dtype, levels, shading, &defects, dynamic,
+                                  out_f32_plain, flags ? &flags : nullptr, stream, "dynamic_defects_raw");
+}
+
+extern "C" int mi_isp_dynamic_defects_raw_batch(const void* const* src, void* const* cfa, int n, int H, int W, int kind,
+                                                int ids_format, int work_dtype, const mi_isp_levels* levels,
+                                                const mi_isp_shading* shading, const mi_isp_defects* const* defects,
+                                                const mi_isp_dynamic_defects* dynamic, int out_f32_plain, void* stream,
+                                                uint32_t* const* flags) {
+  return dynamic_defects_raw_impl(src, cfa, n, H, W, kind, ids_format, work_dtype, levels, shading, defects, dynamic,
+                                  out_f32_plain, flags, stream, "dynamic_defects_raw_batch");
+}
+
+extern "C" int mi_isp_dynamic_defects_cfa(const void* in, void* out, int H, int W, int dtype,
+                                          const mi_isp_dynamic_defects* dynamic, void* stream, uint32_t* flags) {
+  const char* who = "dynamic_defects_cfa";
+  ddp::Args a = {};
+  if (int rc = dynamic_defects_settings(a, dynamic, who)) return rc;
+  if (int rc = raw_geometry(H, W, dtype, kDynamicDefects, who)) return rc;
+  if (H == 0 || W == 0) return 0;
+  MI_REQUIRE(in && out, "%s: dynamic defects: null pointer", who);
+  MI_REQUIRE(in != out, "%s: dynamic defects: the output must not overwrite the input", who);
+  MI_REQUIRE(!flags || ((const void*)flags != in && (void*)flags != out),
+             "%s: dynamic defects: the flags must not overwrite the input or the output", who);
+  a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
+  a.n_frames = 1;
+  a.f[0] = {in, out, nullptr, flags};
+  return ddp::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
+                     (hipStream_t)stream);
 }
 
 // ---- directional demosaic (isp_demosaic_dir.h; DESIGN.md 3, "Directional demosaic") ---------------------------------

@@ -203,6 +203,13 @@ def build_parser() -> argparse.ArgumentParser:
     # limited to the balanced clip level ("clip"); T the clip level in units of the white level (default 0.98)
     tone.add_argument("--highlights", dest="highlights", choices=("rebuild", "clip"), default=None)
     tone.add_argument("--highlights-clip", dest="highlights_clip", type=float, metavar="T", default=None)
+    # dynamic defects (an extension): defective raw pixels found on the fly, without a map, and replaced from their
+    # same-site neighbours; T the threshold in units of the white level (default 0.02), S its slope over the signal
+    # (default 0.2), K in {0, 1} how many of a pixel's neighbours may be defective themselves (default 1)
+    tone.add_argument("--dynamic-defects", dest="dynamic_defects", action="store_true")
+    tone.add_argument("--dynamic-defects-threshold", dest="dynamic_defects_threshold", type=float, metavar="T", default=None)
+    tone.add_argument("--dynamic-defects-slope", dest="dynamic_defects_slope", type=float, metavar="S", default=None)
+    tone.add_argument("--dynamic-defects-tolerate", dest="dynamic_defects_tolerate", type=int, metavar="K", default=None)
     # the demosaic (an extension): "directional" interpolates along edges instead of across them; "malvar" (the default)
     # is the 13-tap filter
     tone.add_argument("--demosaic", dest="demosaic", choices=("malvar", "directional"), default=None)
@@ -270,6 +277,7 @@ def main(argv=None) -> int:
     from ..lens import LensDistortion
     from ..denoise import RawDenoise
     from ..highlights import Highlights
+    from ..dynamic_defects import DynamicDefects
     from ..demosaic import Demosaic
     from ..resample import Resample
     from ..chromatic import ChromaticAberration
@@ -301,6 +309,14 @@ def main(argv=None) -> int:
         highlights = Highlights(args.highlights, 0.98 if args.highlights_clip is None else args.highlights_clip)
     elif args.highlights_clip is not None:
         raise ValueError("--highlights-clip needs --highlights {rebuild,clip}")
+    dynamic = None
+    dyn = dict(threshold=args.dynamic_defects_threshold, slope=args.dynamic_defects_slope,
+               tolerate=args.dynamic_defects_tolerate)
+    if args.dynamic_defects:                                        # (also before any frame is read)
+        dynamic = DynamicDefects(**{k: v for k, v in dyn.items() if v is not None})
+    elif any(v is not None for v in dyn.values()):
+        raise ValueError("--dynamic-defects-threshold, --dynamic-defects-slope and --dynamic-defects-tolerate need "
+                         "--dynamic-defects")
     chromatic = None
     if args.chromatic_aberration is not None:                       # (also before any frame is read)
         k = args.chromatic_aberration
@@ -368,7 +384,8 @@ def main(argv=None) -> int:
                               highlights=highlights, chromatic_aberration=chromatic, temporal_denoise=temporal,
                               local_tonemap=local_tonemap, luma_denoise=luma_denoise,
                               demosaic=None if args.demosaic is None else Demosaic(args.demosaic),
-                              resample=None if args.resample is None else Resample(args.resample))
+                              resample=None if args.resample is None else Resample(args.resample),
+                              dynamic_defects=dynamic)
     # temporal noise reduction: the state of each camera folder, for the whole scan
     histories = [TemporalHistory() if temporal is not None else None for _ in index.cameras]
     row_bytes = args.width * 3 // 2
