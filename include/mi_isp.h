@@ -706,8 +706,9 @@ int mi_isp_resample_batch(const void* const* srcs_host, void* const* dsts_host, 
  *  - mi_isp_sharpen_yuv420_batch: n planar YUV 4:2:0 images (H * 3 / 2 rows of W bytes; H, W of the Y plane, H even): the
  *    filter with L = Y, out = clamp(Y + delta, 0, 255); the chroma rows are copied.
  * src_host / dst_host: n device pointers each, read on the host.  The stencil cannot run in place: src[i] != dst[i], and
- * the images must not overlap.  Host-side checks before any launch (error text names "sharpen"): the settings' ranges,
- * n >= 1, H, W >= 0, NULL pointers, src == dst.  H * W == 0 is a successful no-op. */
+ * no output (H * W * 3 bytes, H * W * 3 / 2 for the planar form) may overlap an input or another output of the call.
+ * Host-side checks before any launch (error text names "sharpen"): the settings' ranges, n >= 1, H, W >= 0, NULL
+ * pointers, src == dst, overlapping images.  H * W == 0 is a successful no-op. */
 typedef struct { int32_t amount_q6, radius, threshold, overshoot /* -1: none */; } mi_isp_sharpen;
 int mi_isp_sharpen_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
                              const mi_isp_sharpen* sharpen_host, void* stream);
@@ -732,12 +733,13 @@ int mi_isp_sharpen_yuv420_batch(const uint8_t* const* src_host, uint8_t* const* 
  *    apply) per 32 images, ordered by the stream.
  *  - mi_isp_local_contrast_yuv420_batch: n planar YUV 4:2:0 images (H * 3 / 2 rows of W bytes; H, W of the Y plane, both
  *    even): the operator with L = Y, out = clamp(Y + delta, 0, 255); the chroma rows are copied when src[i] != dst[i].
- * src_host / dst_host: n device pointers each, read on the host.  src[i] == dst[i] is allowed (the apply step is
- * pointwise); images that overlap otherwise are not.  ws_dev: mi_isp_local_contrast_workspace_bytes(n, lc) bytes of
+ * src_host / dst_host: n device pointers each, read on the host.  src[i] == dst[i] exactly is allowed (the apply step is
+ * pointwise); otherwise no output (H * W * 3 bytes, H * W * 3 / 2 for the planar form) may overlap an input - its own
+ * source at a shifted address or another image's - or another output of the call.  ws_dev: mi_isp_local_contrast_workspace_bytes(n, lc) bytes of
  * device memory, 16-byte aligned, contents irrelevant before and after the call (0 bytes for bad settings or n <= 0).
  * Host-side checks before any launch (error text names "local_contrast"): the settings' ranges, n >= 0, H, W >= 0,
- * H >= tiles_y and W >= tiles_x and both <= 32768 (unless H * W == 0), NULL pointers.  n == 0 and H * W == 0 are
- * successful no-ops. */
+ * H >= tiles_y and W >= tiles_x and both <= 32768 (unless H * W == 0), NULL pointers, overlapping images.  n == 0 and
+ * H * W == 0 are successful no-ops. */
 typedef struct { int32_t tiles_y, tiles_x, clip_q8 /* 0: no clip */, strength_q6; } mi_isp_local_contrast;
 size_t mi_isp_local_contrast_workspace_bytes(int n, const mi_isp_local_contrast* lc_host);
 int mi_isp_local_contrast_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
@@ -760,9 +762,9 @@ int mi_isp_local_contrast_yuv420_batch(const uint8_t* const* src_host, uint8_t* 
  *    V plane; H, W of the Y plane, both even): SL = the sum of the cell's four Y, SB = 4 U(a, b), SR = 4 V(a, b);
  *    U' = clamp(U + db, 0, 255), V' = clamp(V + dr, 0, 255); the Y rows are copied.
  * src_host / dst_host: n device pointers each, read on the host.  The stencil cannot run in place: src[i] != dst[i], and
- * the images must not overlap.  Host-side checks before any launch (error text names "chroma_denoise"): the settings'
- * ranges, n >= 0, H, W >= 0 (both even for the planar form), NULL pointers, src == dst.  n == 0 and H * W == 0 are
- * successful no-ops. */
+ * no output may overlap an input or another output of the call.  Host-side checks before any launch (error text names
+ * "chroma_denoise"): the settings' ranges, n >= 0, H, W >= 0 (both even for the planar form), NULL pointers, src == dst,
+ * overlapping images.  n == 0 and H * W == 0 are successful no-ops. */
 typedef struct { int32_t radius, luma_threshold, chroma_threshold, strength_q6; } mi_isp_chroma_denoise;
 int mi_isp_chroma_denoise_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,
                                     const mi_isp_chroma_denoise* settings_host, void* stream);
@@ -809,9 +811,11 @@ int mi_isp_luma_denoise_yuv420_batch(const uint8_t* const* src_host, uint8_t* co
  *    on it.
  *  - mi_isp_color_lut_rgb_batch_path: the same with the path given (for measurements and tests): 0 the dispatcher's choice,
  *    1 the table in LDS (n_points <= 33), 2 the table in global memory.
- * src_host / dst_host: n device pointers each, read on the host.  The operator is pointwise: src[i] == dst[i] is allowed,
- * any other overlap is not.  Host-side checks before any launch (error text names "color_lut"): the settings' ranges, the
- * path, n >= 0, H, W >= 0, NULL pointers.  n == 0 and H * W == 0 are successful no-ops.  No host synchronisation; the
+ * src_host / dst_host: n device pointers each, read on the host.  The operator is pointwise: src[i] == dst[i] exactly is
+ * allowed; otherwise no output (H * W * 3 bytes) may overlap an input - its own source at a shifted address or another
+ * image's - or another output of the call.  Host-side checks before any launch (error text names "color_lut"): the
+ * settings' ranges, the path, n >= 0, H, W >= 0, NULL pointers, overlapping images.  n == 0 and H * W == 0 are successful
+ * no-ops.  No host synchronisation; the
  * launches run on `stream`. */
 typedef struct { int32_t n_points, strength_q6; } mi_isp_color_lut;
 int mi_isp_color_lut_rgb_batch(const uint8_t* const* src_host, uint8_t* const* dst_host, int n, int H, int W,

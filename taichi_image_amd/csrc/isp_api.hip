@@ -1593,14 +1593,13 @@ struct U8Stage {
   const char* noun;
   bool one_image;                 // n == 0 is an error (else: nothing to do)
   bool even_width;                // the Y plane of the YUV form must have an even width as well as an even height
-  bool in_place;                  // src[i] == dst[i] is allowed
-  bool disjoint;                  // a written image must overlap no read image and no other written image
+  bool in_place;                  // src[i] == dst[i] exactly is allowed: the one exception to the overlap rule of u8_images
 };
-static const U8Stage kSharpen = {"sharpen", true, false, false, false},
-                     kLocalContrast = {"local_contrast", false, true, true, false},
-                     kChromaDenoise = {"chroma_denoise", false, true, false, false},
-                     kLumaDenoise = {"luma_denoise", false, true, false, true},
-                     kColorLut = {"color_lut", false, false, true, false};    // (RGB only: no evenness rule applies)
+static const U8Stage kSharpen = {"sharpen", true, false, false},
+                     kLocalContrast = {"local_contrast", false, true, true},
+                     kChromaDenoise = {"chroma_denoise", false, true, false},
+                     kLumaDenoise = {"luma_denoise", false, true, false},
+                     kColorLut = {"color_lut", false, false, true};    // (RGB only: no evenness rule applies)
 
 // one 256-thread block per 128 x 64 pixels: the launch's work-items per image must stay below 2^32
 static_assert(2 * cdn::TILE_CW == u8::TILE_W && 2 * cdn::TILE_CH == u8::TILE_H, "the chroma_denoise tile in pixels");
@@ -1610,6 +1609,7 @@ static bool u8_tiles_fit(int H, int W) {
 }
 
 static bool u8_nothing(int n, int H, int W) { return n == 0 || (size_t)H * (size_t)W == 0; }
+static size_t u8_bytes(bool rgb, int H, int W) { return rgb ? (size_t)H * W * 3 : (size_t)H * W * 3 / 2; }    // of one image
 
 // the count, the shape, the stage's size limit (fits) and the evenness of the YUV form
 static int u8_shape(int n, int H, int W, bool rgb, bool fits, const U8Stage& st, const char* who) {
@@ -1629,17 +1629,20 @@ static int u8_list(const uint8_t* const* src, uint8_t* const* dst, const U8Stage
   return 0;
 }
 
-// the n images' pointers; bytes: of one image
+// the n images' pointers; bytes: of one image.  Every block of a launch reads while others write, so for every stage a written
+// image overlaps no read image and no other written image of the call; a stage that may run in place takes dst[i] == src[i]
+// exactly, and nothing else (a shifted address, or another image's source, is read by blocks other than the one that writes it).
 static int u8_images(const uint8_t* const* src, uint8_t* const* dst, int n, size_t bytes, const U8Stage& st, const char* who) {
   for (int i = 0; i < n; ++i) {
     MI_REQUIRE(src[i] && dst[i], "%s: %s image %d has a null pointer", who, st.noun, i);
     MI_REQUIRE(st.in_place || src[i] != dst[i], "%s: %s image %d: the filter cannot run in place", who, st.noun, i);
   }
-  for (int i = 0; st.disjoint && i < n; ++i) {
+  for (int i = 0; i < n; ++i) {
     const uintptr_t d = (uintptr_t)dst[i];
     for (int j = 0; j < n; ++j) {
       const uintptr_t sj = (uintptr_t)src[j], dj = (uintptr_t)dst[j];
-      MI_REQUIRE(d + bytes <= sj || sj + bytes <= d, "%s: %s output %d overlaps input %d", who, st.noun, i, j);
+      MI_REQUIRE(d + bytes <= sj || sj + bytes <= d || (st.in_place && i == j && d == sj), "%s: %s output %d overlaps input %d",
+                 who, st.noun, i, j);
       MI_REQUIRE(i == j || d + bytes <= dj || dj + bytes <= d, "%s: %s outputs %d and %d overlap", who, st.noun, i, j);
     }
   }
@@ -1683,7 +1686,7 @@ static int sharpen_impl(const uint8_t* const* src, uint8_t* const* dst, int n, i
   if (int rc = u8_shape(n, H, W, rgb, u8_tiles_fit(H, W), kSharpen, who)) return rc;
   if (int rc = u8_list(src, dst, kSharpen, who)) return rc;
   if (u8_nothing(n, H, W)) return 0;
-  if (int rc = u8_images(src, dst, n, 0, kSharpen, who)) return rc;
+  if (int rc = u8_images(src, dst, n, u8_bytes(rgb, H, W), kSharpen, who)) return rc;
   shp::Args a = {};
   a.H = H; a.W = W;
   a.amount_q6 = s->amount_q6; a.threshold = s->threshold; a.overshoot = s->overshoot;
@@ -1730,7 +1733,7 @@ static int local_contrast_impl(const uint8_t* const* src, uint8_t* const* dst, i
   MI_REQUIRE(H <= lc::MAX_SIDE && W <= lc::MAX_SIDE, "%s: local_contrast image %dx%d larger than %d", who, H, W, lc::MAX_SIDE);
   if (int rc = u8_list(src, dst, kLocalContrast, who)) return rc;
   MI_REQUIRE(ws && mi_aligned(ws, 16), "%s: local_contrast workspace null or not 16-byte aligned", who);
-  if (int rc = u8_images(src, dst, n, 0, kLocalContrast, who)) return rc;
+  if (int rc = u8_images(src, dst, n, u8_bytes(rgb, H, W), kLocalContrast, who)) return rc;
   const size_t per_image = (size_t)s->tiles_y * s->tiles_x * 256;
   uint32_t* hist = static_cast<uint32_t*>(ws);
   uint8_t* lut = static_cast<uint8_t*>(ws) + lc::hist_bytes(n, s->tiles_y, s->tiles_x);
@@ -1769,7 +1772,7 @@ static int chroma_denoise_impl(const uint8_t* const* src, uint8_t* const* dst, i
   if (int rc = u8_shape(n, H, W, rgb, u8_tiles_fit(H, W), kChromaDenoise, who)) return rc;
   if (int rc = u8_list(src, dst, kChromaDenoise, who)) return rc;
   if (u8_nothing(n, H, W)) return 0;
-  if (int rc = u8_images(src, dst, n, 0, kChromaDenoise, who)) return rc;
+  if (int rc = u8_images(src, dst, n, u8_bytes(rgb, H, W), kChromaDenoise, who)) return rc;
   cdn::Args a = {};
   a.H = H; a.W = W;
   a.tl4 = 4 * s->luma_threshold; a.tc4 = 4 * s->chroma_threshold; a.strength_q6 = s->strength_q6;
@@ -1801,7 +1804,7 @@ static int luma_denoise_impl(const uint8_t* const* src, uint8_t* const* dst, int
   if (int rc = u8_shape(n, H, W, rgb, u8_tiles_fit(H, W), kLumaDenoise, who)) return rc;
   if (int rc = u8_list(src, dst, kLumaDenoise, who)) return rc;
   if (u8_nothing(n, H, W)) return 0;
-  if (int rc = u8_images(src, dst, n, rgb ? (size_t)H * W * 3 : (size_t)H * W * 3 / 2, kLumaDenoise, who)) return rc;
+  if (int rc = u8_images(src, dst, n, u8_bytes(rgb, H, W), kLumaDenoise, who)) return rc;
   ydn::Args a = {};
   a.H = H; a.W = W;
   a.t0 = s->threshold; a.t1 = s->threshold_bright; a.strength_q6 = s->strength_q6;
@@ -1834,7 +1837,7 @@ static int color_lut_impl(const uint8_t* const* src, uint8_t* const* dst, int n,
   MI_REQUIRE(table, "%s: null color_lut table", who);
   if (int rc = u8_list(src, dst, kColorLut, who)) return rc;
   if (u8_nothing(n, H, W)) return 0;
-  if (int rc = u8_images(src, dst, n, 0, kColorLut, who)) return rc;
+  if (int rc = u8_images(src, dst, n, u8_bytes(true, H, W), kColorLut, who)) return rc;
   int dev = 0;
   MI_HIP(hipGetDevice(&dev));
   clut::Args a = {};

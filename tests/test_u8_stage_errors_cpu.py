@@ -2,8 +2,9 @@
 luma noise reduction in their RGB and YUV 4:2:0 forms, the colour LUT with and without a forced path) rejects a bad argument,
 or returns for nothing to do, before any launch, with its return code and its full error text.  The addresses are made up
 (host buffers): nothing is launched or dereferenced.  Where the five stages differ is their behaviour and is pinned here:
-the least n, the evenness rule of the YUV form, in place, the overlap checks, the size limit and the order of the checks
-(the cases with two faults: the text says which check came first)."""
+the least n, the evenness rule of the YUV form, in place, the size limit and the order of the checks (the cases with two
+faults: the text says which check came first).  The overlap rule is one for all five: a written image overlaps no read image
+and no other written image of the call, dst[i] == src[i] exactly excepted for the stages that run in place."""
 import ctypes
 
 import pytest
@@ -94,11 +95,38 @@ def _tiled(noun, yuv, sides):
     return cases
 
 
+def _overlap(noun, yuv, in_place=False):
+    """the overlap checks, every stage's since they became one rule (they were luma noise reduction's alone): a written image
+    overlaps no read image and no other written image; in_place: the stage takes dst[i] == src[i] exactly, and only that"""
+    size = H * W * 3 // (2 if yuv else 1)                    # bytes of one image
+    pixel = 1 if yuv else 3
+    cases = [
+        ("output_in_input", dict(dst=[_A + size - 1]), f"{noun} output 0 overlaps input 0"),
+        ("input_in_output", dict(dst=[_A - size + 1 + 2048], src=[_A + 2048]), f"{noun} output 0 overlaps input 0"),
+        ("output_in_other_input", dict(n=2, src=[_A, _C], dst=[_B, _A + 8]), f"{noun} output 1 overlaps input 0"),
+        ("outputs_overlap", dict(n=2, src=[_A, _C], dst=[_B, _B + size - 1]), f"{noun} outputs 0 and 1 overlap"),
+        ("same_output_twice", dict(n=2, src=[_A, _C], dst=[_B, _B]), f"{noun} outputs 0 and 1 overlap"),
+        ("pointers_before_overlap", dict(n=2, src=[_A, 0], dst=[_A + 8, _B]), f"{noun} image 1 has a null pointer"),
+    ]
+    if in_place:
+        cases += [
+            # exact in place passes to the next check: image 1's fault speaks, not image 0's
+            ("in_place_then_overlap", dict(n=2, src=[_A, _C], dst=[_A, _C + pixel]), f"{noun} output 1 overlaps input 1"),
+            ("in_place_shifted_by_a_pixel", dict(dst=[_A + pixel]), f"{noun} output 0 overlaps input 0"),
+            ("in_place_shifted_back_by_a_row", dict(src=[_A + W * pixel], dst=[_A]), f"{noun} output 0 overlaps input 0"),
+            ("output_is_other_input", dict(n=2, src=[_A, _C], dst=[_B, _A]), f"{noun} output 1 overlaps input 0"),
+            ("in_place_output_is_other_input", dict(n=2, src=[_A, _A], dst=[_A, _B]), f"{noun} output 0 overlaps input 1"),
+            ("same_image_twice_in_place", dict(n=2, src=[_A, _A], dst=[_A, _A]), f"{noun} output 0 overlaps input 1"),
+            ("same_output_twice_one_in_place", dict(n=2, src=[_A, _C], dst=[_A, _A]), f"{noun} outputs 0 and 1 overlap"),
+        ]
+    return cases
+
+
 def _sharpen_cases(yuv):
     noun = "sharpen"
     few = lambda n: f"sharpen needs at least one image, got {n}"
     good = _native.Sharpen(64, 1, 0, -1)
-    return good, _common(noun, few) + _tiled(noun, yuv, sides=False) + [
+    return good, _common(noun, few) + _tiled(noun, yuv, sides=False) + _overlap(noun, yuv) + [
         ("no_image", dict(n=0), few(0)),
         ("no_image_null_list", dict(n=0, src=None), few(0)),
         ("radius", dict(s=_native.Sharpen(64, 3, 0, -1)), "sharpen radius 3 (1 or 2)"),
@@ -112,7 +140,7 @@ def _sharpen_cases(yuv):
 def _chroma_cases(yuv):
     noun = "chroma_denoise"
     good = _native.ChromaDenoise(2, 8, 12, 64)
-    return good, _common(noun, lambda n: f"{noun} with {n} images") + _tiled(noun, yuv, sides=True) + [
+    return good, _common(noun, lambda n: f"{noun} with {n} images") + _tiled(noun, yuv, sides=True) + _overlap(noun, yuv) + [
         ("no_image", dict(n=0, src=[0]), None),
         ("list_before_no_image", dict(n=0, src=None), f"null {noun} image list"),
         ("radius", dict(s=_native.ChromaDenoise(4, 8, 12, 64)), f"{noun} radius 4 (1, 2 or 3)"),
@@ -125,28 +153,20 @@ def _chroma_cases(yuv):
 def _luma_cases(yuv):
     noun = "luma_denoise"
     good = _native.LumaDenoise(2, 6, 6, 64)
-    size = H * W * 3 // (2 if yuv else 1)                    # bytes of one image
-    return good, _common(noun, lambda n: f"{noun} with {n} images") + _tiled(noun, yuv, sides=True) + [
+    return good, _common(noun, lambda n: f"{noun} with {n} images") + _tiled(noun, yuv, sides=True) + _overlap(noun, yuv) + [
         ("no_image", dict(n=0, src=[0]), None),
         ("list_before_no_image", dict(n=0, src=None), f"null {noun} image list"),
         ("radius", dict(s=_native.LumaDenoise(0, 6, 6, 64)), f"{noun} radius 0 (1, 2 or 3)"),
         ("threshold", dict(s=_native.LumaDenoise(2, 256, 6, 64)), f"{noun} threshold 256 outside 0 .. 255"),
         ("threshold_bright", dict(s=_native.LumaDenoise(2, 6, -1, 64)), f"{noun} threshold_bright -1 outside 0 .. 255"),
         ("strength", dict(s=_native.LumaDenoise(2, 6, 6, -1)), f"{noun} strength_q6 -1 outside 0 .. 64"),
-        # the overlap checks that only this stage has
-        ("output_in_input", dict(dst=[_A + size - 1]), f"{noun} output 0 overlaps input 0"),
-        ("input_in_output", dict(dst=[_A - size + 1 + 2048], src=[_A + 2048]), f"{noun} output 0 overlaps input 0"),
-        ("output_in_other_input", dict(n=2, src=[_A, _C], dst=[_B, _A + 8]), f"{noun} output 1 overlaps input 0"),
-        ("outputs_overlap", dict(n=2, src=[_A, _C], dst=[_B, _B + size - 1]), f"{noun} outputs 0 and 1 overlap"),
-        ("same_output_twice", dict(n=2, src=[_A, _C], dst=[_B, _B]), f"{noun} outputs 0 and 1 overlap"),
-        ("pointers_before_overlap", dict(n=2, src=[_A, 0], dst=[_A + 8, _B]), f"{noun} image 1 has a null pointer"),
     ]
 
 
 def _local_contrast_cases(yuv):
     noun = "local_contrast"
     good = _native.LocalContrast(2, 2, 512, 64)
-    cases = _common(noun, lambda n: f"{noun} with {n} images") + [
+    cases = _common(noun, lambda n: f"{noun} with {n} images") + _overlap(noun, yuv, in_place=True) + [
         ("tiles", dict(s=_native.LocalContrast(17, 2, 512, 64)), f"{noun} tiles 17 x 2 outside 1 .. 16"),
         ("clip", dict(s=_native.LocalContrast(2, 2, 255, 64)), f"{noun} clip_q8 255 outside 256 .. 16384 (0: no clip)"),
         ("strength", dict(s=_native.LocalContrast(2, 2, 512, 65)), f"{noun} strength_q6 65 outside 0 .. 64"),
@@ -183,7 +203,7 @@ def _local_contrast_cases(yuv):
 def _color_lut_cases(forced):
     noun = "color_lut"
     good = _native.ColorLut(17, 64)
-    cases = _common(noun, lambda n: f"{noun} with {n} images") + [
+    cases = _common(noun, lambda n: f"{noun} with {n} images") + _overlap(noun, False, in_place=True) + [
         ("n_points", dict(s=_native.ColorLut(66, 64)), f"{noun} n_points 66 outside 2 .. 65"),
         ("strength", dict(s=_native.ColorLut(17, 65)), f"{noun} strength_q6 65 outside 0 .. 64"),
         ("too_many_pixels", dict(H=1 << 16, W=1 << 15), f"{noun} image {1 << 16}x{1 << 15} too large"),
@@ -249,8 +269,14 @@ def test_u8_batch_entry_checks_on_the_host(who, case):
 def test_every_entry_point_has_its_cases():
     assert len(ENTRIES) == 10
     n = {who: len(_table(who)) for who in ENTRIES}
-    # the YUV forms add the evenness cases; the forced path adds the path cases
-    assert n == {"sharpen_rgb_batch": 25, "sharpen_yuv420_batch": 28, "local_contrast_rgb_batch": 26,
-                 "local_contrast_yuv420_batch": 29, "chroma_denoise_rgb_batch": 25, "chroma_denoise_yuv420_batch": 28,
-                 "luma_denoise_rgb_batch": 31, "luma_denoise_yuv420_batch": 34, "color_lut_rgb_batch": 21,
-                 "color_lut_rgb_batch_path": 26}
+    # the YUV forms add the evenness cases; the forced path adds the path cases; every stage has the six overlap cases and
+    # the stages that run in place seven more
+    assert n == {"sharpen_rgb_batch": 31, "sharpen_yuv420_batch": 34, "local_contrast_rgb_batch": 39,
+                 "local_contrast_yuv420_batch": 42, "chroma_denoise_rgb_batch": 31, "chroma_denoise_yuv420_batch": 34,
+                 "luma_denoise_rgb_batch": 31, "luma_denoise_yuv420_batch": 34, "color_lut_rgb_batch": 34,
+                 "color_lut_rgb_batch_path": 39}
+    for who in ENTRIES:
+        names = set(_table(who))
+        assert {"output_in_input", "input_in_output", "output_in_other_input", "outputs_overlap", "same_output_twice",
+                "pointers_before_overlap"} <= names, who
+        assert ("in_place_shifted_by_a_pixel" in names) == ("in_place_allowed" in names), who
