@@ -473,6 +473,43 @@ int mi_isp_dynamic_defects_raw_batch(const void* const* src_host, void* const* c
                                      uint32_t* const* flags_host);
 int mi_isp_dynamic_defects_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype,
                                const mi_isp_dynamic_defects* dynamic_host, void* stream, uint32_t* flags_dev);
+/* ---- green equalisation ("Green equalisation") ----------------------------------------------------------------
+ * Correction of the imbalance between the two green sites of a Bayer quad (Gr beside red, Gb beside blue).  x(p) is the
+ * f32 value a loader computes before shading and the cast.  p = (r, c) is a green site iff ((r + c) & 1) == gp, gp = 1
+ * for MI_RGGB and MI_BGGR and 0 for MI_GRBG and MI_GBRG (`pattern`: the demosaic pattern).  The taps of a green p, in
+ * this order:
+ *   radius 1: group O (the other phase) (r-1,c-1) (r-1,c+1) (r+1,c-1) (r+1,c+1)
+ *             group S (the own phase)   (r,c) (r-2,c) (r,c-2) (r,c+2) (r+2,c)
+ *   radius 2: group O (r+dy, c+dx) for dy in (-3,-1,1,3), for dx in (-3,-1,1,3), row-major: 16 taps
+ *             group S (r,c), then (r+dy, c+dx) for dy in (-2,0,2), for dx in (-2,0,2), without (0,0), row-major: 9 taps
+ * A tap is kept when it is inside the frame, not listed in the frame's defect mask and its x is finite.  For each group:
+ * the f32 sum of the kept taps in the listed order, starting from the first kept tap; their count n; their maximum and
+ * their minimum.  Every operation is one f32 rounding, in the order written, never contracted; the divisions are IEEE:
+ *   O = sumO / f32(nO)        S = sumS / f32(nS)        d = O - S
+ *   lim = threshold + slope * max(O, S)                   e = edge * lim
+ *   apply  iff  nO >= 1  and  |d| <= lim  and  maxO - minO <= e  and  maxS - minS <= e     (a NaN makes a comparison false)
+ *   y = x(p) + (f32(strength) * 0.5f) * d      if apply
+ *   y = x(p), the same bits                    otherwise
+ *   cfa = cast_work(y * g(p))      (g the lens shading gain of shading_host, 1 for NULL)
+ * A site that is not green, a listed defect (the fix-up replaces it afterwards) and a pixel whose x(p) is not finite keep
+ * x(p), the same bits.
+ * Source kinds, levels, grids, defect maps and outputs as mi_isp_highlights_raw(_batch), out_f32_plain included (the
+ * output is the H x W f32 y itself; shading_host must be NULL).
+ *  - mi_isp_green_equalize_cfa: a normalised H x W CFA of dtype MI_F16 / MI_F32 (no levels, gain or mask), out of the same dtype.
+ * Host-side checks before any launch (error text names "green equalize"): threshold, slope and edge finite >= 0, strength
+ * in [0, 1], radius 1 or 2, pattern, shapes, dtypes, kinds, levels, grids, NULL pointers.  n == 0 and H * W == 0 are
+ * successful no-ops. */
+typedef struct { float threshold, slope, strength; int32_t radius; float edge; } mi_isp_green_equalize;
+int mi_isp_green_equalize_raw(const void* src_dev, void* cfa_dev, int H, int W, int src_kind, int ids_format, int work_dtype,
+                              int pattern, const mi_isp_levels* levels_host, const mi_isp_shading* shading_host,
+                              const mi_isp_defects* defects_host, const mi_isp_green_equalize* green_host,
+                              int out_f32_plain, void* stream);
+int mi_isp_green_equalize_raw_batch(const void* const* src_host, void* const* cfa_host, int n, int H, int W, int src_kind,
+                                    int ids_format, int work_dtype, int pattern, const mi_isp_levels* levels_host,
+                                    const mi_isp_shading* shading_host, const mi_isp_defects* const* defects_host,
+                                    const mi_isp_green_equalize* green_host, int out_f32_plain, void* stream);
+int mi_isp_green_equalize_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, int pattern,
+                              const mi_isp_green_equalize* green_host, void* stream);
 /* ---- directional demosaic ("Directional demosaic") --------------------------------------------------------
  * A direction-adaptive alternative to mi_isp_demosaic's 13-tap filter, in f32 with one rounding per operation, in the
  * order written, never contracted: the output is the contract's bit for bit.  X(r, c) is the f32 value of the H x W CFA

@@ -58,6 +58,12 @@ class DynamicDefects(ctypes.Structure):
     _fields_ = [("threshold", c_float), ("slope", c_float), ("tolerate", c_int32), ("hot", c_int32), ("dead", c_int32)]
 
 
+class GreenEqualize(ctypes.Structure):
+    """mi_isp_green_equalize: the threshold of the believed imbalance and its slope over the signal, the strength of the
+    correction, the radius of the local means (1 or 2) and the edge gate's factor."""
+    _fields_ = [("threshold", c_float), ("slope", c_float), ("strength", c_float), ("radius", c_int32), ("edge", c_float)]
+
+
 class Highlights(ctypes.Structure):
     """mi_isp_highlights: the mode (0 rebuild, 1 clip), the clip level, the balance gains of R, G, B and, when not NULL,
     3 f32 on the device that override them."""
@@ -229,6 +235,12 @@ SIGNATURES = {
                                                  POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(DynamicDefects),
                                                  c_int, _P, POINTER(_P)]),
     "mi_isp_dynamic_defects_cfa": (c_int, [_P, _P, c_int, c_int, c_int, POINTER(DynamicDefects), _P, _P]),
+    "mi_isp_green_equalize_raw": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Shading),
+                                          POINTER(Defects), POINTER(GreenEqualize), c_int, _P]),
+    "mi_isp_green_equalize_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(GreenEqualize),
+                                                c_int, _P]),
+    "mi_isp_green_equalize_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(GreenEqualize), _P]),
     "mi_isp_demosaic_directional_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "mi_isp_demosaic_directional_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
                                                       c_int, POINTER(Levels), POINTER(Shading), POINTER(c_float), _P]),

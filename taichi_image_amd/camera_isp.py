@@ -24,6 +24,7 @@ from . import defects as _defects
 from . import denoise as _dn
 from . import highlights as _hl
 from . import dynamic_defects as _ddp
+from . import green_equalize as _geq
 from . import chromatic as _ca
 from . import temporal as _tn
 from . import exposure_merge as _em
@@ -44,6 +45,7 @@ _OPTIONAL_STAGES = (
     ("raw_denoise", "_raw_denoise", _dn.check_raw_denoise),
     ("highlights", "_highlights", _hl.check_highlights),
     ("dynamic_defects", "_dynamic_defects", _ddp.check_dynamic_defects),
+    ("green_equalize", "_green_equalize", _geq.check_green_equalize),
     ("chromatic_aberration", "_chromatic", _ca.check_chromatic_aberration),
     ("temporal_denoise", "_temporal", _tn.check_temporal_denoise),
     ("exposure_merge", "_merge", _em.check_exposure_merge),
@@ -322,7 +324,8 @@ def camera_isp(name: str, dtype=types.f32):
                      luma_denoise=None,
                      demosaic=None,
                      resample=None,
-                     dynamic_defects=None):
+                     dynamic_defects=None,
+                     green_equalize=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -341,6 +344,7 @@ def camera_isp(name: str, dtype=types.f32):
             raw_denoise = _dn.check_raw_denoise(raw_denoise)
             highlights = _hl.check_highlights(highlights)
             dynamic_defects = _ddp.check_dynamic_defects(dynamic_defects)
+            green_equalize = _geq.check_green_equalize(green_equalize)
             chromatic_aberration = _ca.check_chromatic_aberration(chromatic_aberration)
             temporal_denoise = _tn.check_temporal_denoise(temporal_denoise)
             exposure_merge = _em.check_exposure_merge(exposure_merge)
@@ -403,6 +407,9 @@ def camera_isp(name: str, dtype=types.f32):
             # dynamic defects (an extension): the DynamicDefects the loaders detect and replace defective raw pixels with,
             # without a map, or None (the loaders run exactly as without it).  DESIGN.md 3, "Dynamic defects".
             self._dynamic_defects = dynamic_defects
+            # green equalisation (an extension): the GreenEqualize the loaders balance the two green phases with, or None
+            # (the loaders run exactly as without it).  DESIGN.md 3, "Green equalisation".
+            self._green_equalize = green_equalize
             # chromatic aberration (an extension): the ChromaticAberration the loaders correct on the CFA, or None (the
             # loaders run exactly as without it).  DESIGN.md 3, "Chromatic aberration".
             self._chromatic = chromatic_aberration
@@ -457,7 +464,8 @@ def camera_isp(name: str, dtype=types.f32):
                 black_level=None, white_level: Optional[int] = None, lens_shading=None, auto_white_balance=None,
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
                 highlights=None, chromatic_aberration=None, temporal_denoise=None, exposure_merge=None,
-                local_tonemap=None, luma_denoise=None, demosaic=None, resample=None, dynamic_defects=None):
+                local_tonemap=None, luma_denoise=None, demosaic=None, resample=None, dynamic_defects=None,
+                green_equalize=None):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -481,7 +489,8 @@ def camera_isp(name: str, dtype=types.f32):
             luma_denoise (the extension): None leaves it, False turns it off, a LumaDenoise replaces it.
             demosaic (the extension): None leaves it, False turns it off, a Demosaic replaces it.
             resample (the extension): None leaves it, False turns it off, a Resample replaces it.
-            dynamic_defects (the extension): None leaves it, False turns it off, a DynamicDefects replaces it."""
+            dynamic_defects (the extension): None leaves it, False turns it off, a DynamicDefects replaces it.
+            green_equalize (the extension): None leaves it, False turns it off, a GreenEqualize replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -495,7 +504,7 @@ def camera_isp(name: str, dtype=types.f32):
                          temporal_denoise=temporal_denoise, exposure_merge=exposure_merge, local_tonemap=local_tonemap,
                          sharpen=sharpen, local_contrast=local_contrast, chroma_denoise=chroma_denoise,
                          luma_denoise=luma_denoise, color_lut=color_lut, demosaic=demosaic, resample=resample,
-                         dynamic_defects=dynamic_defects)
+                         dynamic_defects=dynamic_defects, green_equalize=green_equalize)
             replaced = {name: check(given[name]) for name, _, check in _OPTIONAL_STAGES
                         if given[name] is not None and given[name] is not False}
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
@@ -635,7 +644,8 @@ def camera_isp(name: str, dtype=types.f32):
         def _raw_stage_on(self):
             """True when a loader of single frames goes through _raw_chain."""
             return (self._highlights is not None or self._chromatic is not None or self._temporal is not None
-                    or self._raw_denoise is not None or self._dynamic_defects is not None)
+                    or self._raw_denoise is not None or self._dynamic_defects is not None
+                    or self._green_equalize is not None)
 
         @property
         def raw_denoise(self) -> Optional[_dn.RawDenoise]:
@@ -651,6 +661,11 @@ def camera_isp(name: str, dtype=types.f32):
         def dynamic_defects(self) -> Optional[_ddp.DynamicDefects]:
             """The DynamicDefects the loaders apply, or None."""
             return self._dynamic_defects
+
+        @property
+        def green_equalize(self) -> Optional[_geq.GreenEqualize]:
+            """The GreenEqualize the loaders apply, or None."""
+            return self._green_equalize
 
         def _highlights_arg(self):
             """The mi_isp_highlights of a load: the balance gains are the AWB gains on the device with AWB on, else
@@ -696,14 +711,15 @@ def camera_isp(name: str, dtype=types.f32):
         def _raw_chain(self, srcs, h, w, kind, ids_format, lv, maps, hists=None, brackets=None):
             """The raw chain, the one route of every loader with a raw stage on: the raw stages that are on, in the order
             exposure merge, dynamic defects, highlight reconstruction, chromatic aberration, temporal noise reduction, raw
-            noise reduction, one launch each for the raw frames srcs (one shape, source kind `kind`; with exposure merge on brackets holds
-            the E frames of each, and srcs their first), then the defect fix-up of each frame with a map (maps: one
-            DefectMap or None per frame).  A stage that is not the last writes the plain f32 y, which the next takes as an
+            noise reduction, green equalisation, one launch each for the raw frames srcs (one shape, source kind `kind`;
+            with exposure merge on brackets holds the E frames of each, and srcs their first), then the defect fix-up of
+            each frame with a map (maps: one DefectMap or None per frame).  A stage that is not the last writes the plain f32 y, which the next takes as an
             f32 source without levels; the last applies the grid and the cast; all read the same masks.  The temporal
             stage reads and writes the planes of hists (one checked TemporalHistory per frame), which swap once its launch
-            was issued; when it is not the last, its new history planes are the y the next stage reads.  DESIGN.md 3, "Raw
-            noise reduction", "Highlight reconstruction", "Exposure merge", "Chromatic aberration", "Temporal noise
-            reduction" and "Dynamic defects"."""
+            was issued; when it is not the last, its new history planes are the y the next stage reads.  Raw noise
+            reduction has no plain output of its own: in front of green equalisation it writes an f32 CFA without a grid,
+            which is its y.  DESIGN.md 3, "Raw noise reduction", "Highlight reconstruction", "Exposure merge", "Chromatic
+            aberration", "Temporal noise reduction", "Dynamic defects" and "Green equalisation"."""
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             n = len(srcs)
@@ -734,7 +750,11 @@ def camera_isp(name: str, dtype=types.f32):
             if self._raw_denoise is not None:
                 dn_arg = self._raw_denoise._arg()
                 stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_denoise_raw_batch(
-                    i, o, n, h, w, k, f, dtype.code, l, s, p_maps, dn_arg, stream))
+                    i, o, n, h, w, k, f, types.f32.code if plain else dtype.code, l, s, p_maps, dn_arg, stream))
+            if self._green_equalize is not None:         # (the last stage: directly in front of the demosaic)
+                ge_arg = self._green_equalize._arg()
+                stages.append(lambda i, o, k, f, l, s, plain: L.mi_isp_green_equalize_raw_batch(
+                    i, o, n, h, w, k, f, dtype.code, pattern, l, s, p_maps, ge_arg, plain, stream))
             cfas = [torch.empty((h, w), dtype=torch_dtype, device=self.device) for _ in srcs]
             cur, cur_kind, cur_ids, cur_lv = srcs, kind, ids, lv
             for k, stage in enumerate(stages):
@@ -1521,6 +1541,7 @@ def camera_isp(name: str, dtype=types.f32):
                      and self._raw_denoise is None            # (raw noise reduction: the two calls below)
                      and self._highlights is None             # (highlight reconstruction: the two calls below)
                      and self._dynamic_defects is None        # (dynamic defects: the two calls below)
+                     and self._green_equalize is None         # (green equalisation: the two calls below)
                      and self._chromatic is None              # (chromatic aberration: the two calls below)
                      and self._temporal is None               # (temporal noise reduction: the two calls below)
                      and self._ltm is None                    # (local tone mapping: the two calls below)

@@ -17,6 +17,7 @@
 #include "isp_denoise.h"
 #include "isp_highlights.h"
 #include "isp_dynamic_defects.h"
+#include "isp_green_equalize.h"
 #include "isp_demosaic_dir.h"
 #include "isp_chromatic.h"
 #include "isp_temporal.h"
@@ -973,6 +974,92 @@ extern "C" int mi_isp_dynamic_defects_cfa(const void* in, void* out, int H, int 
   a.f[0] = {in, out, nullptr, flags};
   return ddp::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
                      (hipStream_t)stream);
+}
+
+// ---- green equalisation (isp_green_equalize.h; DESIGN.md 3, "Green equalisation") ------------------------------------
+static const RawStage kGreenEqualize = {"green equalize", "green equalize: ", "frame"};
+
+// the operator's settings and the demosaic pattern, checked on the host; fills the operator members of a
+static int green_equalize_settings(geq::Args& a, const mi_isp_green_equalize* g, int pattern, const char* who) {
+  static const int colours[4][4] = {{0, 1, 1, 2}, {1, 0, 2, 1}, {1, 2, 0, 1}, {2, 1, 1, 0}};   // RGGB GRBG GBRG BGGR
+  MI_REQUIRE(g, "%s: null green equalize settings", who);
+  MI_REQUIRE(std::isfinite(g->threshold) && g->threshold >= 0.f, "%s: green equalize threshold %g must be finite and >= 0",
+             who, (double)g->threshold);
+  MI_REQUIRE(std::isfinite(g->slope) && g->slope >= 0.f, "%s: green equalize slope %g must be finite and >= 0", who,
+             (double)g->slope);
+  MI_REQUIRE(g->strength >= 0.f && g->strength <= 1.f, "%s: green equalize strength %g must be in [0, 1]", who,
+             (double)g->strength);
+  MI_REQUIRE(g->radius == 1 || g->radius == 2, "%s: green equalize radius %d (1 or 2)", who, (int)g->radius);
+  MI_REQUIRE(std::isfinite(g->edge) && g->edge >= 0.f, "%s: green equalize edge %g must be finite and >= 0", who,
+             (double)g->edge);
+  MI_REQUIRE(pattern >= MI_RGGB && pattern <= MI_BGGR, "%s: bad green equalize pattern %d", who, pattern);
+  a.t = g->threshold;
+  a.s = g->slope;
+  a.edge = g->edge;
+  a.hs = g->strength * 0.5f;
+  a.gp = colours[pattern][0] == 1 ? 0 : 1;            // (r, c) is green iff ((r + c) & 1) == gp: site (0, 0) tells
+  return 0;
+}
+
+// n raw frames of one geometry: every frame's pointers (and defect mask) in the kernel arguments, 32 per launch
+static int green_equalize_raw_impl(const void* const* src, void* const* cfa, int n, int H, int W, int kind, int ids_format,
+                                   int work_dtype, int pattern, const mi_isp_levels* levels, const mi_isp_shading* shading,
+                                   const mi_isp_defects* const* defects, const mi_isp_green_equalize* g, int plain,
+                                   void* stream, const char* who) {
+  geq::Args a = {};
+  if (int rc = green_equalize_settings(a, g, pattern, who)) return rc;
+  if (int rc = raw_geometry(H, W, work_dtype, kGreenEqualize, who)) return rc;
+  if (int rc = raw_kind(kind, kGreenEqualize, who)) return rc;
+  MI_REQUIRE(n >= 0, "%s: green equalize with %d frames", who, n);
+  if (n == 0 || H == 0 || W == 0) return 0;
+  MI_REQUIRE(src && cfa, "%s: green equalize: null frame list", who);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && cfa[i], "%s: green equalize: frame %d has a null pointer", who, i);
+    MI_REQUIRE(src[i] != cfa[i], "%s: green equalize: frame %d: the CFA must not overwrite its source", who, i);
+  }
+  if (int rc = raw_source_rules(H, W, kind, ids_format, shading, plain, kGreenEqualize, who)) return rc;
+  int src_kind;
+  if (int rc = raw_source_setup(a, src_kind, H, W, kind, ids_format, levels, shading, defects, n, kGreenEqualize, who))
+    return rc;
+  const int out = plain ? hl::OUT_PLAIN : (work_dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32);
+  for (int i0 = 0; i0 < n; i0 += geq::MAX_FRAMES) {
+    a.n_frames = n - i0 < geq::MAX_FRAMES ? n - i0 : geq::MAX_FRAMES;
+    for (int i = 0; i < a.n_frames; ++i) a.f[i] = {src[i0 + i], cfa[i0 + i], mask_of(defects, i0 + i)};
+    if (int rc = geq::launch(a, src_kind, out, g->radius, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mi_isp_green_equalize_raw(const void* src, void* cfa, int H, int W, int kind, int ids_format,
+                                         int work_dtype, int pattern, const mi_isp_levels* levels,
+                                         const mi_isp_shading* shading, const mi_isp_defects* defects,
+                                         const mi_isp_green_equalize* green, int out_f32_plain, void* stream) {
+  return green_equalize_raw_impl(&src, &cfa, 1, H, W, kind, ids_format, work_dtype, pattern, levels, shading, &defects,
+                                 green, out_f32_plain, stream, "green_equalize_raw");
+}
+
+extern "C" int mi_isp_green_equalize_raw_batch(const void* const* src, void* const* cfa, int n, int H, int W, int kind,
+                                               int ids_format, int work_dtype, int pattern, const mi_isp_levels* levels,
+                                               const mi_isp_shading* shading, const mi_isp_defects* const* defects,
+                                               const mi_isp_green_equalize* green, int out_f32_plain, void* stream) {
+  return green_equalize_raw_impl(src, cfa, n, H, W, kind, ids_format, work_dtype, pattern, levels, shading, defects, green,
+                                 out_f32_plain, stream, "green_equalize_raw_batch");
+}
+
+extern "C" int mi_isp_green_equalize_cfa(const void* in, void* out, int H, int W, int dtype, int pattern,
+                                         const mi_isp_green_equalize* green, void* stream) {
+  const char* who = "green_equalize_cfa";
+  geq::Args a = {};
+  if (int rc = green_equalize_settings(a, green, pattern, who)) return rc;
+  if (int rc = raw_geometry(H, W, dtype, kGreenEqualize, who)) return rc;
+  if (H == 0 || W == 0) return 0;
+  MI_REQUIRE(in && out, "%s: green equalize: null pointer", who);
+  MI_REQUIRE(in != out, "%s: green equalize: the output must not overwrite the input", who);
+  a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
+  a.n_frames = 1;
+  a.f[0] = {in, out, nullptr};
+  return geq::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
+                     green->radius, (hipStream_t)stream);
 }
 
 // ---- directional demosaic (isp_demosaic_dir.h; DESIGN.md 3, "Directional demosaic") ---------------------------------

@@ -210,6 +210,16 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--dynamic-defects-threshold", dest="dynamic_defects_threshold", type=float, metavar="T", default=None)
     tone.add_argument("--dynamic-defects-slope", dest="dynamic_defects_slope", type=float, metavar="S", default=None)
     tone.add_argument("--dynamic-defects-tolerate", dest="dynamic_defects_tolerate", type=int, metavar="K", default=None)
+    # green equalisation (an extension): the imbalance between the two green sites of a Bayer quad removed in front of the
+    # demosaic; T the believed imbalance in units of the white level (default 1/256), S its slope over the signal (default
+    # 1/16), A the strength in [0, 1] (default 1), R in {1, 2} the radius of the local means (default 1), E the edge
+    # gate's factor (default 4)
+    tone.add_argument("--green-equalize", dest="green_equalize", action="store_true")
+    tone.add_argument("--green-equalize-threshold", dest="green_equalize_threshold", type=float, metavar="T", default=None)
+    tone.add_argument("--green-equalize-slope", dest="green_equalize_slope", type=float, metavar="S", default=None)
+    tone.add_argument("--green-equalize-strength", dest="green_equalize_strength", type=float, metavar="A", default=None)
+    tone.add_argument("--green-equalize-radius", dest="green_equalize_radius", type=int, metavar="R", default=None)
+    tone.add_argument("--green-equalize-edge", dest="green_equalize_edge", type=float, metavar="E", default=None)
     # the demosaic (an extension): "directional" interpolates along edges instead of across them; "malvar" (the default)
     # is the 13-tap filter
     tone.add_argument("--demosaic", dest="demosaic", choices=("malvar", "directional"), default=None)
@@ -278,6 +288,7 @@ def main(argv=None) -> int:
     from ..denoise import RawDenoise
     from ..highlights import Highlights
     from ..dynamic_defects import DynamicDefects
+    from ..green_equalize import GreenEqualize
     from ..demosaic import Demosaic
     from ..resample import Resample
     from ..chromatic import ChromaticAberration
@@ -317,6 +328,13 @@ def main(argv=None) -> int:
     elif any(v is not None for v in dyn.values()):
         raise ValueError("--dynamic-defects-threshold, --dynamic-defects-slope and --dynamic-defects-tolerate need "
                          "--dynamic-defects")
+    green = None
+    geq = dict(threshold=args.green_equalize_threshold, slope=args.green_equalize_slope,
+               strength=args.green_equalize_strength, radius=args.green_equalize_radius, edge=args.green_equalize_edge)
+    if args.green_equalize:                                         # (also before any frame is read)
+        green = GreenEqualize(**{k: v for k, v in geq.items() if v is not None})
+    elif any(v is not None for v in geq.values()):
+        raise ValueError("--green-equalize-threshold, -slope, -strength, -radius and -edge need --green-equalize")
     chromatic = None
     if args.chromatic_aberration is not None:                       # (also before any frame is read)
         k = args.chromatic_aberration
@@ -385,7 +403,7 @@ def main(argv=None) -> int:
                               local_tonemap=local_tonemap, luma_denoise=luma_denoise,
                               demosaic=None if args.demosaic is None else Demosaic(args.demosaic),
                               resample=None if args.resample is None else Resample(args.resample),
-                              dynamic_defects=dynamic)
+                              dynamic_defects=dynamic, green_equalize=green)
     # temporal noise reduction: the state of each camera folder, for the whole scan
     histories = [TemporalHistory() if temporal is not None else None for _ in index.cameras]
     row_bytes = args.width * 3 // 2
