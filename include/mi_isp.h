@@ -510,6 +510,51 @@ int mi_isp_green_equalize_raw_batch(const void* const* src_host, void* const* cf
                                     const mi_isp_green_equalize* green_host, int out_f32_plain, void* stream);
 int mi_isp_green_equalize_cfa(const void* in_dev, void* out_dev, int H, int W, int dtype, int pattern,
                               const mi_isp_green_equalize* green_host, void* stream);
+/* ---- frame statistics ("Frame statistics") ---------------------------------------------------------------
+ * Exposure and focus measurements of raw frames: a read-only side output, exact in integers (the result depends neither
+ * on the launch geometry nor on the order of the atomics).  x(p) is the f32 value a loader computes before shading, AWB
+ * gain and the cast (levels applied where the source has them); H and W are even.  Pixel p = (r, c) is valid when it is
+ * inside the frame, not listed in the frame's defect mask and x(p) > -inf (a NaN and -inf drop out).  For a valid pixel:
+ *   v = i32(rint(min(max(x, 0), 1) * 65536))   (one exact f32 product, ties to even)      site s = (r & 1) * 2 + (c & 1)
+ *   clipped iff x >= f32(clip)                  dark iff x <= f32(dark)
+ *   zone (i, j) = (((r >> 1) * zones_h) / (H / 2), ((c >> 1) * zones_w) / (W / 2))   (integer divisions; a quad is never
+ *   split; zones_h <= H / 2 and zones_w <= W / 2, so no zone is empty)
+ * One frame's result is one contiguous buffer of mi_isp_statistics_words() int64, which the entry points clear on the
+ * stream themselves (what it held before does not matter):
+ *   Z[zones_h][zones_w][4][4]   per zone and site, over its valid pixels: their count, the sum of v, the clipped, the dark
+ *   F[zones_h][zones_w][2]      per zone: the sum of L * L and the count, over the valid green pixels p (((r + c) & 1) == gp,
+ *                               gp = 1 for MI_RGGB and MI_BGGR, 0 for MI_GRBG and MI_GBRG; `pattern`: the demosaic pattern)
+ *                               whose four taps (r - 2, c), (r + 2, c), (r, c - 2), (r, c + 2) are valid, p and the taps
+ *                               all with x < f32(clip) (a clipped plateau's rim is not detail):  L = 4 v(p) - sum of v(taps)
+ *   Hist[4][256]                per site: every valid pixel adds 1 to bin min(v >> 8, 255)
+ * |L| <= 2^18, so the sum of L * L stays inside an int64 for H * W <= 2^26; larger frames are refused.
+ * Source kinds, ids_format, levels and defect maps as mi_isp_highlights_raw(_batch); there is no shading argument: the
+ * statistics describe the sensor.
+ *  - mi_isp_statistics_cfa: a normalised H x W CFA of dtype MI_F16 / MI_F32 (no levels), with an optional defect map.
+ *  - mi_isp_statistics_words (host only): the int64 count per frame, zones_h * zones_w * 18 + 1024; -1 for bad zones.
+ *  - mi_isp_statistics_geometry (host only): {tile rows, tile columns, zone cells of a block's LDS table, the largest
+ *    number of consecutive tiles a block takes}.  mi_isp_statistics_strip (host only): the consecutive tiles a block takes
+ *    in ONE launch of n frames, 1 <= n <= 32 (a call of more frames is launches of 32 and one of the rest, each with its
+ *    own strip); -1 on an error.  A block whose tiles span more zone cells than the table holds adds to global memory
+ *    directly; mi_isp_statistics_direct_blocks (host only) counts such blocks per frame for one launch of n frames, 0 <= n
+ *    <= 32 (-1 on an error).
+ * Host-side checks before any launch (error text names "statistics"): zones 1 .. 32 each and no larger than the quad
+ * grid, clip finite > 0, dark finite >= 0 and < clip, pattern, odd H or W, H * W > 2^26, more than 65535 tile rows, kinds, levels, NULL pointers, an
+ * output that is not aligned to 8 bytes.  n == 0 and H * W == 0 are successful no-ops. */
+typedef struct { int32_t zones_h, zones_w; float clip, dark; } mi_isp_statistics;
+int64_t mi_isp_statistics_words(const mi_isp_statistics* statistics_host);
+int mi_isp_statistics_geometry(int32_t out[4]);
+int mi_isp_statistics_strip(int n, int H, int W);
+int mi_isp_statistics_direct_blocks(int n, int H, int W, const mi_isp_statistics* statistics_host);
+int mi_isp_statistics_raw(const void* src_dev, int64_t* out_dev, int H, int W, int src_kind, int ids_format, int pattern,
+                          const mi_isp_levels* levels_host, const mi_isp_defects* defects_host,
+                          const mi_isp_statistics* statistics_host, void* stream);
+int mi_isp_statistics_raw_batch(const void* const* src_host, int64_t* const* out_host, int n, int H, int W, int src_kind,
+                                int ids_format, int pattern, const mi_isp_levels* levels_host,
+                                const mi_isp_defects* const* defects_host, const mi_isp_statistics* statistics_host,
+                                void* stream);
+int mi_isp_statistics_cfa(const void* cfa_dev, int64_t* out_dev, int H, int W, int dtype, int pattern,
+                          const mi_isp_defects* defects_host, const mi_isp_statistics* statistics_host, void* stream);
 /* ---- directional demosaic ("Directional demosaic") --------------------------------------------------------
  * A direction-adaptive alternative to mi_isp_demosaic's 13-tap filter, in f32 with one rounding per operation, in the
  * order written, never contracted: the output is the contract's bit for bit.  X(r, c) is the f32 value of the H x W CFA

@@ -64,6 +64,11 @@ class GreenEqualize(ctypes.Structure):
     _fields_ = [("threshold", c_float), ("slope", c_float), ("strength", c_float), ("radius", c_int32), ("edge", c_float)]
 
 
+class Statistics(ctypes.Structure):
+    """mi_isp_statistics: the zone grid (rows, columns), the clip level and the dark level."""
+    _fields_ = [("zones_h", c_int32), ("zones_w", c_int32), ("clip", c_float), ("dark", c_float)]
+
+
 class Highlights(ctypes.Structure):
     """mi_isp_highlights: the mode (0 rebuild, 1 clip), the clip level, the balance gains of R, G, B and, when not NULL,
     3 f32 on the device that override them."""
@@ -241,6 +246,15 @@ SIGNATURES = {
                                                 POINTER(Levels), POINTER(Shading), POINTER(_P), POINTER(GreenEqualize),
                                                 c_int, _P]),
     "mi_isp_green_equalize_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(GreenEqualize), _P]),
+    "mi_isp_statistics_words": (c_int64, [POINTER(Statistics)]),
+    "mi_isp_statistics_geometry": (c_int, [POINTER(c_int32)]),
+    "mi_isp_statistics_strip": (c_int, [c_int, c_int, c_int]),
+    "mi_isp_statistics_direct_blocks": (c_int, [c_int, c_int, c_int, POINTER(Statistics)]),
+    "mi_isp_statistics_raw": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(Levels), POINTER(Defects),
+                                      POINTER(Statistics), _P]),
+    "mi_isp_statistics_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
+                                            POINTER(Levels), POINTER(_P), POINTER(Statistics), _P]),
+    "mi_isp_statistics_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, POINTER(Defects), POINTER(Statistics), _P]),
     "mi_isp_demosaic_directional_cfa": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P]),
     "mi_isp_demosaic_directional_raw_batch": (c_int, [POINTER(_P), POINTER(_P), c_int, c_int, c_int, c_int, c_int, c_int,
                                                       c_int, POINTER(Levels), POINTER(Shading), POINTER(c_float), _P]),

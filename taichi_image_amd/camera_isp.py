@@ -25,6 +25,7 @@ from . import denoise as _dn
 from . import highlights as _hl
 from . import dynamic_defects as _ddp
 from . import green_equalize as _geq
+from . import statistics as _st
 from . import chromatic as _ca
 from . import temporal as _tn
 from . import exposure_merge as _em
@@ -40,12 +41,15 @@ from . import resample as _rs
 from . import white_balance as _wb
 from . import distributed as _dist
 
+_LEAVE = object()                            # set(statistics=): "not given" (None turns the option off)
+
 # the optional stages of Camera16 / Camera32: (constructor / set() argument, attribute, checker), in the order set() checks them
 _OPTIONAL_STAGES = (
     ("raw_denoise", "_raw_denoise", _dn.check_raw_denoise),
     ("highlights", "_highlights", _hl.check_highlights),
     ("dynamic_defects", "_dynamic_defects", _ddp.check_dynamic_defects),
     ("green_equalize", "_green_equalize", _geq.check_green_equalize),
+    ("statistics", "_statistics", _st.check_statistics),
     ("chromatic_aberration", "_chromatic", _ca.check_chromatic_aberration),
     ("temporal_denoise", "_temporal", _tn.check_temporal_denoise),
     ("exposure_merge", "_merge", _em.check_exposure_merge),
@@ -325,7 +329,8 @@ def camera_isp(name: str, dtype=types.f32):
                      demosaic=None,
                      resample=None,
                      dynamic_defects=None,
-                     green_equalize=None):
+                     green_equalize=None,
+                     statistics=None):
             _typecheck("bayer_pattern", bayer_pattern, bayer.BayerPattern)
             _typecheck("scale", scale, float, optional=True)
             _typecheck("resize_width", resize_width, int)
@@ -345,6 +350,7 @@ def camera_isp(name: str, dtype=types.f32):
             highlights = _hl.check_highlights(highlights)
             dynamic_defects = _ddp.check_dynamic_defects(dynamic_defects)
             green_equalize = _geq.check_green_equalize(green_equalize)
+            statistics = _st.check_statistics(statistics)
             chromatic_aberration = _ca.check_chromatic_aberration(chromatic_aberration)
             temporal_denoise = _tn.check_temporal_denoise(temporal_denoise)
             exposure_merge = _em.check_exposure_merge(exposure_merge)
@@ -410,6 +416,12 @@ def camera_isp(name: str, dtype=types.f32):
             # green equalisation (an extension): the GreenEqualize the loaders balance the two green phases with, or None
             # (the loaders run exactly as without it).  DESIGN.md 3, "Green equalisation".
             self._green_equalize = green_equalize
+            # frame statistics (an extension): the Statistics the loaders measure every raw frame with, or None (the
+            # loaders run exactly as without it); frame_statistics: the result of the last loader call, one FrameStatistics
+            # per frame (after a bracket loader one list per bracket with one entry per exposure), None with the option
+            # off.  A side output: no image, no route and no raw stage depends on it.  DESIGN.md 3, "Frame statistics".
+            self._statistics = statistics
+            self.frame_statistics = None
             # chromatic aberration (an extension): the ChromaticAberration the loaders correct on the CFA, or None (the
             # loaders run exactly as without it).  DESIGN.md 3, "Chromatic aberration".
             self._chromatic = chromatic_aberration
@@ -465,7 +477,7 @@ def camera_isp(name: str, dtype=types.f32):
                 raw_denoise=None, sharpen=None, local_contrast=None, chroma_denoise=None, color_lut=None,
                 highlights=None, chromatic_aberration=None, temporal_denoise=None, exposure_merge=None,
                 local_tonemap=None, luma_denoise=None, demosaic=None, resample=None, dynamic_defects=None,
-                green_equalize=None):
+                green_equalize=None, statistics=_LEAVE):
             """camera_isp.py:270-300; black_level / white_level / lens_shading (the extensions): None leaves the current
             value.  lens_shading=False removes the grid.  A grid of the current shape is copied in place on the device's
             current stream (launches queued before on that stream read the old gains, later ones the new; a captured
@@ -490,7 +502,9 @@ def camera_isp(name: str, dtype=types.f32):
             demosaic (the extension): None leaves it, False turns it off, a Demosaic replaces it.
             resample (the extension): None leaves it, False turns it off, a Resample replaces it.
             dynamic_defects (the extension): None leaves it, False turns it off, a DynamicDefects replaces it.
-            green_equalize (the extension): None leaves it, False turns it off, a GreenEqualize replaces it."""
+            green_equalize (the extension): None leaves it, False turns it off, a GreenEqualize replaces it.
+            statistics (the extension): left as it is when not given; None or False turns it off (frame_statistics is None
+            again), a Statistics replaces it."""
             if black_level is not None or white_level is not None:
                 _check_levels(self.black_level if black_level is None else black_level,
                               self.white_level if white_level is None else white_level)
@@ -504,7 +518,8 @@ def camera_isp(name: str, dtype=types.f32):
                          temporal_denoise=temporal_denoise, exposure_merge=exposure_merge, local_tonemap=local_tonemap,
                          sharpen=sharpen, local_contrast=local_contrast, chroma_denoise=chroma_denoise,
                          luma_denoise=luma_denoise, color_lut=color_lut, demosaic=demosaic, resample=resample,
-                         dynamic_defects=dynamic_defects, green_equalize=green_equalize)
+                         dynamic_defects=dynamic_defects, green_equalize=green_equalize,
+                         statistics=None if statistics is _LEAVE else (False if statistics is None else statistics))
             replaced = {name: check(given[name]) for name, _, check in _OPTIONAL_STAGES
                         if given[name] is not None and given[name] is not False}
             _typecheck("moving_alpha", moving_alpha, float, optional=True)
@@ -552,6 +567,8 @@ def camera_isp(name: str, dtype=types.f32):
                     setattr(self, attr, None)
                 elif replaced.get(name) is not None:
                     setattr(self, attr, replaced[name])
+            if self._statistics is None:
+                self.frame_statistics = None
             if replaced.get("color_lut") is not None:
                 replaced["color_lut"]._device_table(self.device)  # (uploaded now: a captured step finds it on the device)
             if auto_white_balance is not None:
@@ -640,6 +657,31 @@ def camera_isp(name: str, dtype=types.f32):
                     _native.ptr_array(srcs), len(srcs), h, w, bits, int(bool(ids_format)), lv,
                     _native.shading_arg(self._shading), float(self._awb.clip), float(self._awb.floor),
                     int(self._awb.stride), self._awb_pending.data_ptr(), _native.stream_ptr(self.device)))
+
+        def _check_statistics_fits(self, shape):
+            """With statistics on, ValueError for a frame shape the statistics cannot take (before anything is uploaded or
+            launched)."""
+            if self._statistics is not None:
+                self._statistics.check_shape(shape)
+
+        def _frame_stats(self, srcs, h, w, kind, ids_format, lv, maps, exposures=None):
+            """With statistics on, the statistics of the raw frames srcs (one shape, source kind `kind`, the call's levels
+            lv, one DefectMap or None per frame) in one launch per 32 frames behind the loads, on their stream, into
+            frame_statistics; nothing with it off.  exposures: the E of a bracket loader, whose srcs hold the E frames
+            of each bracket one after another (maps: one per bracket).  Nothing is read to the host."""
+            if self._statistics is None:
+                self.frame_statistics = None
+                return
+            e = 1 if exposures is None else exposures
+            args = [None if m is None else m._arg(self.device) for m in maps for _ in range(e)]
+            out = _st.measure_raw(srcs, h, w, kind, ids_format, self._demosaic_pattern, lv, args, self._statistics,
+                                  self.device)
+            self.frame_statistics = out if exposures is None else [out[i:i + e] for i in range(0, len(out), e)]
+
+        @property
+        def statistics(self) -> Optional[_st.Statistics]:
+            """The Statistics the loaders measure with, or None."""
+            return self._statistics
 
         def _raw_stage_on(self):
             """True when a loader of single frames goes through _raw_chain."""
@@ -938,6 +980,7 @@ def camera_isp(name: str, dtype=types.f32):
                 self._chromatic.check_shape((h, w))      # (before anything is uploaded or launched)
             hists = _tn.check_histories(self._temporal, None if history is None else [history], 1, (h, w), self.device)
             self._check_resample_fits((h, w))
+            self._check_statistics_fits((h, w))
             L = _native.lib()
             stream = _native.stream_ptr(self.device)
             src = image.to(self.device).contiguous()
@@ -951,6 +994,7 @@ def camera_isp(name: str, dtype=types.f32):
                 if dm is not None:                       # defective pixels: the CFA's listed sites, in place
                     _native.check(L.mi_isp_defects_fix_cfa(cfa.data_ptr(), h, w, dtype.code, dm._arg(self.device), stream))
             self._awb_stats_cfa(src, h, w, mode, lv)     # auto white balance: the statistics of the source
+            self._frame_stats([src], h, w, _native.MI_RAW_16U + mode, False, lv, [dm])
             return self._tone_mapped([self._process_image(cfa, lens)])[0]
 
         def load_16u(self, image, defects=None, undistort=None, history=None):
@@ -1066,6 +1110,7 @@ def camera_isp(name: str, dtype=types.f32):
                                  f"{type(history).__name__}")
             hists = _tn.check_histories(self._temporal, history, len(frames), (h, w), self.device)
             self._check_resample_fits((h, w))
+            self._check_statistics_fits((h, w))
             srcs = [d.to(self.device).contiguous() for d in frames]
             aa = self._antialiased()                     # (every route below then stays at full resolution)
             if self._raw_stage_on():
@@ -1101,6 +1146,8 @@ def camera_isp(name: str, dtype=types.f32):
             if aa:
                 rgbs = self._resampled(rgbs)             # (all images of the call in ONE launch)
             self._awb_stats_packed(srcs, h, w, bits, ids_format, lv)     # auto white balance: the statistics of the sources
+            self._frame_stats(srcs, h, w, _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16, ids_format, lv,
+                              maps)
             return self._tone_mapped(rgbs)
 
         def _load_directional(self, srcs, h, w, bits, ids_format, lv, maps, lenses, keep_size=False):
@@ -1211,6 +1258,7 @@ def camera_isp(name: str, dtype=types.f32):
             _typecheck("images_data", images_data, list)
             if not images_data:
                 _tn.check_histories(self._temporal, history, 0, (0, 0), self.device)
+                self.frame_statistics = None if self._statistics is None else []
                 return []
             return self._load_packed(images_data, 12, ids_format, defects, undistort, True, history)
 
@@ -1220,6 +1268,7 @@ def camera_isp(name: str, dtype=types.f32):
             _typecheck("images_data", images_data, list)
             if not images_data:
                 _tn.check_histories(self._temporal, history, 0, (0, 0), self.device)
+                self.frame_statistics = None if self._statistics is None else []
                 return []
             return self._load_packed(images_data, 16, False, defects, undistort, True, history)
 
@@ -1240,10 +1289,12 @@ def camera_isp(name: str, dtype=types.f32):
                                  "load_16f / load_32f take normalised values")
             if self._chromatic is not None:
                 self._chromatic.check_shape((h, w))
+            self._check_statistics_fits((h, w))
             hists = _tn.check_histories(self._temporal, None if history is None else [history], 1, (h, w), self.device)
             srcs = [f.to(self.device).contiguous() for f in frames]
             cfa = self._raw_chain([srcs[0]], h, w, _native.MI_RAW_16U + mode, False, lv, [dm], hists, brackets=[srcs])[0]
             self._awb_stats_cfa(srcs[0], h, w, mode, lv)   # auto white balance: the statistics of frame 0 (the output's units)
+            self._frame_stats(srcs, h, w, _native.MI_RAW_16U + mode, False, lv, [dm], exposures=len(srcs))
             return self._tone_mapped([self._process_image(cfa, lens)])[0]
 
         def load_16u_bracket(self, frames, defects=None, undistort=None, history=None):
@@ -1277,6 +1328,7 @@ def camera_isp(name: str, dtype=types.f32):
                                  f"{type(history).__name__}")
             if n == 0:
                 _tn.check_histories(self._temporal, history, 0, (0, 0), self.device)
+                self.frame_statistics = None if self._statistics is None else []
                 return []
             f0 = brackets[0][0]
             for i, b in enumerate(brackets):
@@ -1291,6 +1343,7 @@ def camera_isp(name: str, dtype=types.f32):
                 self._chromatic.check_shape((h, w))
             hists = _tn.check_histories(self._temporal, history, n, (h, w), self.device)
             self._check_resample_fits((h, w))
+            self._check_statistics_fits((h, w))
             srcs = [[f.to(self.device).contiguous() for f in b] for b in brackets]
             first = [b[0] for b in srcs]
             kind = _native.MI_RAW_PACKED12 if bits == 12 else _native.MI_RAW_PACKED16
@@ -1300,6 +1353,7 @@ def camera_isp(name: str, dtype=types.f32):
             if aa:
                 rgbs = self._resampled(rgbs)
             self._awb_stats_packed(first, h, w, bits, ids_format, lv)    # auto white balance: each bracket's frame 0
+            self._frame_stats([f for b in srcs for f in b], h, w, kind, ids_format, lv, maps, exposures=len(srcs[0]))
             return self._tone_mapped(rgbs)
 
         def load_packed12_bracket(self, frames, ids_format=False, defects=None, undistort=None, history=None):
@@ -1562,6 +1616,7 @@ def camera_isp(name: str, dtype=types.f32):
                 fused = False                  # (a captured resident launch can be neither ordered against others nor checked)
             if fused:
                 h, w = f0.shape[0], f0.shape[1] * 2 // 3
+                self._check_statistics_fits((h, w))
                 with torch.cuda.device(self.device):
                     fused = bool(group("mi_isp_camera_group_fits", h, w, self._demosaic_pattern.value, dtype.code, 8))
             if not fused:
@@ -1591,6 +1646,7 @@ def camera_isp(name: str, dtype=types.f32):
                         ws.data_ptr())
                 _native.check(group("mi_isp_camera_group_reinhard", *args, tail=(stream,)))
                 self.metrics = metrics
+                self._frame_stats(srcs, h, w, _native.MI_RAW_PACKED12, False, lv, [None] * n)
                 outputs = self._finished(outputs)
                 return (outputs, images) if keep_images else outputs
             # a sharded group (one process per GPU): the same three steps with the metering's two all-gathers in between
@@ -1603,6 +1659,7 @@ def camera_isp(name: str, dtype=types.f32):
             args = (p_srcs, p_imgs, p_outs, n, h, w, self._demosaic_pattern.value, ccm, self.metrics.data_ptr(), float(gamma),
                     float(intensity), float(light_adapt), float(color_adapt), ws.data_ptr())
             _native.check(group("mi_isp_camera_group_tonemap", *args, tail=(stream,)))
+            self._frame_stats(srcs, h, w, _native.MI_RAW_PACKED12, False, lv, [None] * n)
             outputs = self._finished(outputs)
             return (outputs, images) if keep_images else outputs
 

@@ -18,6 +18,7 @@
 #include "isp_highlights.h"
 #include "isp_dynamic_defects.h"
 #include "isp_green_equalize.h"
+#include "isp_statistics.h"
 #include "isp_demosaic_dir.h"
 #include "isp_chromatic.h"
 #include "isp_temporal.h"
@@ -1060,6 +1061,140 @@ extern "C" int mi_isp_green_equalize_cfa(const void* in, void* out, int H, int W
   a.f[0] = {in, out, nullptr};
   return geq::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, dtype == MI_F16 ? hl::OUT_F16 : hl::OUT_F32,
                      green->radius, (hipStream_t)stream);
+}
+
+// ---- frame statistics (isp_statistics.h; DESIGN.md 3, "Frame statistics") --------------------------------------------
+static const RawStage kStatistics = {"statistics", "statistics: ", "frame"};
+
+// the settings and the demosaic pattern, checked on the host; fills the members of a that need no shape
+static int statistics_settings(st::Args& a, const mi_isp_statistics* s, int pattern, const char* who) {
+  static const int first_colour[4] = {0, 1, 1, 2};   // of site (0, 0): RGGB GRBG GBRG BGGR
+  MI_REQUIRE(s, "%s: null statistics settings", who);
+  MI_REQUIRE(s->zones_h >= 1 && s->zones_h <= st::MAX_ZONES && s->zones_w >= 1 && s->zones_w <= st::MAX_ZONES,
+             "%s: statistics zones %dx%d outside 1 .. %d", who, (int)s->zones_h, (int)s->zones_w, st::MAX_ZONES);
+  MI_REQUIRE(std::isfinite(s->clip) && s->clip > 0.f, "%s: statistics clip %g must be finite and > 0", who, (double)s->clip);
+  MI_REQUIRE(std::isfinite(s->dark) && s->dark >= 0.f && s->dark < s->clip,
+             "%s: statistics dark %g must be finite, >= 0 and below clip %g", who, (double)s->dark, (double)s->clip);
+  MI_REQUIRE(pattern >= MI_RGGB && pattern <= MI_BGGR, "%s: bad statistics pattern %d", who, pattern);
+  a.gh = s->zones_h; a.gw = s->zones_w;
+  a.clip = s->clip; a.dark = s->dark;
+  a.gp = first_colour[pattern] == 1 ? 0 : 1;          // (r, c) is green iff ((r + c) & 1) == gp: site (0, 0) tells
+  return 0;
+}
+
+// the shape rules of a frame with pixels: even, at most 2^26 pixels, no zone empty
+static int statistics_shape(const st::Args& a, int H, int W, const char* who) {
+  MI_REQUIRE(H % 2 == 0 && W % 2 == 0, "%s: statistics: frames must be even size, got %dx%d", who, H, W);
+  MI_REQUIRE((long long)H * W <= st::MAX_PIXELS, "%s: statistics: frame %dx%d has more than 2^26 pixels", who, H, W);
+  MI_REQUIRE((H + st::TILE_H - 1) / st::TILE_H <= 65535, "%s: statistics: frame %dx%d has more than 65535 tile rows", who, H,
+             W);
+  MI_REQUIRE(a.gh <= H / 2 && a.gw <= W / 2, "%s: statistics: zones %dx%d exceed the %dx%d quads of the frame", who, a.gh,
+             a.gw, H / 2, W / 2);
+  return 0;
+}
+
+static int statistics_raw_impl(const void* const* src, int64_t* const* out, int n, int H, int W, int kind, int ids_format,
+                               int pattern, const mi_isp_levels* levels, const mi_isp_defects* const* defects,
+                               const mi_isp_statistics* s, void* stream, const char* who) {
+  st::Args a = {};
+  if (int rc = statistics_settings(a, s, pattern, who)) return rc;
+  if (int rc = raw_geometry(H, W, MI_F32, kStatistics, who)) return rc;
+  if (int rc = raw_kind(kind, kStatistics, who)) return rc;
+  MI_REQUIRE(n >= 0, "%s: statistics with %d frames", who, n);
+  if (n == 0 || H == 0 || W == 0) return 0;
+  if (int rc = statistics_shape(a, H, W, who)) return rc;
+  MI_REQUIRE(src && out, "%s: statistics: null frame list", who);
+  for (int i = 0; i < n; ++i) {
+    MI_REQUIRE(src[i] && out[i], "%s: statistics: frame %d has a null pointer", who, i);
+    MI_REQUIRE((uintptr_t)out[i] % 8 == 0, "%s: statistics: the output of frame %d is not aligned to 8 bytes", who, i);
+  }
+  if (int rc = raw_source_rules(H, W, kind, ids_format, nullptr, 0, kStatistics, who)) return rc;
+  int src_kind;
+  if (int rc = raw_source_setup(a, src_kind, H, W, kind, ids_format, levels, nullptr, defects, n, kStatistics, who)) return rc;
+  for (int i0 = 0; i0 < n; i0 += st::MAX_FRAMES) {
+    a.n_frames = n - i0 < st::MAX_FRAMES ? n - i0 : st::MAX_FRAMES;
+    a.strip = st::strip_of(H, W, a.n_frames);
+    for (int i = 0; i < a.n_frames; ++i)
+      a.f[i] = {src[i0 + i], reinterpret_cast<unsigned long long*>(out[i0 + i]), mask_of(defects, i0 + i)};
+    if (int rc = st::launch(a, src_kind, (hipStream_t)stream)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int64_t mi_isp_statistics_words(const mi_isp_statistics* s) {
+  if (!s || s->zones_h < 1 || s->zones_h > st::MAX_ZONES || s->zones_w < 1 || s->zones_w > st::MAX_ZONES) {
+    mi_set_error("statistics_words: statistics zones outside 1 .. %d", st::MAX_ZONES);
+    return -1;
+  }
+  return st::words(s->zones_h, s->zones_w);
+}
+
+extern "C" int mi_isp_statistics_geometry(int32_t out[4]) {
+  MI_REQUIRE(out, "statistics_geometry: null pointer");
+  out[0] = st::TILE_H; out[1] = st::TILE_W; out[2] = st::CELLS; out[3] = st::MAX_STRIP;
+  return 0;
+}
+
+extern "C" int mi_isp_statistics_strip(int n, int H, int W) {
+  if (n <= 0 || n > st::MAX_FRAMES || H <= 0 || W <= 0) {
+    mi_set_error("statistics_strip: statistics: a launch of %d frames of %dx%d", n, H, W);
+    return -1;
+  }
+  return st::strip_of(H, W, n);
+}
+
+extern "C" int mi_isp_statistics_direct_blocks(int n, int H, int W, const mi_isp_statistics* s) {
+  const char* who = "statistics_direct_blocks";
+  st::Args a = {};
+  if (statistics_settings(a, s, MI_RGGB, who) || raw_geometry(H, W, MI_F32, kStatistics, who)) return -1;
+  if (n > st::MAX_FRAMES) {
+    mi_set_error("%s: statistics: a launch takes at most %d frames, got %d", who, st::MAX_FRAMES, n);
+    return -1;
+  }
+  if (n <= 0 || H == 0 || W == 0) return 0;
+  if (statistics_shape(a, H, W, who)) return -1;
+  const int strip = st::strip_of(H, W, n);
+  const int tiles = (W + st::TILE_W - 1) / st::TILE_W, nbx = (tiles + strip - 1) / strip, nby = (H + st::TILE_H - 1) / st::TILE_H;
+  int direct = 0;
+  for (int by = 0; by < nby; ++by)
+    for (int bx = 0; bx < nbx; ++bx) direct += st::lds_route(H, W, a.gh, a.gw, strip, bx, by) ? 0 : 1;
+  return direct;
+}
+
+extern "C" int mi_isp_statistics_raw(const void* src, int64_t* out, int H, int W, int kind, int ids_format, int pattern,
+                                     const mi_isp_levels* levels, const mi_isp_defects* defects,
+                                     const mi_isp_statistics* statistics, void* stream) {
+  return statistics_raw_impl(&src, &out, 1, H, W, kind, ids_format, pattern, levels, &defects, statistics, stream,
+                             "statistics_raw");
+}
+
+extern "C" int mi_isp_statistics_raw_batch(const void* const* src, int64_t* const* out, int n, int H, int W, int kind,
+                                           int ids_format, int pattern, const mi_isp_levels* levels,
+                                           const mi_isp_defects* const* defects, const mi_isp_statistics* statistics,
+                                           void* stream) {
+  return statistics_raw_impl(src, out, n, H, W, kind, ids_format, pattern, levels, defects, statistics, stream,
+                             "statistics_raw_batch");
+}
+
+extern "C" int mi_isp_statistics_cfa(const void* cfa, int64_t* out, int H, int W, int dtype, int pattern,
+                                     const mi_isp_defects* defects, const mi_isp_statistics* statistics, void* stream) {
+  const char* who = "statistics_cfa";
+  st::Args a = {};
+  if (int rc = statistics_settings(a, statistics, pattern, who)) return rc;
+  if (int rc = raw_geometry(H, W, dtype, kStatistics, who)) return rc;
+  if (H == 0 || W == 0) return 0;
+  if (int rc = statistics_shape(a, H, W, who)) return rc;
+  MI_REQUIRE(cfa && out, "%s: statistics: null pointer", who);
+  MI_REQUIRE((uintptr_t)out % 8 == 0, "%s: statistics: the output of frame 0 is not aligned to 8 bytes", who);
+  if (defects) {
+    MI_REQUIRE(defects->n >= 0, "%s: statistics: negative defect count %d", who, (int)defects->n);
+    MI_REQUIRE(defects->n == 0 || defects->mask_dev, "%s: statistics: frame 0: defects without a mask", who);
+  }
+  a.H = H; a.W = W; a.mask_w = (W + 31) / 32;
+  a.n_frames = 1;
+  a.strip = st::strip_of(H, W, 1);
+  a.f[0] = {cfa, reinterpret_cast<unsigned long long*>(out), mask_of(&defects, 0)};
+  return st::launch(a, dtype == MI_F16 ? raw::SRC_CFA_F16 : raw::SRC_CFA_F32, (hipStream_t)stream);
 }
 
 // ---- directional demosaic (isp_demosaic_dir.h; DESIGN.md 3, "Directional demosaic") ---------------------------------

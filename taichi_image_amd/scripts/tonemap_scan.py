@@ -11,6 +11,7 @@ Host side without OpenCV / natsort / tqdm: grids are written as PNG, nothing is 
 from __future__ import annotations
 
 import argparse
+import json
 import re
 import struct
 import zipfile
@@ -156,6 +157,19 @@ def load_lens_distortion(directory, cameras: Sequence[Path]) -> Dict[str, dict]:
     return lenses
 
 
+def statistics_report(settings, cameras, measured):
+    """The content of <name>.stats.json: per camera the per-zone means, clipped and dark fractions (zone rows x zone
+    columns x the four CFA sites), the sharpness per zone and the 1 / 50 / 99 % percentiles per site; NaN (an empty zone,
+    a zone without a focus pixel) is written as null."""
+    def plain(a):
+        return [plain(v) for v in a] if isinstance(a, list) else (None if a != a else a)
+    return {"zones": list(settings.zones), "clip": settings.clip, "dark": settings.dark,
+            "cameras": {name: {"mean": plain(m.mean().tolist()), "clipped_fraction": plain(m.clipped_fraction().tolist()),
+                               "dark_fraction": plain(m.dark_fraction().tolist()), "sharpness": plain(m.sharpness().tolist()),
+                               "percentiles": {str(q): plain([m.percentile(q, site) for site in range(4)]) for q in (1, 50, 99)}}
+                        for name, m in zip(cameras, measured)}}
+
+
 def build_parser() -> argparse.ArgumentParser:
     """The argument surface of scripts/tonemap_scan.py:104-128 (+ --device, --ids_format)."""
     from ..interpolate import ImageTransform
@@ -220,6 +234,9 @@ def build_parser() -> argparse.ArgumentParser:
     tone.add_argument("--green-equalize-strength", dest="green_equalize_strength", type=float, metavar="A", default=None)
     tone.add_argument("--green-equalize-radius", dest="green_equalize_radius", type=int, metavar="R", default=None)
     tone.add_argument("--green-equalize-edge", dest="green_equalize_edge", type=float, metavar="E", default=None)
+    # frame statistics (an extension): the exposure and focus measurements of every raw frame over GH x GW zones, written
+    # as <name>.stats.json next to each output (--write)
+    tone.add_argument("--statistics", dest="statistics", type=str, metavar="GHxGW", default=None)
     # the demosaic (an extension): "directional" interpolates along edges instead of across them; "malvar" (the default)
     # is the 13-tap filter
     tone.add_argument("--demosaic", dest="demosaic", choices=("malvar", "directional"), default=None)
@@ -289,6 +306,7 @@ def main(argv=None) -> int:
     from ..highlights import Highlights
     from ..dynamic_defects import DynamicDefects
     from ..green_equalize import GreenEqualize
+    from ..statistics import Statistics
     from ..demosaic import Demosaic
     from ..resample import Resample
     from ..chromatic import ChromaticAberration
@@ -335,6 +353,12 @@ def main(argv=None) -> int:
         green = GreenEqualize(**{k: v for k, v in geq.items() if v is not None})
     elif any(v is not None for v in geq.values()):
         raise ValueError("--green-equalize-threshold, -slope, -strength, -radius and -edge need --green-equalize")
+    statistics = None
+    if args.statistics is not None:                                 # (also before any frame is read)
+        parts = args.statistics.lower().split("x")
+        if len(parts) != 2 or not all(p.isdigit() for p in parts):
+            raise ValueError(f"--statistics takes GHxGW (two integers, e.g. 8x8), got {args.statistics!r}")
+        statistics = Statistics(zones=(int(parts[0]), int(parts[1])))
     chromatic = None
     if args.chromatic_aberration is not None:                       # (also before any frame is read)
         k = args.chromatic_aberration
@@ -403,7 +427,7 @@ def main(argv=None) -> int:
                               local_tonemap=local_tonemap, luma_denoise=luma_denoise,
                               demosaic=None if args.demosaic is None else Demosaic(args.demosaic),
                               resample=None if args.resample is None else Resample(args.resample),
-                              dynamic_defects=dynamic, green_equalize=green)
+                              dynamic_defects=dynamic, green_equalize=green, statistics=statistics)
     # temporal noise reduction: the state of each camera folder, for the whole scan
     histories = [TemporalHistory() if temporal is not None else None for _ in index.cameras]
     row_bytes = args.width * 3 // 2
@@ -418,14 +442,20 @@ def main(argv=None) -> int:
             shape = (frames[0].shape[0], args.width)
             maps = [DefectMap(coords[c.name], shape) if c.name in coords else None for c in index.cameras]
             lenses = [LensDistortion(shape=shape, **calib[c.name]) if c.name in calib else None for c in index.cameras]
-        images = [isp.load_packed12(f, ids_format=args.ids_format, defects=m, undistort=ln, history=hist)
-                  for f, m, ln, hist in zip(frames, maps, lenses, histories)]
+        images, measured = [], []
+        for f, m, ln, hist in zip(frames, maps, lenses, histories):
+            images.append(isp.load_packed12(f, ids_format=args.ids_format, defects=m, undistort=ln, history=hist))
+            measured.extend(isp.frame_statistics or [])
         outputs = isp.tonemap_reinhard(images, gamma=args.gamma, intensity=args.intensity,
                                        color_adapt=args.color_adapt, light_adapt=args.light_adapt)
         if args.write is not None:
             target = args.write / (Path(name).stem + ".png")
             write_png(target, tile_grid(outputs, args.rows).cpu().numpy())
             print(f"wrote {target}")
+            if statistics is not None:
+                target = args.write / (Path(name).stem + ".stats.json")
+                target.write_text(json.dumps(statistics_report(statistics, [c.name for c in index.cameras], measured)))
+                print(f"wrote {target}")
         done += 1
     print(f"processed {done} frame group(s) from {len(index.cameras)} camera(s)")
     return 0
